@@ -5,6 +5,11 @@ A step = UnifiedModel.compress + UnifiedModel.decompress of one synthetic longdr
 (~0.79 M voxels, one block, R2 architecture `configs/CVPR_inverse_scaling_fixed_R2.yaml`, q = [[0.5, 0.5]]), input
 resident in HBM, timed like `utils.py:454-465` (sync, wall clock, sync).  Each rank codes its own frame (weak
 scaling, no data-path collective); rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times `--steps` steps and prints the headline line.  `--full` adds every diagnostic pass
+behind it: FLOP accounting and the event-timed roofline, the strict / fp32 / cached-decoder passes, the step without the
+entropy coder, rate / distortion against the oracle, the true-geometry and train-step figures and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step returned (bitstreams, latent coordinates, decoded points) as .npy.
 """
 import argparse
 import json
@@ -426,6 +431,151 @@ def self_launch(args):
     return subprocess.run(cmd, env=env).returncode
 
 
+DUMP_BYTES = 60 * 10 ** 6   # cap of the array data one --dump-outputs directory holds (under 64 MB with the .npy headers)
+
+
+def _dump_array(x):
+    """One returned value as a float array: bytes -> their byte values, integers -> float32 (float64 past 2^24)."""
+    if isinstance(x, (bytes, bytearray)):
+        a = np.frombuffer(bytes(x), dtype=np.uint8)
+    elif torch.is_tensor(x):
+        a = x.detach().cpu().numpy()
+    else:
+        a = np.asarray(x)
+    if a.dtype in (np.float32, np.float64):
+        return np.ascontiguousarray(a)
+    if a.dtype.kind in "iub" and a.size and int(np.abs(a.astype(np.int64)).max()) >= 1 << 24:
+        return a.astype(np.float64)
+    return a.astype(np.float32)
+
+
+def dump_outputs(path, out, rec):
+    """What a caller of the timed step receives, as DIR/<name>.npy: per block b the byte strings (`strings_b<b>_<i>..`,
+    i = 0 latent, 1 hyper-latent), `shape_b<b>`, `k_b<b>`, `coordinates_b<b>` (latent coordinates) and `q_vals_b<b>`;
+    and the decoded points (`reconstruction`, [N, 6]).  Past DUMP_BYTES in all, the largest arrays keep a seeded sample
+    of their rows (same rows for the same row count)."""
+    strings, shapes, ks, coords, q_vals = out
+    arrays = {}
+
+    def flat(name, x):           # nested lists of numbers become one array; lists of strings / tensors one array per item
+        if isinstance(x, (list, tuple)):
+            try:
+                a = np.asarray(x)
+            except (ValueError, TypeError):
+                a = None
+            if a is None or a.dtype.kind not in "iubf":
+                for i, v in enumerate(x):
+                    flat(f"{name}_{i}", v)
+                return
+        arrays[name] = _dump_array(x)
+
+    for b in range(len(strings)):
+        for nme, v in (("strings", strings), ("shape", shapes), ("k", ks), ("coordinates", coords), ("q_vals", q_vals)):
+            flat(f"{nme}_b{b}", v[b])
+    flat("reconstruction", rec)
+    total = sum(a.nbytes for a in arrays.values())
+    for name in sorted(arrays, key=lambda n: -arrays[n].nbytes):
+        if total <= DUMP_BYTES:
+            break
+        a = arrays[name]
+        rest = total - a.nbytes
+        keep = max(1, int(a.shape[0] * max(DUMP_BYTES - rest, 0) / a.nbytes)) if a.ndim else 1
+        if a.ndim and keep < a.shape[0]:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            arrays[name] = a[rows]
+            total = rest + arrays[name].nbytes
+            print(f"bench: {name}: {keep} of {a.shape[0]} rows dumped (seeded sample)", file=sys.stderr)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def roofline(forms, flops_by_form, flops_step, exec_flops_step, alg_bytes_step, launches_step, pairs_step):
+    """The `roofline` entry of a --full line: event-timed kernel forms priced by SURVEY 8d (see the note it carries)."""
+    # ---- roofline (SURVEY 8d accounting; VERDICT r3 item 4) ----------------------------------------------------------------
+    # Every event-timed kernel form is priced with the ALGORITHMIC work of the layers it ran: FLOP = 2 P Cin Cout and
+    # BYTES = 4 (N_in Cin + N_out Cout + K Cin Cout) + 8 P + 16 (N_in + N_out) -- the layer's compulsory traffic; buffers
+    # the design adds (the per-pair products T) count as `traffic`, never as useful bytes.  The DOMINANT kernel is the form
+    # with the most time per step; `unit` prices the SURVEY 8d unit it belongs to (a composite level = dense products +
+    # ordered gather-sum) the same way.
+    kernels = {}
+    for nme, f in forms.items():
+        if f["launches_per_step"] <= 0 or nme == "k_convt_gather_csr":
+            continue
+        bf = flops_by_form.get(nme, {})
+        fl, by8 = bf.get("flops", 0.0), bf.get("bytes_8d", 0.0)           # per step (one accounting step)
+        sec = f["ms_per_step"] * 1e-3
+        roof_t = PEAK_BF16_MFMA_TFLOPS / FORM_TERMS[nme]
+        k = {"ms_per_step": f["ms_per_step"], "launches_per_step": f["launches_per_step"],
+             "alg_tflops": fl / sec / 1e12 if sec > 0 else None, "mfma_roof_tflops": roof_t,
+             "alg_gbs_8d": by8 / sec / 1e9 if sec > 0 else None}
+        k["mfma_frac"] = k["alg_tflops"] / roof_t if k["alg_tflops"] else None
+        k["hbm_frac"] = k["alg_gbs_8d"] / PEAK_HBM_GBS if k["alg_gbs_8d"] else None
+        k["flop_per_byte"] = fl / by8 if by8 else None
+        ridge = roof_t * 1e12 / (PEAK_HBM_GBS * 1e9)
+        k["bound"] = "hbm" if (k["flop_per_byte"] is not None and k["flop_per_byte"] < ridge) else "mfma"
+        if f["bytes"] > 0:      # dense products: operand + RESULT stream of the kernel itself (counts the product buffer T)
+            k["kernel_stream_gbs"] = f["bytes"] / sec / 1e9
+            k["kernel_stream_frac"] = k["kernel_stream_gbs"] / PEAK_HBM_GBS
+        kernels[nme] = k
+    dom = max(kernels, key=lambda n: kernels[n]["ms_per_step"]) if kernels else None
+    d, df = (kernels[dom], forms[dom]) if dom else ({}, {})
+    traffic, traffic_note = pmc_traffic(dom) if dom else (None, "no timed launches")
+    conv_ms = sum(k["ms_per_step"] for k in kernels.values())
+    fam_ach = flops_step / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else None
+    fam_peak = PEAK_BF16_MFMA_TFLOPS * flops_step / exec_flops_step if exec_flops_step else PEAK_FP32_MFMA_TFLOPS
+    lps = max(df.get("launches_per_step", 0), 1e-9)
+    bf = flops_by_form.get(dom, {}) if dom else {}
+    alg_b = bf.get("bytes_8d", 0.0) / lps if bf else None
+    alg_f = bf.get("flops", 0.0) / lps if bf else None
+    if d.get("bound") == "hbm":
+        roof = {"bound": "hbm", "achieved": d.get("alg_gbs_8d"), "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": d.get("hbm_frac")}
+    else:
+        roof = {"bound": "mfma", "achieved": d.get("alg_tflops"), "peak": d.get("mfma_roof_tflops"), "unit": "TFLOP/s",
+                "frac": d.get("mfma_frac")}
+    # the SURVEY 8d unit of the composite levels: dense products (k_gemm_h2) + ordered gather-sum (k_convt_gather_csr)
+    unit = None
+    gat = forms.get("k_convt_gather_csr")
+    if dom == "k_gemm_h2" and gat and gat["launches_per_step"] > 0:
+        u_ms = df["ms_per_step"] + gat["ms_per_step"]
+        # (the PMC run also holds the small gather-sums of the hyper-synthesis under the same kernel name: their traffic is
+        #  negligible, so ALL gather-sum bytes of the run are divided by the run's composite levels = its k_gemm_h2 launches)
+        g_bytes, _ = pmc_total("k_convt_gather_csr")
+        m_bytes, m_launches = pmc_total("k_gemm_h2")
+        u_note = "k_gemm_h2 + k_convt_gather_csr entries of " + PMC_FILE
+        ut = ((m_bytes + g_bytes) / m_launches) if (g_bytes and m_bytes and m_launches) else None
+        unit = {"name": "composite level = k_gemm_h2 + k_convt_gather_csr (pcc_convt_fwd_csr_grid)",
+                "units_per_step": lps, "ms_per_unit": u_ms / lps, "alg_flops_per_unit": alg_f, "alg_bytes_per_unit": alg_b,
+                "alg_tflops": bf["flops"] / (u_ms * 1e-3) / 1e12, "mfma_frac": bf["flops"] / (u_ms * 1e-3) / 1e12 / d["mfma_roof_tflops"],
+                "alg_gbs": bf["bytes_8d"] / (u_ms * 1e-3) / 1e9, "hbm_frac": bf["bytes_8d"] / (u_ms * 1e-3) / 1e9 / PEAK_HBM_GBS,
+                "traffic": ut, "traffic_over_alg_bytes": (ut / alg_b) if (ut and alg_b) else None,
+                "traffic_source": u_note, "layers": bf.get("layers")}
+    roof.update({
+        "kernel": dom, "traffic": traffic, "traffic_unit": "HBM bytes per launch", "traffic_source": traffic_note,
+        "alg_bytes_per_launch": alg_b, "alg_flops_per_launch": alg_f,
+        "traffic_over_alg_bytes": (traffic / alg_b) if (traffic and alg_b) else None,
+        "avg_launch_ms": df.get("ms_per_step", 0.0) / lps, "launches_per_step": df.get("launches_per_step"),
+        "mfma_frac": d.get("mfma_frac"), "hbm_frac": d.get("hbm_frac"), "flop_per_byte": d.get("flop_per_byte"),
+        "kernel_stream_frac": d.get("kernel_stream_frac"), "kernel_stream_gbs": d.get("kernel_stream_gbs"),
+        "unit": unit,
+        "note": ("dominant kernel = the event-timed form with the most time per step, priced by SURVEY 8d: algorithmic FLOPs = "
+                 "2 x pairs x Cin x Cout of the layers it ran, algorithmic bytes = 4 (N_in Cin + N_out Cout + K Cin Cout) + 8 pairs + "
+                 "16 (N_in + N_out) -- the per-pair product buffer T is NOT counted (it shows up in `traffic`); `kernel_stream_frac` "
+                 "is the kernel's own operand + result stream (T included) against the HBM peak, the figure rounds 2-3 printed as "
+                 "`frac`; `unit` = the composite level the kernel is half of.  Durations: HIP events on the launch stream, recorded "
+                 "inside the library in a separate pass (never inside the loop `value` is timed on); mfma roof = dense 16-bit MFMA "
+                 "peak 2500 TFLOP/s / MFMA terms per product of the form"),
+        "kernels": kernels,
+        # all event-timed MFMA launches together (round-2 style figure, kept for comparison across rounds)
+        "mfma_family": {"achieved": fam_ach, "peak": fam_peak, "unit": "TFLOP/s", "frac": (fam_ach / fam_peak) if fam_ach else None,
+                        "executed_16bit_tflops": (fam_ach * exec_flops_step / flops_step) if (fam_ach and flops_step) else None,
+                        "vs_fp32_mfma_peak": (fam_ach / PEAK_FP32_MFMA_TFLOPS) if fam_ach else None,
+                        "flop_per_step": flops_step, "pairs_per_step": pairs_step, "launches_per_step": launches_step,
+                        "conv_ms_per_step": conv_ms, "alg_bytes_per_launch_survey_8d": (alg_bytes_step / launches_step) if launches_step else None},
+    })
+    return roof
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -436,7 +586,15 @@ def main():
     ap.add_argument("--coder", default="pcc_streams", choices=["pcc_streams", "ans", "symbols"],
                     help="entropy coder inside the timed region (default: per-channel GPU rANS)")
     ap.add_argument("--no-aux", action="store_true", help="skip the auxiliary (un-timed) true-geometry and train-step figures")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every diagnostic pass: FLOP accounting, event-timed roofline, strict / "
+                         "fp32 / cached-decoder passes, step without the entropy coder, rate / distortion, auxiliary figures "
+                         "and the CPU baseline (--no-aux / --no-cpu-baseline drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -477,7 +635,7 @@ def main():
         step(model, pc, q)
     torch.cuda.synchronize()
     (flops_step, launches_step, pairs_step, alg_bytes_step, exec_flops_step, flops_by_form) = (
-        account_flops(model, pc, q) if rank == 0 else (0.0, 0, 0, 0.0, 0.0, {}))
+        account_flops(model, pc, q) if (rank == 0 and args.full) else (0.0, 0, 0, 0.0, 0.0, {}))
 
     def timed_loop(steps, reuse_encoder_sets=False, all_ranks=True):
         """EXACTLY `steps` steps between barrier + synchronize on both sides.  The decoder gets PLAIN coordinate tensors
@@ -518,11 +676,16 @@ def main():
     diag = frames.gather_records([(rank, t_enc / args.steps * 1e3, (dt - t_enc) / args.steps * 1e3, dt / args.steps * 1e3, min(steps_ms),
                                    max(steps_ms), len(cores), cores[0] if cores else -1)], coll_device, n_fields=8)
     total_points = sum(r[1] for r in recs)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rec)
+
+    # everything below (rank 0, --full only) is diagnostics beside the headline
+    full = rank == 0 and args.full
 
     # pass 2 (rank 0, un-timed for `value`): the same steps with a HIP-event pair around every MFMA launch, recorded on the
     # launch stream inside the library -> launch durations by kernel form (roofline)
     forms = None
-    if rank == 0:
+    if full:
         lib.call("pcc_prof_enable", 1)
         ev_steps = min(args.steps, 10)
         for _ in range(ev_steps):
@@ -540,7 +703,7 @@ def main():
     # beside the headline: dense / pair products as six bf16 terms (24-bit split of both operands) instead of three fp16
     # terms; and every product on the fp32-input MFMA instructions
     strict_ms = fp32_ms = cached_dec_ms = None
-    if rank == 0 and not args.no_aux:
+    if full and not args.no_aux:
         def quick(n=5, **kw):
             for _ in range(2):
                 step(model, pc, q, **kw)
@@ -558,7 +721,7 @@ def main():
     # auxiliary (un-timed for `value`): the same step with integer symbols handed across the entropy-coder boundary,
     # i.e. the SURVEY 8a hot path alone (sparse convolutions + likelihood kernels), for comparison across rounds
     hot_ms = None
-    if rank == 0 and args.coder != "symbols":
+    if full and args.coder != "symbols":
         m2 = build_model(device, coder="symbols")
         m2.load_state_dict(model.state_dict())
         for _ in range(2):
@@ -574,12 +737,12 @@ def main():
 
     def count_bits(strings):   # `utils.count_bits` (utils.py:30-48)
         return sum(count_bits(x) if isinstance(x, list) else len(x) * 8 for x in strings)
-    bpp = (count_bits(out[0]) / n_points) if args.coder != "symbols" else None
+    bpp = (count_bits(out[0]) / n_points) if (full and args.coder != "symbols") else None
 
     # rate / distortion of the coded frame (un-timed): -sum log2 p / N (`loss.py:77-79`) and the D1 report of
     # `metrics/metric.py:113-118,74` on the GPU, next to the oracle's figures for the same frame and weights
     rd = None
-    if rank == 0:
+    if full:
         from unified_point_cloud_compression_amd import metrics
         y, _ = model.g_a(model.block_input(pc))
         y_lik, z_lik = model.entropy_model.likelihoods(y, q)
@@ -591,87 +754,6 @@ def main():
     if rank == 0:
         split_on = lib.ARITH_DEFAULT != lib.ARITH_F32
         ms_step = dt_max / args.steps * 1e3
-        # ---- roofline (SURVEY 8d accounting) ----------------------------------------------------------------
-        # Every event-timed kernel form is priced with the ALGORITHMIC work of the layers it ran: FLOP = 2 P Cin Cout and
-        # BYTES = 4 (N_in Cin + N_out Cout + K Cin Cout) + 8 P + 16 (N_in + N_out) -- the layer's compulsory traffic; buffers
-        # the design adds (the per-pair products T) count as `traffic`, never as useful bytes.  The DOMINANT kernel is the form
-        # with the most time per step; `unit` prices the SURVEY 8d unit it belongs to (a composite level = dense products +
-        # ordered gather-sum) the same way.
-        kernels = {}
-        for nme, f in forms.items():
-            if f["launches_per_step"] <= 0 or nme == "k_convt_gather_csr":
-                continue
-            bf = flops_by_form.get(nme, {})
-            fl, by8 = bf.get("flops", 0.0), bf.get("bytes_8d", 0.0)           # per step (one accounting step)
-            sec = f["ms_per_step"] * 1e-3
-            roof_t = PEAK_BF16_MFMA_TFLOPS / FORM_TERMS[nme]
-            k = {"ms_per_step": f["ms_per_step"], "launches_per_step": f["launches_per_step"],
-                 "alg_tflops": fl / sec / 1e12 if sec > 0 else None, "mfma_roof_tflops": roof_t,
-                 "alg_gbs_8d": by8 / sec / 1e9 if sec > 0 else None}
-            k["mfma_frac"] = k["alg_tflops"] / roof_t if k["alg_tflops"] else None
-            k["hbm_frac"] = k["alg_gbs_8d"] / PEAK_HBM_GBS if k["alg_gbs_8d"] else None
-            k["flop_per_byte"] = fl / by8 if by8 else None
-            ridge = roof_t * 1e12 / (PEAK_HBM_GBS * 1e9)
-            k["bound"] = "hbm" if (k["flop_per_byte"] is not None and k["flop_per_byte"] < ridge) else "mfma"
-            if f["bytes"] > 0:      # dense products: operand + RESULT stream of the kernel itself (counts the product buffer T)
-                k["kernel_stream_gbs"] = f["bytes"] / sec / 1e9
-                k["kernel_stream_frac"] = k["kernel_stream_gbs"] / PEAK_HBM_GBS
-            kernels[nme] = k
-        dom = max(kernels, key=lambda n: kernels[n]["ms_per_step"]) if kernels else None
-        d, df = (kernels[dom], forms[dom]) if dom else ({}, {})
-        traffic, traffic_note = pmc_traffic(dom) if dom else (None, "no timed launches")
-        conv_ms = sum(k["ms_per_step"] for k in kernels.values())
-        fam_ach = flops_step / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else None
-        fam_peak = PEAK_BF16_MFMA_TFLOPS * flops_step / exec_flops_step if exec_flops_step else PEAK_FP32_MFMA_TFLOPS
-        lps = max(df.get("launches_per_step", 0), 1e-9)
-        bf = flops_by_form.get(dom, {}) if dom else {}
-        alg_b = bf.get("bytes_8d", 0.0) / lps if bf else None
-        alg_f = bf.get("flops", 0.0) / lps if bf else None
-        if d.get("bound") == "hbm":
-            roof = {"bound": "hbm", "achieved": d.get("alg_gbs_8d"), "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": d.get("hbm_frac")}
-        else:
-            roof = {"bound": "mfma", "achieved": d.get("alg_tflops"), "peak": d.get("mfma_roof_tflops"), "unit": "TFLOP/s",
-                    "frac": d.get("mfma_frac")}
-        # the SURVEY 8d unit of the composite levels: dense products (k_gemm_h2) + ordered gather-sum (k_convt_gather_csr)
-        unit = None
-        gat = forms.get("k_convt_gather_csr")
-        if dom == "k_gemm_h2" and gat and gat["launches_per_step"] > 0:
-            u_ms = df["ms_per_step"] + gat["ms_per_step"]
-            # (the PMC run also holds the small gather-sums of the hyper-synthesis under the same kernel name: their traffic is
-            #  negligible, so ALL gather-sum bytes of the run are divided by the run's composite levels = its k_gemm_h2 launches)
-            g_bytes, _ = pmc_total("k_convt_gather_csr")
-            m_bytes, m_launches = pmc_total("k_gemm_h2")
-            u_note = "k_gemm_h2 + k_convt_gather_csr entries of " + PMC_FILE
-            ut = ((m_bytes + g_bytes) / m_launches) if (g_bytes and m_bytes and m_launches) else None
-            unit = {"name": "composite level = k_gemm_h2 + k_convt_gather_csr (pcc_convt_fwd_csr_grid)",
-                    "units_per_step": lps, "ms_per_unit": u_ms / lps, "alg_flops_per_unit": alg_f, "alg_bytes_per_unit": alg_b,
-                    "alg_tflops": bf["flops"] / (u_ms * 1e-3) / 1e12, "mfma_frac": bf["flops"] / (u_ms * 1e-3) / 1e12 / d["mfma_roof_tflops"],
-                    "alg_gbs": bf["bytes_8d"] / (u_ms * 1e-3) / 1e9, "hbm_frac": bf["bytes_8d"] / (u_ms * 1e-3) / 1e9 / PEAK_HBM_GBS,
-                    "traffic": ut, "traffic_over_alg_bytes": (ut / alg_b) if (ut and alg_b) else None,
-                    "traffic_source": u_note, "layers": bf.get("layers")}
-        roof.update({
-            "kernel": dom, "traffic": traffic, "traffic_unit": "HBM bytes per launch", "traffic_source": traffic_note,
-            "alg_bytes_per_launch": alg_b, "alg_flops_per_launch": alg_f,
-            "traffic_over_alg_bytes": (traffic / alg_b) if (traffic and alg_b) else None,
-            "avg_launch_ms": df.get("ms_per_step", 0.0) / lps, "launches_per_step": df.get("launches_per_step"),
-            "mfma_frac": d.get("mfma_frac"), "hbm_frac": d.get("hbm_frac"), "flop_per_byte": d.get("flop_per_byte"),
-            "kernel_stream_frac": d.get("kernel_stream_frac"), "kernel_stream_gbs": d.get("kernel_stream_gbs"),
-            "unit": unit,
-            "note": ("dominant kernel = the event-timed form with the most time per step, priced by SURVEY 8d: algorithmic FLOPs = "
-                     "2 x pairs x Cin x Cout of the layers it ran, algorithmic bytes = 4 (N_in Cin + N_out Cout + K Cin Cout) + 8 pairs + "
-                     "16 (N_in + N_out) -- the per-pair product buffer T is NOT counted (it shows up in `traffic`); `kernel_stream_frac` "
-                     "is the kernel's own operand + result stream (T included) against the HBM peak, the figure rounds 2-3 printed as "
-                     "`frac`; `unit` = the composite level the kernel is half of.  Durations: HIP events on the launch stream, recorded "
-                     "inside the library in a separate pass (never inside the loop `value` is timed on); mfma roof = dense 16-bit MFMA "
-                     "peak 2500 TFLOP/s / MFMA terms per product of the form"),
-            "kernels": kernels,
-            # all event-timed MFMA launches together (round-2 style figure, kept for comparison across rounds)
-            "mfma_family": {"achieved": fam_ach, "peak": fam_peak, "unit": "TFLOP/s", "frac": (fam_ach / fam_peak) if fam_ach else None,
-                            "executed_16bit_tflops": (fam_ach * exec_flops_step / flops_step) if (fam_ach and flops_step) else None,
-                            "vs_fp32_mfma_peak": (fam_ach / PEAK_FP32_MFMA_TFLOPS) if fam_ach else None,
-                            "flop_per_step": flops_step, "pairs_per_step": pairs_step, "launches_per_step": launches_step,
-                            "conv_ms_per_step": conv_ms, "alg_bytes_per_launch_survey_8d": (alg_bytes_step / launches_step) if launches_step else None},
-        })
         line = {
             "metric": "points/sec encode+decode, longdress vox10, 1 GPU; bpp & D1-PSNR parity",
             "value": total_points * args.steps / dt_max,
@@ -691,24 +773,27 @@ def main():
                                       "tests/test_gpu_fp16_pairs.py). `ms_per_step_strict` is the same step with every product "
                                       "on the six-term 24-bit form, `ms_per_step_fp32_mfma` on the fp32-input MFMA instructions")
                        if split_on else "fp32-input MFMA",
-                       "ms_per_step_strict": strict_ms, "ms_per_step_fp32_mfma": fp32_ms,
-                       "decode_ms_reusing_encoder_sets": cached_dec_ms,
-                       "bpp_y_z_strings": bpp, "bpp_likelihood": rd["bpp_likelihood"], "d1_psnr": rd["d1_psnr_sym"],
-                       "rate_distortion": rd, "ms_per_step_without_entropy_coder": hot_ms,
                        "frames_per_step": world, "encode_ms": recs[0][2] * 1e3, "decode_ms": recs[0][3] * 1e3,
                        "step_ms_rank0": [round((b - a) * 1e3, 2) for a, b in zip(step_marks[:-1], step_marks[1:])],
                        "per_rank": [{"rank": int(d[0]), "encode_ms": round(d[1], 3), "decode_ms": round(d[2], 3), "ms_per_step": round(d[3], 3),
                                      "step_ms_min": round(d[4], 3), "step_ms_max": round(d[5], 3), "host_cores": int(d[6]),
                                      "first_core": int(d[7])} for d in diag],
                        "device": arch, "cus": cu},
-            "roofline": roof,
         }
+        if full:
+            line["config"].update({
+                "ms_per_step_strict": strict_ms, "ms_per_step_fp32_mfma": fp32_ms,
+                "decode_ms_reusing_encoder_sets": cached_dec_ms,
+                "bpp_y_z_strings": bpp, "bpp_likelihood": rd["bpp_likelihood"], "d1_psnr": rd["d1_psnr_sym"],
+                "rate_distortion": rd, "ms_per_step_without_entropy_coder": hot_ms})
+            line["roofline"] = roofline(forms, flops_by_form, flops_step, exec_flops_step, alg_bytes_step, launches_step,
+                                        pairs_step)
         if rehearse:
             line["rehearsal"] = f"{world} ranks sharing ONE GPU, collectives over gloo: a control-flow check, not a measurement"
-        if world == 1 and not args.no_aux:
+        if full and world == 1 and not args.no_aux:
             line["config"]["aux_true_geometry"] = true_geometry_ms(model, pc, q)
             line["config"]["aux_train_step"] = train_step_ms(device)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), flush=True)
     if world > 1:

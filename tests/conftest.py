@@ -10,7 +10,6 @@ if ROOT not in sys.path:
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with `-m gpu` on the GPU box)")
-    config.addinivalue_line("markers", "reference: needs /root/reference (this container only)")
 
 
 def _has_gpu():
@@ -23,12 +22,9 @@ def _has_gpu():
 
 def pytest_collection_modifyitems(config, items):
     has_gpu = _has_gpu()
-    has_ref = os.path.isdir("/root/reference/model")
     for item in items:
         if "gpu" in item.keywords and not has_gpu:
             item.add_marker(pytest.mark.skip(reason="no GPU in this container"))
-        if "reference" in item.keywords and not has_ref:
-            item.add_marker(pytest.mark.skip(reason="/root/reference not present"))
 
 
 @pytest.fixture(autouse=True)

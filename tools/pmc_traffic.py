@@ -22,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import csrc_sha  # noqa: E402
 
 KERNELS = ("k_conv_mfma", "k_conv_wave16", "k_gemm_bf2", "k_gemm_h2", "k_pair_h2", "k_convt_gather_csr")
-BENCH = ["python3", "bench.py", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-aux", "--coder", "symbols"]
+BENCH = ["python3", "bench.py", "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-aux", "--coder", "symbols"]
 
 
 def collect(out):

@@ -25,7 +25,7 @@ import sys
 
 PASSES = (("p1", "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_MFMA"),
           ("p2", "GRBM_GUI_ACTIVE SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU"))
-BENCH = ["python3", "bench.py", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-aux", "--coder", "symbols"]
+BENCH = ["python3", "bench.py", "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-aux", "--coder", "symbols"]
 KERNELS = r"k_gemm_h2<|k_pair_h2<|k_conv_mfma_bf<|k_convt_gather_csr<|k_gemm_bf2<|k_gdn_bf<|k_conv_in4_bf<|k_thin_project"
 
 
