@@ -505,6 +505,33 @@ int pcc_conv_wgrad_self(const float* feat, int64_t n, int32_t cin, const float* 
                         void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Channelwise sparse convolution by grid gather (reference loss.py:181-189,219-273: ShepardsLoss' conv_sum over
+ * ME.MinkowskiChannelwiseConvolution, the colour-loss ablation configs/CVPR_inverse_scaling_shepard.yaml)
+ *   out[q][c] = sum_t W[t][c or 0] * feat[row(q + off_t * step)][c]
+ * Input: a canonical set (keys, n) with fp32 features [n][c], 1 <= c <= 64, and optionally its grid index (grid_bits,
+ * grid_rank, h_grid as pcc_kernel_map_build takes them; the grid pitch must equal `step`; NULL: binary search).  Queries:
+ * arbitrary keys at the set's pitch (members or not, inside its lattice or not, any batch).  Taps: odd kernel_size <= 9,
+ * grouped by the caller into ncol (dx, dy) columns, cols int32 [ncol][4] = (dx, dy, zmask, first) in units of `step`, zmask
+ * bit k <-> dz = k - kernel_size / 2; widx int32 [ntaps] = weight row of the j-th set bit of a column's zmask at
+ * widx[first + j].  Every tap appears in exactly one column and widx is a permutation of 0..ntaps-1.  W is [ntaps][wc] with
+ * wc = c, or wc = 1 (broadcast over channels, the reference's (729, 1) window).  Fixed summation order (columns in table order,
+ * dz ascending), no atomics: bitwise reproducible, and the grid and search paths give the same bits.
+ * The feature gradient of a set mapped onto itself is pcc_chconv_fwd over the set with the negated taps. */
+int pcc_chconv_supported(int32_t kernel_size, int32_t c);
+int pcc_chconv_fwd(const int64_t* keys, int64_t n, const float* feat, int32_t c, const uint64_t* grid_bits,
+                   const int32_t* grid_rank, const int32_t* h_grid, int32_t step, const int32_t* cols, int32_t ncol,
+                   const int32_t* widx, int32_t ntaps, int32_t kernel_size, const float* w, int32_t wc,
+                   const int64_t* query_keys, int64_t nq, float* out /*[nq, c]*/, void* stream);
+/* dW[t][c] = sum_j grad_out[j][c] * feat[row(q_j + off_t * step)][c], summed over c as well when wc = 1: per-workgroup partial
+ * slabs [ntaps][c] in `ws` and a fixed-order reduce pass (no atomics). */
+size_t pcc_chconv_wgrad_ws_bytes(int64_t nq, int32_t ntaps, int32_t c);
+int pcc_chconv_wgrad(const int64_t* keys, int64_t n, const float* feat, int32_t c, const uint64_t* grid_bits,
+                     const int32_t* grid_rank, const int32_t* h_grid, int32_t step, const int32_t* cols, int32_t ncol,
+                     const int32_t* widx, int32_t ntaps, int32_t kernel_size, const int64_t* query_keys, int64_t nq,
+                     const float* grad_out /*[nq, c]*/, float* dW /*[ntaps, wc]*/, int32_t wc, void* ws, size_t ws_bytes,
+                     void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * 8f-1  rANS entropy coder + CDF tables  (CompressAI `_CXX`: `pmf_to_quantized_cdf`, `BufferedRansEncoder`,
  *       `RansDecoder`; reference call sites model/entropy_models.py:371-372,397-400,438,471,484, model/model.py:30-34)
  * rans64 scheme: 64-bit state, 32-bit words, 16-bit probabilities, 4-bit bypass digits outside a table.

@@ -2,7 +2,8 @@
 
 Constructor signatures, parameter names and shapes follow MinkowskiEngine 0.5.x so the reference's
 `state_dict`s load: `kernel` is [K, Cin, Cout] ([Cin, Cout] when K == 1), `bias` is [1, Cout]
-(SURVEY A.4).  Forward passes call libpcc_hip; under autograd they go through `autograd.SparseConvFn`.
+(SURVEY A.4).  Forward passes call libpcc_hip; under autograd they go through `autograd.SparseConvFn`
+(`autograd.ChannelwiseConvFn` for `MinkowskiChannelwiseConvolution`, whose `kernel` is [K, C] or [K, 1]).
 """
 import math
 
@@ -189,13 +190,46 @@ class MinkowskiAvgPooling(nn.Module):
 
 
 class MinkowskiChannelwiseConvolution(nn.Module):
-    """Constructed by the Shepard's-loss ablation (`loss.py:185`); out of scope."""
+    """`ME.MinkowskiChannelwiseConvolution` (constructed by the Shepard's-loss ablation, `loss.py:181-189`): one kernel column
+    per channel, out[x][c] = sum_k kernel[k][c] * in[x + off_k * tensor_stride][c] over the same coordinate set.  `kernel` is
+    [K, C] or [K, 1] (broadcast over the channels; the reference assigns its (729, 1) window), offsets enumerated x fastest
+    (WEIGHT_OFFSET_ORDER).  Stride 1, dilation 1, no bias, odd kernel_size <= 9, 1 <= C <= 64; the gather kernel reads the
+    neighbours from the set's grid index (`pcc_chconv_fwd`), under autograd through `autograd.ChannelwiseConvFn`."""
 
     def __init__(self, in_channels, kernel_size=-1, stride=1, dilation=1, bias=False, kernel_generator=None,
                  dimension=None):
         super().__init__()
-        K = _iso(kernel_size, "kernel_size") ** 3
+        self.in_channels = int(in_channels)
+        self.kernel_size = _iso(kernel_size, "kernel_size")
+        self.stride, self.dilation, self.has_bias = stride, dilation, bool(bias)
+        K = self.kernel_size ** 3
+        self.kernel_volume = K
         self.kernel = nn.Parameter(torch.zeros(K, int(in_channels)))
 
     def forward(self, input):
-        raise L.PccError("MinkowskiChannelwiseConvolution.forward is outside the hot path")
+        if _iso(self.stride, "stride") != 1:
+            raise L.PccError("MinkowskiChannelwiseConvolution: stride != 1 is not supported")
+        if _iso(self.dilation, "dilation") != 1:
+            raise L.PccError("MinkowskiChannelwiseConvolution: dilation != 1 is not supported")
+        if self.has_bias:
+            raise L.PccError("MinkowskiChannelwiseConvolution: bias is not supported")
+        ks = self.kernel_size
+        if ks < 1 or ks % 2 == 0 or ks > 9:
+            raise L.PccError(f"MinkowskiChannelwiseConvolution: kernel_size {ks} unsupported (odd, at most 9)")
+        feats = input._canonical_features()
+        c = feats.shape[1]
+        K = ks ** 3
+        if self.kernel.dim() != 2 or self.kernel.shape[0] != K or self.kernel.shape[1] not in (1, c):
+            raise L.PccError(f"MinkowskiChannelwiseConvolution: kernel {tuple(self.kernel.shape)} is neither [{K}, {c}] nor [{K}, 1]")
+        if not 1 <= c <= 64:
+            raise L.PccError(f"MinkowskiChannelwiseConvolution: {c} channels unsupported (1..64)")
+        perm = S.weight_offset_perm(K, self.kernel.device)
+        kernel = self.kernel if perm is None else self.kernel[perm]
+        taps = S.channelwise_full_taps(ks)
+        cs = input._cset
+        if torch.is_grad_enabled() and (feats.requires_grad or kernel.requires_grad):
+            from ..autograd import ChannelwiseConvFn
+            out = ChannelwiseConvFn.apply(feats, kernel.to(torch.float32), cs, taps)
+        else:
+            out = S.channelwise_gather(cs, feats, taps, kernel.detach().to(torch.float32), cs.keys, cs.n)
+        return input._like(out)

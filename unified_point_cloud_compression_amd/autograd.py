@@ -344,3 +344,26 @@ class EbLikFn(torch.autograd.Function):
         dp = torch.empty_like(packed)
         L.call("pcc_eb_lik_bwd", L.ptr(v), L.ptr(g), v.shape[0], v.shape[1], L.ptr(packed), L.ptr(dv), L.ptr(dp), L.stream())
         return dv, (dp if ctx.needs_input_grad[1] else None)
+
+
+class ChannelwiseConvFn(torch.autograd.Function):
+    """Channelwise convolution of a set onto itself (`ME.MinkowskiChannelwiseConvolution`, reference `loss.py:181-189`) through
+    `pcc_chconv_fwd`.  Backward: the feature gradient is the same gather over the set with the taps mirrored through the
+    centre, the weight gradient `pcc_chconv_wgrad` (partial slabs + a fixed-order reduce); each only when required."""
+
+    @staticmethod
+    def forward(ctx, feats, kernel, cset, taps):          # kernel [T, C] or [T, 1], rows in the order of `taps`
+        feats, kernel = feats.contiguous(), kernel.contiguous()
+        out = S.channelwise_gather(cset, feats, taps, kernel, cset.keys, cset.n)
+        ctx.save_for_backward(feats, kernel)
+        ctx.cset, ctx.taps = cset, taps
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        feats, kernel = ctx.saved_tensors
+        cset, taps = ctx.cset, ctx.taps
+        g = g.contiguous()
+        df = S.channelwise_gather(cset, g, taps.negated(), kernel, cset.keys, cset.n) if ctx.needs_input_grad[0] else None
+        dw = S.channelwise_wgrad(cset, feats, taps, g, cset.keys, cset.n, kernel.shape[1]) if ctx.needs_input_grad[1] else None
+        return df, dw, None, None

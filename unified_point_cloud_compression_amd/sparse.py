@@ -1007,3 +1007,94 @@ def lookup_gather(cset, feats, query_keys, nq):
         L.call("pcc_lookup_gather", L.ptr(cset.keys), cset.n, L.ptr(feats), feats.shape[1], L.ptr(query_keys), nq,
                L.ptr(out), L.stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# channelwise convolution by grid gather (reference `loss.py:181-189,219-273`)
+# ------------------------------------------------------------------------------------------------
+class ChannelwiseTaps:
+    """A tap list of `pcc_chconv_*` grouped into (dx, dy) columns: taps [(dx, dy, dz)] in units of the pitch, the weight row of
+    tap t is t.  Columns are ordered y-major / x-minor and the taps of a column by dz, which fixes the summation order.  The
+    host table is built once; its device copy is cached per device."""
+
+    def __init__(self, taps, kernel_size):
+        ks = int(kernel_size)
+        if ks < 1 or ks % 2 == 0 or ks > 9:
+            raise L.PccError(f"channelwise convolution: kernel_size {ks} unsupported (odd, at most 9)")
+        r = ks // 2
+        taps = [tuple(int(v) for v in t) for t in taps]
+        if not taps or len(set(taps)) != len(taps) or any(len(t) != 3 or max(abs(v) for v in t) > r for t in taps):
+            raise L.PccError(f"channelwise convolution: taps must be distinct offsets within the {ks}^3 cube")
+        cols = {}
+        for t, (dx, dy, dz) in enumerate(taps):
+            cols.setdefault((dy, dx), []).append((dz, t))
+        table, widx = [], []
+        for dy, dx in sorted(cols):
+            entries = sorted(cols[(dy, dx)])
+            zmask = 0
+            for dz, _ in entries:
+                zmask |= 1 << (dz + r)
+            table += [dx, dy, zmask, len(widx)]
+            widx += [t for _, t in entries]
+        self.taps, self.kernel_size = taps, ks
+        self.table, self.widx = table, widx
+        self.ncol, self.ntaps = len(table) // 4, len(taps)
+        self._dev = {}
+        self._neg = None
+
+    def negated(self):
+        """The same taps mirrored through the centre, same weight rows (the feature gradient of a self-mapped convolution)."""
+        if self._neg is None:
+            self._neg = ChannelwiseTaps([(-a, -b, -c) for a, b, c in self.taps], self.kernel_size)
+        return self._neg
+
+    def on(self, device):
+        t = self._dev.get(str(device))
+        if t is None:
+            t = (torch.tensor(self.table, dtype=torch.int32, device=device),
+                 torch.tensor(self.widx, dtype=torch.int32, device=device))
+            self._dev[str(device)] = t
+        return t
+
+
+_FULL_TAPS = {}
+
+
+def channelwise_full_taps(kernel_size):
+    """All k^3 offsets of an odd kernel in the x-fastest enumeration of `kernel[K, ...]` (WEIGHT_OFFSET_ORDER)."""
+    t = _FULL_TAPS.get(kernel_size)
+    if t is None:
+        ks, r = int(kernel_size), int(kernel_size) // 2
+        t = ChannelwiseTaps([(k % ks - r, (k // ks) % ks - r, k // (ks * ks) - r) for k in range(ks ** 3)], ks)
+        _FULL_TAPS[kernel_size] = t
+    return t
+
+
+def _chconv_common(cset, feats, taps):
+    cols, widx = taps.on(feats.device)
+    g = cset.grid() if USE_GRID else None
+    return (L.ptr(cset.keys), cset.n, L.ptr(feats), feats.shape[1], L.ptr(g[0]) if g else None, L.ptr(g[1]) if g else None,
+            g[2] if g else None, cset.ts, L.ptr(cols), taps.ncol, L.ptr(widx), taps.ntaps, taps.kernel_size)
+
+
+def channelwise_gather(cset, feats, taps, weights, query_keys, nq):
+    """out[q][c] = sum_t weights[t][c or 0] * feats[row(q + taps[t] * pitch)][c] for `nq` query keys at the set's pitch
+    (members of `cset` or not), through the set's grid index (`pcc_chconv_fwd`).  weights: [T, C] or [T, 1]."""
+    feats = feats.contiguous()
+    w = weights.contiguous()
+    out = torch.empty((nq, feats.shape[1]), dtype=torch.float32, device=feats.device)
+    if nq == 0:
+        return out
+    L.call("pcc_chconv_fwd", *_chconv_common(cset, feats, taps), L.ptr(w), w.shape[1], L.ptr(query_keys), nq, L.ptr(out),
+           L.stream())
+    return out
+
+
+def channelwise_wgrad(cset, feats, taps, grad_out, query_keys, nq, wc):
+    """dW[t][c] = sum_j grad_out[j][c] * feats[row(q_j + taps[t] * pitch)][c] ([T, C]; wc = 1: also summed over c, [T, 1])."""
+    feats, grad_out = feats.contiguous(), grad_out.contiguous()
+    dW = torch.empty((taps.ntaps, wc), dtype=torch.float32, device=feats.device)
+    ws = L.workspace(L.load().pcc_chconv_wgrad_ws_bytes(nq, taps.ntaps, feats.shape[1]), feats.device)
+    L.call("pcc_chconv_wgrad", *_chconv_common(cset, feats, taps), L.ptr(query_keys), nq, L.ptr(grad_out), L.ptr(dW), wc,
+           L.ptr(ws), ws.numel(), L.stream())
+    return dW
