@@ -608,6 +608,22 @@ int pcc_nn_sorted_x(const int32_t* a_xyz, int64_t n_a, const int32_t* b_xyz, int
                     void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 8f-5  radius normal estimation of the point-to-plane (D2) report (reference evaluate.py:153,
+ *       rec_pc.estimate_normals(KDTreeSearchParamRadius(radius=5.0)); the normals go to pc_error at utils.py:223).
+ *       keys: a canonical, de-duplicated set at pitch 1 (n < 2^31); grid_bits / h_grid: its pcc_grid_build bitmap and host
+ *       parameters (pitch h_grid[6] must be 1; the rank array is not needed), or NULL: binary search over the keys, same bits.
+ *       Neighbourhood of a point: every member at integer offset d with |d|^2 <= lim, the point itself included; the caller
+ *       passes lim = ceil(r^2) - 1 (the strict dist^2 < r^2 of a radius search); 0 <= lim <= 63 (r <= 8), else an error.
+ *       normals [n,3] fp32: the eigenvector of the smallest eigenvalue of M = n S2 - S1 S1^T (exact int64 moments of the
+ *       neighbourhood, n^2 times its covariance), solved in fp64, normalised, flipped so that its largest-magnitude component
+ *       is positive (the first such axis on a tie); fewer than 3 neighbours: (0, 0, 1); a degenerate (collinear)
+ *       neighbourhood: some unit vector of the smallest eigenspace.  counts [n] int32 (nullable): neighbourhood sizes.
+ *       One thread per point in canonical order, no atomics, no order-dependent float sums: bitwise reproducible.
+ * ---------------------------------------------------------------------------------------- */
+int pcc_normals_grid(const int64_t* keys, int64_t n, const uint64_t* grid_bits /*nullable*/, const int32_t* h_grid, int32_t lim,
+                     float* normals /*[n,3]*/, int32_t* counts /*nullable*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * measurement support: per-launch HIP-event timing of the conv kernel (bench.py roofline)
  * ---------------------------------------------------------------------------------------- */
 int pcc_prof_enable(int32_t on);

@@ -3,7 +3,9 @@
 into their blocks (`partition`), the (frame, block) items are assigned to the ranks (one process per GPU, longest first over
 ALL items, so a vox11 frame's >= 8 blocks spread over the node), each rank codes its items to byte strings and decodes
 them from plain coordinates, measures bits and the block-local D1 numerators on its GPU, and one all_gather of fixed-size
-records ends the sweep; per-frame totals are summed from the block records (`evaluate.py:102-195` without the external tools).  Single process: python tools/eval_frames.py [--bits 9 9 10]
+records ends the sweep; per-frame totals are summed from the block records (`evaluate.py:102-195` without the external tools).
+--d2 adds the block-local point-to-plane (D2, `pc_error`'s d2_psnr) numerators, normals estimated per block with radius 5
+(`evaluate.py:153`), gathered in a second record exchange.  Single process: python tools/eval_frames.py [--bits 9 9 10] [--d2]
 N GPUs:  python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/eval_frames.py"""
 import argparse
 import os
@@ -20,6 +22,7 @@ from unified_point_cloud_compression_amd import frames, metrics, synth  # noqa: 
 ap = argparse.ArgumentParser()
 ap.add_argument("--bits", type=int, nargs="+", default=[10, 10, 11, 10], help="grid bits of the synthetic frames")
 ap.add_argument("--block-size", type=int, default=None, help="default: 1024 for <= 10 bits, 512 above (evaluate.py:39-46)")
+ap.add_argument("--d2", action="store_true", help="also the block-local point-to-plane (D2) numerators and PSNR")
 args = ap.parse_args()
 rank, local, world = (int(os.environ.get(k, d)) for k, d in (("RANK", 0), ("LOCAL_RANK", 0), ("WORLD_SIZE", 1)))
 # PCC_BENCH_REHEARSE=1: the N-rank sweep on ONE GPU (every rank on device 0, collectives over gloo on host tensors) -- a check of
@@ -74,15 +77,20 @@ def blocks(i):
     return frame_blocks[i]
 
 
+d2_local = {}                                          # (frame, block) -> D2 numerators (--d2)
+
+
 def process(f, b):
-    """One (frame, block) item: code, decode from plain coordinates, block-local D1 numerators."""
+    """One (frame, block) item: code, decode from plain coordinates, block-local D1 (and with --d2, D2) numerators."""
     x = blocks(f)[b]
     torch.cuda.synchronize(); t0 = time.time()
     strings, shape, k, yc = model.compress_block(x, q)
     torch.cuda.synchronize(); t1 = time.time()
     rec = model.decompress(coordinates=[yc.clone()], strings=[strings], shape=[shape], k=[k], q_vals=[q])
     torch.cuda.synchronize(); t2 = time.time()
-    rep = metrics.pointcloud_metrics(x, rec, resolution=(1 << args.bits[f]) - 1)
+    rep = metrics.pointcloud_metrics(x, rec, resolution=(1 << args.bits[f]) - 1, point_to_plane=args.d2)
+    if args.d2:
+        d2_local[(f, b)] = (rep["AB_d2_mse"] * x.shape[0], x.shape[0], rep["BA_d2_mse"] * rec.shape[0], rec.shape[0])
     return (f, b, x.shape[0], t1 - t0, t2 - t1, metrics.count_bits([strings]), rec.shape[0],
             rep["AB_mse"] * x.shape[0], x.shape[0], rep["BA_mse"] * rec.shape[0], rec.shape[0])
 
@@ -96,20 +104,31 @@ if world > 1:
 torch.cuda.synchronize()
 t_wall0 = time.time()
 recs, totals = frames.run_sharded_blocks(sizes, process, coll, rank, world)
+if args.d2:                                            # D2 numerators: one more exchange of fixed-size records
+    d2_recs = frames.gather_records([(f, b) + v for (f, b), v in sorted(d2_local.items())], coll, n_fields=6)
+    for r in d2_recs:
+        t = totals[int(r[0])]
+        for k, v in zip(("se2_ab", "n2_ab", "se2_ba", "n2_ba"), r[2:]):
+            t[k] = t.get(k, 0.0) + float(v)
 torch.cuda.synchronize()
 wall = torch.tensor([time.time() - t_wall0], dtype=torch.float64, device=coll)
 if world > 1:
     dist.all_reduce(wall, op=dist.ReduceOp.MAX)        # the sweep ends when the slowest rank ends
 wall = float(wall.item())
 if rank == 0:
-    print(f"{'frame':>5s} {'blocks':>6s} {'points':>9s} {'enc ms':>8s} {'dec ms':>8s} {'bpp':>7s} {'decoded':>9s} {'D1 dB':>7s}")
+    print(f"{'frame':>5s} {'blocks':>6s} {'points':>9s} {'enc ms':>8s} {'dec ms':>8s} {'bpp':>7s} {'decoded':>9s} {'D1 dB':>7s}"
+          + (f" {'D2 dB':>7s}" if args.d2 else ""))
     import math
     for f, t in sorted(totals.items()):
         res = (1 << args.bits[f]) - 1
         mse = max(t["mse_ab"], t["mse_ba"])
         d1 = 10 * math.log10(res * res / mse) if mse > 0 else float("inf")
-        print(f"{f:5d} {t['blocks']:6d} {t['n_points']:9d} {t['t_encode'] * 1e3:8.1f} {t['t_decode'] * 1e3:8.1f} {t['bpp']:7.3f} "
-              f"{t['n_decoded']:9d} {d1:7.2f}")
+        line = (f"{f:5d} {t['blocks']:6d} {t['n_points']:9d} {t['t_encode'] * 1e3:8.1f} {t['t_decode'] * 1e3:8.1f} {t['bpp']:7.3f} "
+                f"{t['n_decoded']:9d} {d1:7.2f}")
+        if args.d2:                                    # `pc_error`: 3 res^2 over the worse direction's mse
+            mse2 = max(t["se2_ab"] / max(t["n2_ab"], 1.0), t["se2_ba"] / max(t["n2_ba"], 1.0))
+            line += f" {10 * math.log10(3 * res * res / mse2) if mse2 > 0 else float('inf'):7.2f}"
+        print(line)
     tot = sum(t["n_points"] for t in totals.values())
     busy = sum(t["t_encode"] + t["t_decode"] for t in totals.values())
     print(f"{len(totals)} frames as {len(recs)} (frame, block) items over {world} rank(s): {tot} points in {wall:.3f} s wall (max over "

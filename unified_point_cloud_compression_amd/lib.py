@@ -156,6 +156,7 @@ SIGNATURES = {
     "pcc_conv_fwd_pairs": (C.c_int, [_p, _i64, _i32, _p, _p, _i32, _i32, _p, _p, _p, _i64, _p, _i64, _p, _p, _i32,
                                      C.c_float, _i32, _p, _p]),
     "pcc_nn_sorted_x": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _p]),
+    "pcc_normals_grid": (C.c_int, [_p, _i64, _p, C.POINTER(_i32), _i32, _p, _p, _p]),
     "pcc_prof_enable": (C.c_int, [_i32]),
     "pcc_prof_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(_i64)]),
     "pcc_prof_sequence": (_i64, [C.POINTER(_i32), _i64]),
