@@ -584,6 +584,15 @@ int pcc_rans_decode_streams(const uint8_t* data, int64_t nbytes, const int32_t* 
                             int32_t n_groups, int32_t n_segments, const int32_t* cdf, int32_t cdf_stride,
                             const int32_t* sizes, const int32_t* offsets, const void* dec_table /*nullable, device*/,
                             int64_t dec_bytes, int32_t* sym_out, int32_t* d_status, void* stream);
+/* The same with the decoder form chosen by the caller (tests, A/B runs).  With the table in LDS there are two decoders:
+ * form 1, one LANE per stream (256 streams per workgroup), and form 2, one WAVE per stream (the lanes share the symbol
+ * search; up to 16 streams per workgroup).  form 0 picks form 2 while one round of workgroups covers all streams and
+ * form 1 above that; pcc_rans_decode_streams passes the value of env PCC_RANS_FORM (read once, default 0).  Both forms
+ * give the same symbols and status words.  Without an LDS table the form is ignored. */
+int pcc_rans_decode_streams_form(const uint8_t* data, int64_t nbytes, const int32_t* idx, int64_t n, int32_t channels,
+                                 int32_t n_groups, int32_t n_segments, const int32_t* cdf, int32_t cdf_stride,
+                                 const int32_t* sizes, const int32_t* offsets, const void* dec_table /*nullable, device*/,
+                                 int64_t dec_bytes, int32_t* sym_out, int32_t* d_status, void* stream, int32_t form);
 
 /* ------------------------------------------------------------------------------------------
  * 8f-3  lossless coder for the stride-8 latent coordinates (replaces the PLY file + `tmc3` subprocess round trip of

@@ -1,0 +1,135 @@
+"""The two LDS-table rANS decoders -- one lane per stream (form 1) and one wave per stream (form 2) -- give the same symbols
+and the same status word on the same container.  Decided by equality; all inputs are seeded."""
+import numpy as np
+import pytest
+import torch
+
+from tests.util import dev, t, n
+
+pytestmark = pytest.mark.gpu
+
+
+def _gaussian():
+    from unified_point_cloud_compression_amd.compressai.entropy_models import GaussianConditional, get_scale_table
+    gc = GaussianConditional(None).to(dev())
+    gc.update_scale_table(get_scale_table(), force=True)
+    return gc
+
+
+def _factorised(channels):
+    from unified_point_cloud_compression_amd.compressai.entropy_models import EntropyBottleneck
+    torch.manual_seed(0)
+    eb = EntropyBottleneck(channels).to(dev())
+    eb.update(force=True)
+    return eb
+
+
+def _decode(em, data, rows, c, idx, form):
+    """(symbols, status) of `data` through pcc_rans_decode_streams_form."""
+    from unified_point_cloud_compression_amd import lib as L
+    d = dev()
+    cdf, sizes, offs = (x.to(d).contiguous() for x in (em._quantized_cdf, em._cdf_length, em._offset))
+    buf = em.upload_string(data, d).device_buf
+    tab = em._dec_table(d)
+    sym = torch.full((rows, c), -(1 << 30), dtype=torch.int32, device=d)
+    status = torch.zeros(1, dtype=torch.int32, device=d)
+    L.call("pcc_rans_decode_streams_form", L.ptr(buf), len(data), L.ptr(idx) if idx is not None else None, rows, c,
+           *em._segments_of(data, rows, c), L.ptr(cdf), cdf.shape[1], L.ptr(sizes), L.ptr(offs), L.ptr(tab), tab.numel(),
+           L.ptr(sym), L.ptr(status), L.stream(), form)
+    torch.cuda.synchronize()
+    return sym, int(status.item())
+
+
+def _check(em, sym, idx, want_streams=None):
+    """Encode, decode with both forms (and the automatic choice), compare.  Returns the stream count."""
+    rows, c = sym.shape
+    d_idx = t(idx) if idx is not None else None
+    data = em.compress_rows(t(sym), d_idx)
+    ns = int(np.frombuffer(data[:4], "<u4")[0])
+    if want_streams is not None:
+        assert ns == want_streams, (ns, want_streams)
+    lane, st_lane = _decode(em, data, rows, c, d_idx, 1)
+    wave, st_wave = _decode(em, data, rows, c, d_idx, 2)
+    auto, st_auto = _decode(em, data, rows, c, d_idx, 0)
+    assert st_lane == 0 and st_wave == st_lane and st_auto == st_lane, (st_lane, st_wave, st_auto)
+    assert torch.equal(wave, lane) and torch.equal(auto, lane)
+    assert np.array_equal(n(lane), sym)
+    return ns
+
+
+def _gaussian_symbols(gc, rng, rows, c, idx_hi=64, spread=1.3):
+    """Gaussian draws under random table rows, plus the hard places: first and last regular value of a row (the tail
+    buckets), escapes of no, one, several and eight bypass digits, positive and negative."""
+    idx = rng.integers(0, idx_hi, (rows, c)).astype(np.int32)
+    st, offs, sizes = n(gc.scale_table), n(gc._offset), n(gc._cdf_length)
+    sym = np.rint(rng.standard_normal((rows, c)) * st[idx] * spread).astype(np.int32)
+    lo, hi = offs[idx], offs[idx] + sizes[idx] - 2          # regular values: lo ... hi - 1; hi and beyond / below lo escape
+    flat, flo, fhi = sym.reshape(-1), lo.reshape(-1), hi.reshape(-1)
+    pos = rng.permutation(flat.size)[:min(flat.size // 4, 4000)]
+    for k, p in enumerate(pos):
+        flat[p] = (flo[p], fhi[p] - 1, fhi[p] - 2, flo[p] + 1,          # tails of the row
+                   fhi[p], fhi[p] + 3, flo[p] - 1, flo[p] - 7,          # escapes: no digit, one digit (+), one digit (-, -)
+                   fhi[p] + 9000, flo[p] - 123456,                      # several digits
+                   fhi[p] + (1 << 28), flo[p] - (1 << 28))[k % 12]      # eight digits
+    return sym, idx
+
+
+def test_forms_agree_per_channel_grouped_and_segmented():
+    gc = _gaussian()
+    sizes = n(gc._cdf_length)
+    assert sizes.min() < 64 and sizes.max() > 300           # rows shorter than a wave and rows several hundred entries long
+    rng = np.random.default_rng(5)
+    sym, idx = _gaussian_symbols(gc, rng, 700, 6)
+    gc.STREAM_SYMBOLS = 1                                   # gl = 0, one segment
+    _check(gc, sym, idx, 6)
+    _check(gc, sym[:500, :1].copy(), idx[:500, :1].copy(), 1)          # a single stream
+    for seg_symbols, want in ((200, 3), (64, 10)):          # ragged last segment
+        gc.SEGMENT_SYMBOLS = seg_symbols
+        _check(gc, sym, idx, 6 * want)
+    gc.SEGMENT_SYMBOLS = 2                                  # 9 rows in 4 segments of 3: the last one is empty
+    _check(gc, sym[:9].copy(), idx[:9].copy(), 24)
+    gc.SEGMENT_SYMBOLS = 1 << 30
+    sym2, idx2 = _gaussian_symbols(gc, rng, 300, 8)
+    gc.STREAM_SYMBOLS = 600                                 # gl = 1: two channels per stream
+    assert gc.n_streams(300, 8) == (4, 1)
+    _check(gc, sym2, idx2, 4)
+    gc.STREAM_SYMBOLS = 1200                                # gl = 2
+    assert gc.n_streams(300, 8) == (2, 1)
+    _check(gc, sym2, idx2, 2)
+    gc.STREAM_SYMBOLS, gc.SEGMENT_SYMBOLS = 600, 80         # grouped and segmented: 4 groups x 7 segments of 43 rows, ragged
+    assert gc.n_streams(300, 8) == (4, 7)
+    _check(gc, sym2, idx2, 28)
+
+
+def test_forms_agree_on_the_factorised_prior():
+    rng = np.random.default_rng(6)
+    for channels, rows in ((8, 300), (192, 938)):           # (192, 938): the benchmark's hyper-latent, 96 streams of 2 channels
+        eb = _factorised(channels)
+        offs, sizes = n(eb._offset), n(eb._cdf_length)
+        sym = np.rint(rng.standard_normal((rows, channels)) * 4).astype(np.int32)
+        ch = np.arange(channels)
+        sym[3] = offs + sizes - 3                           # last regular value of every row
+        sym[4] = offs                                       # first
+        sym[5] = offs + sizes - 2 + (ch % 5)                # escapes: no / one digit
+        sym[6] = offs - 1 - (ch % 9)
+        sym[7, ::3] = 1 << 28                               # eight digits
+        sym[8, 1::3] = -(1 << 28)
+        if channels == 192:
+            assert _check(eb, sym, None) == 96
+        else:
+            eb.STREAM_SYMBOLS = 1
+            _check(eb, sym, None, 8)
+            eb.STREAM_SYMBOLS = 1200                        # gl = 2 without idx: the row is the channel inside the group
+            _check(eb, sym, None, 2)
+
+
+def test_forms_agree_on_the_benchmark_latent_shape_and_above_the_dispatch_threshold():
+    gc = _gaussian()
+    rng = np.random.default_rng(7)
+    sym, idx = _gaussian_symbols(gc, rng, 14864, 128, idx_hi=48, spread=1.0)
+    ns = _check(gc, sym, idx)                               # adaptive stream count (framing <= 2 % of the payload)
+    assert ns % 128 == 0 and 3 * 128 < ns <= 29 * 128, ns
+    # more streams than the automatic choice gives to the wave form (16 per compute unit): 80 segments x 128 channels
+    gc.MAX_STREAMS, gc.SEGMENT_SYMBOLS, gc.FRAMING_TARGET = 10240, 64, 0.0
+    assert gc.n_streams(5120, 128) == (128, 80)
+    _check(gc, sym[:5120].copy(), idx[:5120].copy(), 10240)

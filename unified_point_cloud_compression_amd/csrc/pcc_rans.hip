@@ -345,13 +345,20 @@ extern "C" int pcc_rans_decode_host(const uint8_t* h_data, int64_t nbytes, const
 }
 
 // ------------------------------------------------------------------------------------------
-// GPU: many independent streams, one per lane
+// GPU: many independent streams
 //   The [n, channels] symbol matrix is cut into n_groups channel groups (2^gl adjacent channels each) times n_segments
 //   row segments of R = ceil(n / n_segments) rows; stream s = segment * n_groups + group codes its tile row by row.
 //   container: u32 n_streams | u32 nwords[n_streams] | words of stream 0 | words of stream 1 | ...
 //   A lone wave issues about one instruction every 4-5 cycles and the coder state is a serial chain, so speed comes
 //   from (a) many streams (segments), and (b) few instructions per symbol: 32-bit addressing, everything that does
 //   not depend on the state resolved up front, tables in LDS addressed as LDS.
+//   The encoder runs one stream per lane.  The decoder has two forms with the table in LDS (same container, same table
+//   blob, same symbols and status words): one stream per LANE (k_rans_decode_lds: the wave takes the longest search, and
+//   every renormalisation and bypass branch, of its 64 streams per symbol) and one stream per WAVE (k_rans_decode_wave:
+//   the 64 lanes search one symbol's CDF row together and all control flow is wave-uniform).  The stream count is set by
+//   the container's rate policy (about 100 to 4096), far below the lanes of the chip, so the wave form runs whenever one
+//   round of workgroups covers the streams, the lane form above that (pcc_rans_decode_streams_form).  A table too large
+//   for LDS goes to k_rans_decode_global.
 // ------------------------------------------------------------------------------------------
 static constexpr int GB = 8;                        // symbols per prefetch batch in the GPU coders
 static constexpr unsigned short R_ESC = 0x8000;     // RansEncSym::rcp_shift flag: bypass payload in pre_r
@@ -613,6 +620,171 @@ __global__ void __launch_bounds__(256) k_rans_decode_lds(const unsigned* __restr
   if (pos - 1 - off > len) *status = 3;                // consumed past its own stream: corrupt input
 }
 
+// ---- decoder, one WAVE per stream ----------------------------------------------------------------
+// The coder state is the same in all 64 lanes (the compiler keeps it in scalar registers), so every branch -- the
+// renormalisation, the bypass digits, the long-row search -- is wave-uniform, and the lanes are spent on the symbol
+// search instead:
+//   * 64 symbols per batch, one per lane, for everything that does not depend on the state: table row, row start, row
+//     length, value offset (fetched one batch ahead), and the decoded values (stored once per batch);
+//   * per symbol, 64 samples of its CDF row, one per lane, every S-th entry (S = 1 for rows of at most 64 entries: the whole
+//     row).  They do not depend on the state either and are read from LDS one group of WB symbols ahead.  One compare, one
+//     ballot and a population count give the symbol (S = 1; start and next entry are lane reads) or the S entries that hold
+//     it (S > 1: one dependent LDS read of 64 consecutive entries, compare, ballot, count).  The 256-bucket table of the
+//     lane-per-stream form is not used and not loaded;
+//   * the stream's words, 64 per lane read with the next 64 already requested: the renormalisation is a lane read.
+// Loop bounds: symbols per stream (geometry), row length (table), <= 5 + 75 bypass digits; none depends on the stream's words.
+static constexpr int WB = 8;                        // symbols per sample-prefetch group
+
+template <bool HAS_IDX>
+__global__ void __launch_bounds__(1024) k_rans_decode_wave(const unsigned* __restrict__ data, unsigned nwords_total,
+                                                           const int* __restrict__ idx, StreamGeom g,
+                                                           const int* __restrict__ offsets, const int* __restrict__ dec_blob,
+                                                           int dec_words, int* __restrict__ out, int* __restrict__ status) {
+  extern __shared__ int blob_s[];                      // row_off[rows + 1] | value offsets[rows] | cdf16
+  const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63;
+  const int rows_tab = dec_blob[0];
+  const int cdf_w0 = 2 + rows_tab + 1 + rows_tab * 128;    // first word of cdf16 in the blob (behind the bucket table)
+  int* const row_off_s = blob_s;
+  int* const offs_s = blob_s + rows_tab + 1;
+  int* const cdf_s = offs_s + rows_tab;
+  for (int i = tid; i <= rows_tab; i += nthr) row_off_s[i] = dec_blob[2 + i];
+  for (int i = tid; i < rows_tab; i += nthr) offs_s[i] = offsets[i];
+  for (int i = tid; i < dec_words - cdf_w0; i += nthr) cdf_s[i] = dec_blob[cdf_w0 + i];
+  __syncthreads();
+  const unsigned short* const c16 = (const unsigned short*)cdf_s;
+  const int s = blockIdx.x * (nthr >> 6) + __builtin_amdgcn_readfirstlane(tid >> 6);
+  if (s >= g.n_streams) return;
+  if ((int)data[0] != g.n_streams) { if (lane == 0) *status = 1; return; }
+  // stream position: the lengths of all earlier streams, summed by the wave
+  unsigned part = 0;
+  for (int i = lane; i < s; i += 64) part += data[1 + i];
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d, 64);
+  const unsigned off = __builtin_amdgcn_readfirstlane(1u + (unsigned)g.n_streams + part);
+  const unsigned len = data[1 + s];
+  if ((unsigned long long)off + len > nwords_total || len < 2) { if (lane == 0) *status = 2; return; }
+  const unsigned lim = nwords_total + 1;               // the buffer is padded by two words
+  const int seg = s / g.n_groups, grp = s - seg * g.n_groups;
+  int rows = g.n - seg * g.R;
+  rows = rows < 0 ? 0 : (rows > g.R ? g.R : rows);
+  const int cnt = rows << g.gl;
+  const int gm = (1 << g.gl) - 1;
+  const int ch0 = grp << g.gl;
+  const unsigned lane_base = (unsigned)(seg * g.R) * (unsigned)g.channels + (unsigned)ch0;
+  // words: a window of 128, lane l of `w0` / `w1` holds word wbase + l / wbase + 64 + l (clamped to the buffer); each half
+  // is requested again, 128 words on, as soon as its last word is taken, so a reload has 64 words of decoding to arrive
+  unsigned wbase = off;
+  unsigned w0 = data[min(wbase + (unsigned)lane, lim)], w1 = data[min(wbase + 64u + (unsigned)lane, lim)];
+  int widx = 2;                                        // next word = wbase + widx
+  unsigned long long x = (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)w0, 0) |
+                         ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)w0, 1) << 32);
+  auto next_word = [&]() -> unsigned {
+    const unsigned a = (unsigned)__builtin_amdgcn_readlane((int)w0, widx & 63);
+    const unsigned b = (unsigned)__builtin_amdgcn_readlane((int)w1, widx & 63);
+    const unsigned w = widx < 64 ? a : b;
+    ++widx;
+    if (widx == 64) w0 = data[min(wbase + 128u + (unsigned)lane, lim)];
+    if (widx == 128) { widx = 0; wbase += 128u; w1 = data[min(wbase + 64u + (unsigned)lane, lim)]; }
+    return w;
+  };
+  auto low = [](unsigned long long v) { return ((unsigned)(v >> 32) | ((unsigned)v >> 31)) == 0; };   // v < R_L on the scalar unit
+  auto get_bits = [&]() -> unsigned {
+    const unsigned v = (unsigned)x & R_MAXB;
+    x >>= R_BYP;
+    if (low(x)) x = (x << 32) | next_word();
+    return v;
+  };
+  auto addr = [&](int jj) { return lane_base + (unsigned)(jj >> g.gl) * (unsigned)g.channels + (unsigned)(jj & gm); };
+  auto fetch_ci = [&](int j0) {
+    const int jj = min(j0 + lane, cnt - 1);              // past the end: the last symbol's row again (unused)
+    return HAS_IDX ? idx[addr(jj)] : ch0 + (jj & gm);
+  };
+  int ci_n = cnt > 0 ? fetch_ci(0) : 0;
+  for (int j0 = 0; j0 < cnt; j0 += 64) {
+    // per lane: the row of symbol j0 + lane.  last = index of the last comparable entry (entry last + 1 is 2^16 stored as
+    // 0); S = sample stride; nv = number of samples (lanes) that are comparable entries.
+    const int ci = ci_n;
+    if (j0 + 64 < cnt) ci_n = fetch_ci(j0 + 64);
+    const int ro_v = row_off_s[ci];
+    const int last_v = min(max(row_off_s[ci + 1] - ro_v - 2, 0), 0xFFFF);
+    const int offs_v = offs_s[ci];
+    const int S_v = min(last_v / 63 + 1, 63);            // 63 * S > last, or S = 63 and lane 63 covers the rest
+    const int geo_v = last_v | (S_v << 16) | (min(last_v / S_v, 63) << 24);      // nv - 1 in the top byte
+    const int nb = min(64, cnt - j0);
+    int out_v = 0;
+    auto fetch = [&](int u0, unsigned (&p)[WB]) {
+#pragma unroll
+      for (int k = 0; k < WB; ++k) {
+        const int u = min(u0 + k, 63);
+        const int ro = __builtin_amdgcn_readlane(ro_v, u), geo = __builtin_amdgcn_readlane(geo_v, u);
+        p[k] = c16[ro + min(lane * ((geo >> 16) & 0xFF), (geo & 0xFFFF) + 1)];
+      }
+    };
+    auto run = [&](int u0, const unsigned (&p)[WB]) {
+#pragma unroll
+      for (int k = 0; k < WB; ++k) {
+        const int u = u0 + k;
+        if (u >= nb) break;
+        const int geo = __builtin_amdgcn_readlane(geo_v, u), voff = __builtin_amdgcn_readlane(offs_v, u);
+        const int last = geo & 0xFFFF, S = (geo >> 16) & 0xFF, nv1 = geo >> 24;
+        const unsigned cum = (unsigned)x & 0xFFFFu;
+        // The lanes past the nv comparable samples all hold entry last + 1, which is 0 (2^16 in 16 bits) and compares true like
+        // sample 0: the count is (kk + 1) + (64 - nv), no mask needed.  Sample kk is the last one <= cum.
+        const int kk = (int)__popcll(__ballot(p[k] <= cum)) + nv1 - 64;
+        // S = 1: the samples are the row (kk <= last <= 62)
+        int sym = kk;
+        unsigned cur = (unsigned)__builtin_amdgcn_readlane((int)p[k], kk);
+        unsigned nxt = (unsigned)__builtin_amdgcn_readlane((int)p[k], kk + 1);
+        if (S != 1) {
+          const int ro = __builtin_amdgcn_readlane(ro_v, u);
+          int lo = kk * S, c;                             // entry lo <= cum; lo <= last
+          unsigned f;
+          for (;;) {                                      // one trip unless S was capped; lo grows by 63 and stays <= last
+            const int mm = min(last - lo, 63);            // lanes 1 ... mm hold comparable entries, the lanes behind them 0
+            f = c16[ro + min(lo + lane, last + 1)];
+            c = (int)__popcll(__ballot(f <= cum)) + mm - 64;   // entries lo + 1 ... lo + c are <= cum
+            if (c < 63) break;
+            lo += 63;
+          }
+          sym = lo + c;
+          cur = (unsigned)__builtin_amdgcn_readlane((int)f, c);
+          nxt = (unsigned)__builtin_amdgcn_readlane((int)f, c + 1);
+        }
+        const unsigned freq = ((nxt - cur - 1u) & 0xFFFFu) + 1u;
+        x = (unsigned long long)freq * (x >> R_PREC) + (cum - cur);
+        if (__builtin_expect(low(x), 0)) x = (x << 32) | next_word();
+        int value = sym;
+        if (__builtin_expect(sym == last, 0)) {                                // escape: bypass digits
+          unsigned val = get_bits();
+          int nbd = (int)val;
+          while (val == R_MAXB && nbd < 64) { val = get_bits(); nbd += (int)val; }
+          unsigned raw = 0;
+          for (int j = 0; j < nbd; ++j) { const unsigned b = get_bits(); if (j < 8) raw |= b << (j * R_BYP); }
+          value = (int)(raw >> 1);
+          value = (raw & 1) ? -value - 1 : value + last;
+        }
+        out_v = lane == u ? value + voff : out_v;
+      }
+    };
+    // the samples of the NEXT group are requested while this group is decoded (two groups per trip, the buffers swapping
+    // roles as in k_rans_decode_lds)
+    unsigned pa[WB], pb[WB];
+    fetch(0, pa);
+    for (int u0 = 0; u0 < nb; u0 += 2 * WB) {
+      fetch(u0 + WB, pb);
+      __builtin_amdgcn_sched_barrier(0);
+      run(u0, pa);
+      __builtin_amdgcn_sched_barrier(0);
+      if (u0 + 2 * WB < nb) fetch(u0 + 2 * WB, pa);
+      __builtin_amdgcn_sched_barrier(0);
+      run(u0 + WB, pb);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (lane < nb) out[addr(j0 + lane)] = out_v;
+  }
+  if (wbase + (unsigned)widx - 1u - off > len && lane == 0) *status = 3;   // consumed past its own stream: corrupt input
+}
+
 // fallback when the decoder table does not fit LDS: generic search in global memory
 __global__ void __launch_bounds__(64) k_rans_decode_global(const unsigned* __restrict__ data, long long nwords_total,
                                                            const int* __restrict__ idx, StreamGeom g, RansTab t,
@@ -747,13 +919,20 @@ extern "C" int pcc_rans_encode_streams(const int32_t* sym, const int32_t* idx, i
   return PCC_OK;
 }
 
-extern "C" int pcc_rans_decode_streams(const uint8_t* data, int64_t nbytes, const int32_t* idx, int64_t n,
-                                       int32_t channels, int32_t n_groups, int32_t n_segments,
-                                       const int32_t* cdf, int32_t cdf_stride, const int32_t* sizes,
-                                       const int32_t* offsets, const void* dec_table, int64_t dec_bytes, int32_t* sym_out,
-                                       int32_t* d_status, void* stream) {
+// Which LDS decoder runs (form 0 = automatic): wave per stream (2) while one round of workgroups of at most 16 waves covers
+// all streams, lane per stream (1) above that.  Measured on MI355X, profiles/rans_wave_decode_crossover.txt.  env
+// PCC_RANS_FORM (read once) sets the form pcc_rans_decode_streams asks for.
+static constexpr int RANS_WAVES_PER_CU = 16;
+static int g_rans_form = getenv("PCC_RANS_FORM") ? atoi(getenv("PCC_RANS_FORM")) : 0;
+
+extern "C" int pcc_rans_decode_streams_form(const uint8_t* data, int64_t nbytes, const int32_t* idx, int64_t n,
+                                            int32_t channels, int32_t n_groups, int32_t n_segments,
+                                            const int32_t* cdf, int32_t cdf_stride, const int32_t* sizes,
+                                            const int32_t* offsets, const void* dec_table, int64_t dec_bytes,
+                                            int32_t* sym_out, int32_t* d_status, void* stream, int32_t form) {
   hipStream_t s = (hipStream_t)stream;
   PCC_REQUIRE(data && cdf && sizes && offsets && sym_out && d_status, "pcc_rans_decode_streams: NULL array");
+  PCC_REQUIRE(form >= 0 && form <= 2, "pcc_rans_decode_streams: form %d (0 automatic, 1 lane per stream, 2 wave per stream)", form);
   StreamGeom g;
   PCC_REQUIRE(n >= 0 && stream_geom(n, channels, n_groups, n_segments, &g) == 0,
               "pcc_rans_decode_streams: bad geometry: %d channels, %d groups (power-of-two size), %d segments, "
@@ -766,15 +945,34 @@ extern "C" int pcc_rans_decode_streams(const uint8_t* data, int64_t nbytes, cons
   const bool in_lds = dec_table && dec_bytes > 0 && dec_bytes <= 150 * 1024 && dec_bytes % 4 == 0;
   if (in_lds) {
     static unsigned long long attr_set = 0;                      // one bit per device (hipFuncSetAttribute is per device)
+    static int cus[64];                                          // compute units per device
     int dev = 0;
     PCC_CHECK_HIP(hipGetDevice(&dev));
     if (!(attr_set >> (dev & 63) & 1ull)) {
       PCC_CHECK_HIP(hipFuncSetAttribute((const void*)k_rans_decode_lds<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       PCC_CHECK_HIP(hipFuncSetAttribute((const void*)k_rans_decode_lds<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      PCC_CHECK_HIP(hipFuncSetAttribute((const void*)k_rans_decode_wave<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      PCC_CHECK_HIP(hipFuncSetAttribute((const void*)k_rans_decode_wave<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      PCC_CHECK_HIP(hipDeviceGetAttribute(&cus[dev & 63], hipDeviceAttributeMultiprocessorCount, dev));
       attr_set |= 1ull << (dev & 63);
     }
     // LDS: table + per-row offsets (row count = first word of the table, bounded by its size) + scan scratch
     const size_t lds = (size_t)dec_bytes + (size_t)dec_bytes / 128 + 64;
+    const int ncu = cus[dev & 63] > 0 ? cus[dev & 63] : 1;
+    if (form == 2 || (form == 0 && g.n_streams <= RANS_WAVES_PER_CU * ncu)) {
+      // W waves per workgroup (the LDS table admits one workgroup per CU): one round of workgroups where the streams allow
+      const int64_t per_cu = pcc_cdiv(g.n_streams, ncu);
+      const int W = (int)(per_cu < 1 ? 1 : (per_cu > RANS_WAVES_PER_CU ? RANS_WAVES_PER_CU : per_cu));
+      const unsigned wblocks = (unsigned)pcc_cdiv(g.n_streams, W);
+      if (idx)
+        k_rans_decode_wave<true><<<wblocks, 64 * W, lds, s>>>((const unsigned*)data, (unsigned)(nbytes / 4), idx, g, offsets,
+                                                             (const int*)dec_table, (int)(dec_bytes / 4), sym_out, d_status);
+      else
+        k_rans_decode_wave<false><<<wblocks, 64 * W, lds, s>>>((const unsigned*)data, (unsigned)(nbytes / 4), idx, g, offsets,
+                                                              (const int*)dec_table, (int)(dec_bytes / 4), sym_out, d_status);
+      PCC_LAUNCH_CHECK();
+      return PCC_OK;
+    }
     const unsigned blocks = (unsigned)pcc_cdiv(g.n_streams, 256);
     if (idx)
       k_rans_decode_lds<true><<<blocks, 256, lds, s>>>((const unsigned*)data, (unsigned)(nbytes / 4), idx, g, offsets,
@@ -788,4 +986,14 @@ extern "C" int pcc_rans_decode_streams(const uint8_t* data, int64_t nbytes, cons
   }
   PCC_LAUNCH_CHECK();
   return PCC_OK;
+}
+
+extern "C" int pcc_rans_decode_streams(const uint8_t* data, int64_t nbytes, const int32_t* idx, int64_t n,
+                                       int32_t channels, int32_t n_groups, int32_t n_segments,
+                                       const int32_t* cdf, int32_t cdf_stride, const int32_t* sizes,
+                                       const int32_t* offsets, const void* dec_table, int64_t dec_bytes, int32_t* sym_out,
+                                       int32_t* d_status, void* stream) {
+  return pcc_rans_decode_streams_form(data, nbytes, idx, n, channels, n_groups, n_segments, cdf, cdf_stride, sizes, offsets,
+                                      dec_table, dec_bytes, sym_out, d_status, stream,
+                                      g_rans_form >= 0 && g_rans_form <= 2 ? g_rans_form : 0);
 }

@@ -146,6 +146,7 @@ SIGNATURES = {
     "pcc_rans_dec_table_bytes": (_i64, [_i32, _p]),
     "pcc_rans_build_dec_table": (C.c_int, [_p, _i32, _i32, _p, _p]),
     "pcc_rans_decode_streams": (C.c_int, [_p, _i64, _p, _i64, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _i64, _p, _p, _p]),
+    "pcc_rans_decode_streams_form": (C.c_int, [_p, _i64, _p, _i64, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _i64, _p, _p, _p, _i32]),
     "pcc_octree_max_bytes": (_i64, [_i64, _i32]),
     "pcc_octree_encode_host": (C.c_int, [_p, _i64, _i32, _p, _i64, C.POINTER(_i64)]),
     "pcc_octree_decode_host": (C.c_int, [_p, _i64, _p, _i64, C.POINTER(_i64), C.POINTER(_i32)]),
