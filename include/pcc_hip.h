@@ -633,6 +633,55 @@ int pcc_normals_grid(const int64_t* keys, int64_t n, const uint64_t* grid_bits /
                      float* normals /*[n,3]*/, int32_t* counts /*nullable*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 9    training batches: cube slicing and the per-step augmented batch (reference data/dataloader.py:168-208
+ *      StaticDataset.slice_into_cubes; data/transform.py:32-54 ColorJitter, :57-123 RandomRotate; train.py:199-208
+ *      sparse_collate + sparse_quantize).
+ * ---------------------------------------------------------------------------------------- */
+/* dataloader.py:186,196-197: per point of [n,3] fp32, keys[i] = the cube indices floor(p / cube_size) (fp32 division,
+ * round to nearest), each biased by 2^15 into a 16-bit field, x most significant -- integer order is the lexicographic
+ * (ix, iy, iz) order of torch.unique(dim=0) -- and local[i] = p - index * cube_size.  *d_bad (device int32) != 0 when an
+ * index does not fit its field or a point is not finite.  Group with the stable sort + run starts that exist for keys. */
+int pcc_cube_keys(const float* points, int64_t n, int32_t cube_size, int64_t* keys, float* local /*[n,3]*/, int32_t* d_bad,
+                  void* stream);
+/* dataloader.py:191-194: out[i] = in[perm[i]] for both [n,3] arrays at once (perm: the sort's permutation) */
+int pcc_cube_regroup(const float* local, const float* colors, const int32_t* perm, int64_t n, float* out_points,
+                     float* out_colors, void* stream);
+
+/* Batch-slot descriptor: PCC_AUG_SLOT_WORDS 4-byte words per slot, host-built, uploaded once per step.
+ *   [0] in_begin   first row of the slot's cube in the table        [1] rows
+ *   [2] out_begin  first row of the slot in the batch arrays        [3] nsteps (0..4 colour steps)
+ *   [4..7]   steps, applied in this order (PCC_AUG_*)               [8..11]  fp32 factors by step kind: b, c, s, hue shift
+ *   [12..20] fp32 rotation matrix R, row-major                      [21]     fp32 centre c (block_size / 2)
+ *   [22] first_block, [23] nblocks: the slot's run in the block table
+ *   [24..26] lo, [27..29] hi: int32 box that holds every output coordinate of the slot (the caller's bound; the caller sizes
+ *            its de-duplication lattice from it without reading coordinates back); the rest is padding.
+ * Block table: int32 pairs (slot, first row in the slot), PCC_AUG_BLOCK_ROWS rows per workgroup, slots ascending.
+ * Both tables are passed twice, as the host original (validated before any launch: ranges inside the table, output ranges
+ * tiling [0, out_rows) in slot order, block table equal to the enumeration) and as its device copy (read by the kernels). */
+#define PCC_AUG_SLOT_WORDS 32
+#define PCC_AUG_BLOCK_ROWS 1024
+#define PCC_AUG_MAX_SLOTS 4096
+#define PCC_AUG_BRIGHTNESS 0
+#define PCC_AUG_CONTRAST 1
+#define PCC_AUG_SATURATION 2
+#define PCC_AUG_HUE 3
+/* transform.py:36-40, the contrast step of ColorJitter: means[slot] = mean over the slot's rows of the grey value
+ * 0.2989 r + 0.587 g + 0.114 b of the colour as the contrast step finds it (after the steps before it in the slot's order);
+ * 0 for a slot without one.  fp64 sums in a fixed order (partials [nblocks] fp64, one per workgroup; no atomics): the same
+ * inputs give the same bits.  Launches nothing when no slot has a contrast step. */
+int pcc_aug_gray_sums(const float* colors, int64_t table_rows, const int32_t* h_slots, const int32_t* d_slots, int32_t nslots,
+                      const int32_t* h_blocks, const int32_t* d_blocks, int32_t nblocks, double* partials, float* means,
+                      void* stream);
+/* transform.py:42-54,74-93 + train.py:199-201 in one launch: for every row of every slot the colour steps in the slot's
+ * order, out = (p - c) R^T + c evaluated as ((dx R[j][0] + dy R[j][1]) + dz R[j][2]) + c with every product and sum rounded
+ * to fp32 separately (no FMA), floor; out_coords [out_rows,4] int32 = (slot, x, y, z), out_feats [out_rows,3] fp32.
+ * means: from the gray-sums call (nullable when no slot has a colour step).  A coordinate outside its slot's box is moved
+ * onto the box and *d_outside (device int32, zeroed here) is set: with a correct bound that never happens. */
+int pcc_aug_batch(const float* points, const float* colors, int64_t table_rows, const int32_t* h_slots, const int32_t* d_slots,
+                  int32_t nslots, const int32_t* h_blocks, const int32_t* d_blocks, int32_t nblocks, const float* means,
+                  int32_t* out_coords, float* out_feats, int64_t out_rows, int32_t* d_outside, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * measurement support: per-launch HIP-event timing of the conv kernel (bench.py roofline)
  * ---------------------------------------------------------------------------------------- */
 int pcc_prof_enable(int32_t on);

@@ -7,6 +7,7 @@ Layout
   MinkowskiEngine/        `import MinkowskiEngine as ME` compatible surface
   compressai/             `compressai.*` compatible surface
   model/                  UnifiedModel.compress()/decompress() counterpart of the reference's model/
+  data.py                 training batches: cube slicing, colour jitter, rotation, collation on the GPU (reference data/)
   frames.py               frame/block sharding across GPUs (one process per GPU, RCCL gather)
 """
 import sys

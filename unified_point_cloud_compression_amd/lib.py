@@ -158,6 +158,10 @@ SIGNATURES = {
                                      C.c_float, _i32, _p, _p]),
     "pcc_nn_sorted_x": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _p]),
     "pcc_normals_grid": (C.c_int, [_p, _i64, _p, C.POINTER(_i32), _i32, _p, _p, _p]),
+    "pcc_cube_keys": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p]),
+    "pcc_cube_regroup": (C.c_int, [_p, _p, _p, _i64, _p, _p, _p]),
+    "pcc_aug_gray_sums": (C.c_int, [_p, _i64, _p, _p, _i32, _p, _p, _i32, _p, _p, _p]),
+    "pcc_aug_batch": (C.c_int, [_p, _p, _i64, _p, _p, _i32, _p, _p, _i32, _p, _p, _p, _i64, _p, _p]),
     "pcc_prof_enable": (C.c_int, [_i32]),
     "pcc_prof_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(_i64)]),
     "pcc_prof_sequence": (_i64, [C.POINTER(_i32), _i64]),
