@@ -243,11 +243,11 @@ int pcc_map_to_dense(const int32_t* hdr, const int32_t* nbr, const int32_t* rows
 #define PCC_H_GUARD_BUDGET 2.5e-5f   /* a quarter of the 1e-4 parity bar: max|row| * max|column| > 26 at cin = 128 */
 /* 4-channel inputs (the codec's first layer, 4 -> 128, 5x5x5, stride 2): from `rows` output rows on, the (offset, channel)
  * pairs are flattened into one reduction axis and the convolution runs in 32-wide chunks of 8 offsets on the six-term bf16
- * form (default 65536; env PCC_IN4_MIN_ROWS; negative: never).  Tests lower it to reach the path on small inputs. */
+ * form (default 65536; negative: never).  Tests lower it to reach the path on small inputs. */
 int pcc_set_in4_min_rows(int64_t rows);
 /* pcc_conv_thin_grid_fwd with one output channel over 16 input channels (the last level's occupancy head): from `rows` rows on
  * the projection pass pre-adds a column's three z terms for the middle row and the gather reads one value per (dx, dy) column
- * (default 2^20; env PCC_THIN_Z_MIN_ROWS; negative: never).  Tests lower it to reach the path on small inputs. */
+ * (default 2^20; negative: never).  Tests lower it to reach the path on small inputs. */
 int pcc_set_thin_z_min_rows(int64_t rows);
 int64_t pcc_conv_packed_elems(int32_t K, int32_t cin, int32_t cout);
 /* W: ME layout [K, cin, cout] row-major (state_dict `kernel`).  packed_cap: floats available at
@@ -334,22 +334,6 @@ int pcc_convt_fwd_csr_grid(const float* feat_in, int64_t n_in, int32_t cin, cons
                            const int32_t* out_rank, const int32_t* h_out, const float* ex_bias,
                            const int32_t* wg_end /*nullable: first / pair_ids are the slotted lists of pcc_coords_expand_grid_csr_slots*/,
                            int32_t arith, int32_t* d_guard /*nullable*/, void* stream);
-/* Chunked form of pcc_convt_fwd_csr for 7x7x7 composite levels: the per-pair products never exist as a whole.  Parent rows
- * are processed in chunks whose products fit the Infinity Cache (pcc_set_t_chunk_bytes, default 96 MiB; env PCC_T_CHUNK_MIB):
- * GEMM chunk -> staging buffer T (pcc_convt_chunk_t_bytes) -> ordered gather-sum of the children that chunk reaches, partial
- * sums carried in `out`.  Same summation order per output row as the one-pass form (bit-identical result).  in_keys/out_keys:
- * canonical keys of the input / output rows; ts_out: output pitch; ws: pcc_convt_chunk_ws_bytes.  ex_bias (nullable) as in
- * pcc_convt_fwd_csr_grid (then out_bits/out_rank/h_out are the output set's pcc_grid_build arrays). */
-int pcc_set_t_chunk_bytes(int64_t bytes);
-size_t pcc_convt_chunk_t_bytes(int64_t n_in, int32_t K, int32_t cout);
-size_t pcc_convt_chunk_ws_bytes(int64_t n_in, int32_t K, int32_t cout);
-int pcc_convt_fwd_csr_chunked(const float* feat_in, int64_t n_in, int32_t cin, const float* packed_w, const float* bias /*nullable*/,
-                              int32_t K, int32_t cout, const int32_t* first, const int32_t* pair_ids, int64_t n_out,
-                              const int64_t* in_keys, const int64_t* out_keys, int32_t ts_out, float* T, size_t t_bytes,
-                              float* out, int32_t act, float slope, const uint64_t* out_bits /*nullable*/,
-                              const int32_t* out_rank /*nullable*/, const int32_t* h_out /*nullable*/,
-                              const float* ex_bias /*nullable*/, void* ws, size_t ws_bytes, int32_t arith,
-                              int32_t* d_guard /*nullable*/, void* stream);
 size_t pcc_thin_grid_ws_bytes(int64_t n, int32_t cout);
 int pcc_conv_thin_grid_fwd(const float* feat, int64_t n, int32_t cin, const float* packed_w, const float* bias /*nullable*/,
                            int32_t cout, const int64_t* keys, const uint64_t* bits, const int32_t* rank, const int32_t* h_grid,
@@ -587,7 +571,7 @@ int pcc_rans_decode_streams(const uint8_t* data, int64_t nbytes, const int32_t* 
 /* The same with the decoder form chosen by the caller (tests, A/B runs).  With the table in LDS there are two decoders:
  * form 1, one LANE per stream (256 streams per workgroup), and form 2, one WAVE per stream (the lanes share the symbol
  * search; up to 16 streams per workgroup).  form 0 picks form 2 while one round of workgroups covers all streams and
- * form 1 above that; pcc_rans_decode_streams passes the value of env PCC_RANS_FORM (read once, default 0).  Both forms
+ * form 1 above that; pcc_rans_decode_streams passes form 0.  Both forms
  * give the same symbols and status words.  Without an LDS table the form is ignored. */
 int pcc_rans_decode_streams_form(const uint8_t* data, int64_t nbytes, const int32_t* idx, int64_t n, int32_t channels,
                                  int32_t n_groups, int32_t n_segments, const int32_t* cdf, int32_t cdf_stride,

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The dense products of a composite level alone (k_gemm_h2 through pcc_convt_fwd_csr, event-timed inside the library):
-gemm_h2_probe.py [N=58051] [CIN=128] [K=343] [COUT=64] [reps=6].  Env switches (PCC_STAGGER, PCC_DBG, ...) apply."""
+gemm_h2_probe.py [N=58051] [CIN=128] [K=343] [COUT=64] [reps=6].  Env switches (PCC_DBG, PCC_NT) apply."""
 import os
 import sys
 
@@ -30,5 +30,4 @@ L.call("pcc_prof_enable", 0)
 for nme, v in f.items():
     if v["launches"]:
         ms = v["ms"] / v["launches"]
-        print(f"{nme}: {ms:.3f} ms per launch  {v['flops'] / v['launches'] / ms / 1e9:.0f} TFLOP/s  {v['bytes'] / v['launches'] / ms / 1e6:.0f} GB/s "
-              f"(PCC_STAGGER={os.environ.get('PCC_STAGGER', '0')})")
+        print(f"{nme}: {ms:.3f} ms per launch  {v['flops'] / v['launches'] / ms / 1e9:.0f} TFLOP/s  {v['bytes'] / v['launches'] / ms / 1e6:.0f} GB/s")

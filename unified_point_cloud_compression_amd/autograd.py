@@ -17,7 +17,6 @@ Round 4 (the training step of BASELINE configs[3] is bound by launch count and h
     `FocalRowsFn` (one occupancy level of the focal loss), `GdnFn.backward` (library products + four element-wise kernels,
     the reparametrisation's gradient included) replace chains of 10-40 torch launches each.
 """
-import os
 
 import torch
 
@@ -25,8 +24,8 @@ from . import lib as L
 from . import sparse as S
 
 
-GDN_FUSED_BWD = os.environ.get("PCC_GDN_FUSED_BWD", "1") != "0"  # GDN backward: element-wise parts and reparametrisation as kernels
-WGRAD_SELF = os.environ.get("PCC_WGRAD_SELF", "1") != "0"     # one-logit heads: input-stationary weight gradient
+GDN_FUSED_BWD = True  # GDN backward: element-wise parts and reparametrisation as kernels
+WGRAD_SELF = True     # one-logit heads: input-stationary weight gradient
 
 
 def _pack(w3):
@@ -219,7 +218,7 @@ class GdnFn(torch.autograd.Function):
     @staticmethod
     def _backward_torch(ctx, g):
         """The same gradients with torch operators around the library's products (channel counts the fused path does not take;
-        `PCC_GDN_FUSED_BWD=0`; the reference the fused path is tested against)."""
+        `GDN_FUSED_BWD = False`; the reference the fused path is tested against)."""
         x, beta_raw, gamma_raw = ctx.saved_tensors
         m = ctx.module
         with torch.enable_grad():

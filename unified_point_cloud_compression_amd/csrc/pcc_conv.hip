@@ -32,7 +32,6 @@ enum { MODE_CONV = 0, MODE_GDN = 1, MODE_IGDN = 2 };
 #else
 #define PCC_DBG_ON(a, bit) false
 #endif
-static constexpr int PAIR_BM_C = 128;   // rows per pair tile (pair-list GEMMs)
 __device__ inline float act1(float v, int act, float slope);
 
 struct ConvArgs {
@@ -1366,13 +1365,11 @@ __global__ void __launch_bounds__(256, 3) k_conv_in4_bf(ConvArgs a, const unsign
 // The dense products in scaled fp16 pairs (see k_feat_split_h): the structure of k_gemm_bf2 with two planes per operand
 // (8 units of 16 bytes per 32-channel piece, LDS rows of 9 units: 9 is odd, so a fragment read's 16 rows fall on 16 different
 // bank quads), three MFMA terms, and the row and column scales applied to the accumulators on the way out.
-// TN = 32-column MFMA tiles per wave: 2 -> the 128 x 128 workgroup tile, 4 -> 128 x 256 (round 4).  Per tile the kernel reads
-// (128 + BN) operand rows of NCH * 128 B from L2 for 128 * BN * 4 B of products: 2 B read per B written at BN = 128, 1.5 at
-// BN = 256 -- with the product stores out of the operands' way (non-temporal) the L2 -> LDS operand stream is what is left to
-// shrink.  128 accumulator registers per lane, two workgroups per CU.
-template <int NCH, int TN = 2>
-__global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) k_gemm_h2(ConvArgs a) {
-  constexpr int BM = 128, BN = 64 * TN, LDU = 9, NB = BN / 32;
+// TN = 2 32-column MFMA tiles per wave: the 128 x 128 workgroup tile.  Per tile the kernel reads (128 + BN) operand rows of
+// NCH * 128 B from L2 for 128 * BN * 4 B of products: 2 B read per B written.
+template <int NCH>
+__global__ void __launch_bounds__(256, 3) k_gemm_h2(ConvArgs a) {
+  constexpr int TN = 2, BM = 128, BN = 64 * TN, LDU = 9, NB = BN / 32;
   constexpr unsigned ROWB = NCH * 128u;                // bytes of a feature row's planes
   __shared__ __attribute__((aligned(16))) uint4 As[BM * LDU];
   __shared__ __attribute__((aligned(16))) uint4 Bs[BN * LDU];
@@ -1400,7 +1397,7 @@ __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) k_gemm_h2(ConvArgs a) {
   const unsigned char* wb = reinterpret_cast<const unsigned char*>(wplanes) + (size_t)colblock * 128u;
   const float* const cinv = wplanes + a.wp_elems;                                    // [cout_pad] column 1/scale
   const unsigned b_stride = (unsigned)a.cout_pad * 128u;
-  const int bcols = min(BN, a.cout_pad - colblock);                                  // (the last 256-wide block may hold 128 columns)
+  const int bcols = min(BN, a.cout_pad - colblock);
   const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<unsigned char*>(wb), (short)0, (int)((NCH - 1) * b_stride + (unsigned)bcols * 128u), 0x00020000);
 
@@ -1409,7 +1406,7 @@ __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) k_gemm_h2(ConvArgs a) {
   for (int j = 0; j < 4; ++j) vA[j] = (unsigned)((j * 256 + tid) >> 3) * ROWB + (unsigned)(tid & 7) * 16u;
 #pragma unroll
   for (int j = 0; j < NB; ++j) ld[j] = (unsigned)((j * 256 + tid) >> 3) * LDU + (unsigned)(tid & 7);
-  // column (tid >> 3) + 32 j of the block; columns past cout_pad (second half of the last wide block) read zeros
+  // column (tid >> 3) + 32 j of the block; columns past cout_pad read zeros
   unsigned vB[NB];
 #pragma unroll
   for (int j = 0; j < NB; ++j) vB[j] = ((tid >> 3) + 32 * j < bcols) ? (unsigned)tid * 16u + (unsigned)j * 4096u : BUF_OOB;
@@ -1421,11 +1418,7 @@ __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) k_gemm_h2(ConvArgs a) {
       av[j] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsA, PCC_DBG_ON(a, 4) ? BUF_OOB : vA[j] + (unsigned)cbi * 128u, 0, 0));
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
-      if constexpr (TN == 2) {
-        bv[j] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsB, PCC_DBG_ON(a, 4) ? BUF_OOB : vB[0], (int)((unsigned)cbi * b_stride + (unsigned)j * 4096u), 0));
-      } else {
-        bv[j] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsB, (PCC_DBG_ON(a, 4) || vB[j] == BUF_OOB) ? BUF_OOB : vB[j] + (unsigned)cbi * b_stride, 0, 0));
-      }
+      bv[j] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsB, PCC_DBG_ON(a, 4) ? BUF_OOB : vB[0], (int)((unsigned)cbi * b_stride + (unsigned)j * 4096u), 0));
     }
   };
 
@@ -1665,187 +1658,6 @@ __global__ void __launch_bounds__(256, 3) k_pair_h2(ConvArgs a) {
       }
     }
   if (a.guard && guard_mr * fmaxf(cs[0], cs[1]) * (8.f * (float)a.cin) > a.guard_lim) atomicOr(a.guard, 1);   // range guard, as in k_gemm_h2
-}
-
-// ------------------------------------------------------------------------------------------
-// Persistent form of the split kernel for the GEMM-shaped launches -- dense [n, cin] x [cin, ncol] (generative transposed
-// convolutions, 1x1 convolutions, GDN) and the gathered pair GEMMs (one kernel offset per 128-pair tile).  Their
-// reduction is only cin deep (4 chunks at cin = 128): with one tile per workgroup the tile's first loads (full memory
-// latency) and its drain were exposed on every tile, and the matrix pipe idled two thirds of the time (SQ counters,
-// DESIGN.md section 8).  Here a workgroup walks a strided sequence of tiles as ONE chunk stream: the loads of the next
-// tile's first chunk are in flight while the current tile's last chunk is multiplied and its accumulators are stored.
-// Work ids are dealt in contiguous ranges per XCD (L2 locality as in k_conv_mfma); the dense form visits row tiles in
-// groups of 8 per column block so that a block's weights are fetched once per group.
-// ------------------------------------------------------------------------------------------
-template <int WM, int WN, int TM, int TN, int MODE>
-__global__ void __launch_bounds__(256, 2) k_gemm_bf(ConvArgs a) {
-  constexpr int BM = WM * TM * 32;
-  constexpr int BN = WN * TN * 32;
-  static_assert(WM * WN == 4, "4 waves per workgroup");
-  constexpr int LDU = 13;
-  __shared__ __attribute__((aligned(16))) uint4 As[BM * LDU];
-  __shared__ __attribute__((aligned(16))) uint4 Bs[BN * LDU];
-
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const bool pair_mode = (a.pair_in != nullptr);
-  const int gy = a.cout_pad / BN;
-  const long long n_tiles = pair_mode ? *a.n_tiles : (a.n_out + BM - 1) / BM;
-  const bool groups = !pair_mode && gy > 8;
-  const long long total = (groups ? (n_tiles + 7) / 8 * 8 : n_tiles) * gy;
-  const int nwg_x = gridDim.x >> 3;
-  const long long per = (total + 7) / 8;
-  const long long lo = (long long)(blockIdx.x & 7) * per, hi = min(total, lo + per);
-
-  constexpr int NA = (BM * 12 + 255) / 256, NB = (BN * 12 + 255) / 256;
-  int a_row[NA], a_w[NA], b_row[NB];
-#pragma unroll
-  for (int j = 0; j < NA; ++j) { const int u = j * 256 + tid; a_row[j] = u / 12; a_w[j] = u - a_row[j] * 12; if (u >= BM * 12) a_row[j] = -1; }
-#pragma unroll
-  for (int j = 0; j < NB; ++j) { const int u = j * 256 + tid; b_row[j] = (u < BN * 12) ? u / 12 : -1; }
-
-  const int wm = w / WN, wn = w % WN;
-  const int half = lane >> 5, r31 = lane & 31;
-  const unsigned row_bytes = (unsigned)a.cin * 6u;
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<unsigned char*>(a.featb), (short)0, (int)(unsigned)((size_t)a.n_in * row_bytes), 0x00020000);
-  const float* wb = a.wp + a.wp_elems;
-  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(wb), (short)0, (int)(unsigned)((size_t)bf_plane_elems(a.wp_elems) * 4), 0x00020000);
-
-  struct Work { long long id; int tile, colblock, pos0, npos, kid; };
-  auto decode = [&](long long id, Work& wk) {           // first valid work item at or after `id` (stride nwg_x); id >= hi: none
-    for (; id < hi; id += nwg_x) {
-      int tile, cb;
-      if (groups) { const long long g = id / (8 * gy); const int rem = (int)(id - g * 8 * gy); cb = rem >> 3; tile = (int)(g * 8 + (rem & 7)); }
-      else { tile = (int)(id / gy); cb = (int)(id - (long long)tile * gy); }
-      if (tile < n_tiles) {
-        wk.tile = tile; wk.colblock = cb * BN; wk.pos0 = tile * BM;
-        wk.npos = pair_mode ? BM : (int)min((long long)BM, a.n_out - (long long)tile * BM);
-        wk.kid = pair_mode ? a.tile_k[tile] : 0;
-        break;
-      }
-    }
-    wk.id = id;
-  };
-  auto load_rows = [&](const Work& wk, int (&rows)[NA]) {
-#pragma unroll
-    for (int j = 0; j < NA; ++j) {
-      const int rc = min(max(a_row[j], 0), wk.npos - 1);        // tail rows repeat the tile's last row (never stored)
-      rows[j] = pair_mode ? a.pair_in[wk.pos0 + rc] : (wk.pos0 + rc);
-      if (a_row[j] < 0) rows[j] = -1;
-    }
-  };
-  auto issue = [&](const Work& wk, int cbi, const int (&rows)[NA], uint4 (&av)[NA], uint4 (&bv)[NB]) {
-#pragma unroll
-    for (int j = 0; j < NA; ++j) {
-      const unsigned off = rows[j] >= 0 ? (unsigned)rows[j] * row_bytes + (unsigned)cbi * 192u + (unsigned)a_w[j] * 16u : BUF_OOB;
-      av[j] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsA, off, 0, 0));
-    }
-    const unsigned wbase = (unsigned)((wk.kid * a.ppo + cbi) * a.cout_pad + wk.colblock) * 192u;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      const unsigned off = b_row[j] >= 0 ? wbase + (unsigned)(j * 256 + tid) * 16u : BUF_OOB;
-      bv[j] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsB, off, 0, 0));
-    }
-  };
-
-  Work cur, nxt;
-  decode(lo + (blockIdx.x >> 3), cur);
-  if (cur.id >= hi) return;
-  int rows_cur[NA], rows_nxt[NA];
-  uint4 av[NA], bv[NB];
-  load_rows(cur, rows_cur);
-  issue(cur, 0, rows_cur, av, bv);
-  int c = 0;                                             // chunk of `cur` whose data sits in av / bv
-  const int ppo = a.ppo;
-
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-  // what the chunk after (cur, c) is: the same tile's next piece, or the first piece of the next work item
-  bool have_nxt = false;
-  if (ppo == 1) { decode(cur.id + nwg_x, nxt); have_nxt = nxt.id < hi; if (have_nxt) load_rows(nxt, rows_nxt); }
-
-  while (true) {
-    __syncthreads();   // previous chunk's fragment reads are done
-#pragma unroll
-    for (int j = 0; j < NA; ++j)
-      if (a_row[j] >= 0) As[a_row[j] * LDU + a_w[j]] = av[j];
-#pragma unroll
-    for (int j = 0; j < NB; ++j)
-      if (b_row[j] >= 0) Bs[b_row[j] * LDU + (j * 256 + tid) - b_row[j] * 12] = bv[j];
-    __syncthreads();
-    const bool last_piece = (c + 1 == ppo);
-    // prefetch the following chunk (possibly of the next tile) so that it flies during this chunk's MFMAs
-    if (!last_piece) {
-      issue(cur, c + 1, rows_cur, av, bv);
-      if (c + 2 == ppo) { decode(cur.id + nwg_x, nxt); have_nxt = nxt.id < hi; if (have_nxt) load_rows(nxt, rows_nxt); }
-    } else if (have_nxt) {
-      issue(nxt, 0, rows_nxt, av, bv);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 af[3][TM], bf[3][TN];
-#pragma unroll
-      for (int p = 0; p < 3; ++p) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-          af[p][i] = __builtin_bit_cast(bf16x8, As[((wm * TM + i) * 32 + r31) * LDU + p * 4 + ks * 2 + half]);
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          bf[p][j] = __builtin_bit_cast(bf16x8, Bs[((wn * TN + j) * 32 + r31) * LDU + p * 4 + ks * 2 + half]);
-      }
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {           // smallest terms first
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[2][i], bf[0][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[2][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][i], bf[1][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][i], bf[0][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[1][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[0][j], acc[i][j], 0, 0, 0);
-        }
-    }
-    if (!last_piece) { ++c; continue; }
-
-    // ---- tile finished: bias, activation (or GDN), store; then move on to the prefetched tile ----------------------
-    {
-      const int pos0 = cur.pos0, npos = cur.npos, colblock = cur.colblock;
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int col = colblock + (wn * TN + j) * 32 + r31;
-        const float b = (a.bias && col < a.cout) ? a.bias[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const int r = (wm * TM + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
-            float v = acc[i][j][e] + b;
-            acc[i][j][e] = 0.f;
-            if (r >= npos || col >= a.cout) continue;
-            const size_t o = (size_t)(pos0 + r) * a.cout + col;
-            if (MODE == MODE_CONV) v = act1(v, a.act, a.slope);
-            else { const float x = a.feat[o]; v = (MODE == MODE_GDN) ? x / v : x * v; }
-            a.out[o] = v;
-          }
-        }
-      }
-    }
-    if (!have_nxt) break;
-    cur = nxt;
-#pragma unroll
-    for (int j = 0; j < NA; ++j) rows_cur[j] = rows_nxt[j];
-    c = 0;
-    have_nxt = false;
-    if (ppo == 1) { decode(cur.id + nwg_x, nxt); have_nxt = nxt.id < hi; if (have_nxt) load_rows(nxt, rows_nxt); }
-  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2642,36 +2454,11 @@ __global__ void __launch_bounds__(256) k_splitk_reduce(const float* __restrict__
   reinterpret_cast<float4*>(out)[t] = v;
 }
 
-static int g_splitk_chunks = getenv("PCC_SPLITK_CHUNKS") ? atoi(getenv("PCC_SPLITK_CHUNKS")) : 40;
-static bool g_splitk = getenv("PCC_SPLITK") ? atoi(getenv("PCC_SPLITK")) != 0 : true;
-static bool g_gemm_persistent = getenv("PCC_GEMM_PERSISTENT") ? atoi(getenv("PCC_GEMM_PERSISTENT")) != 0 : false;   // measured slower (2 workgroups per CU): off
-static bool g_splitk_tiles = getenv("PCC_SPLITK_TILES") ? atoi(getenv("PCC_SPLITK_TILES")) != 0 : true;
-static int g_gemm2 = getenv("PCC_GEMM2") ? atoi(getenv("PCC_GEMM2")) : 1;       // 0: general kernel, 1: stripped dense-GEMM kernel
+static constexpr int SPLITK_CHUNKS = 40;     // chunks of a split reduction per workgroup
 static int g_dbg = getenv("PCC_DBG") ? atoi(getenv("PCC_DBG")) : 0;
 // non-temporal accesses of the streamed multi-GB buffers (bit 0 dense products' stores, 1 pair products' stores, 2 gather-sum
 // product loads, 3 gather-sum output stores, 4 projection-plane stores, 5 projection-plane gathers); env PCC_NT
 static int g_nt = getenv("PCC_NT") ? atoi(getenv("PCC_NT")) : 1;
-
-// persistent GEMM form (identity rows or pair lists; a.featb set): 2 workgroups per CU (the kernel needs ~200 VGPRs)
-template <int MODE>
-static int launch_gemm_bf(const ConvArgs& a, hipStream_t s) {
-  int dev = 0, cus = 0;
-  PCC_CHECK_HIP(hipGetDevice(&dev));
-  PCC_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const int bn = bn_for(a.cout);
-  const long long gy = a.cout_pad / bn;
-  const long long tiles128 = a.pair_in ? a.n_out / PAIR_BM_C : pcc_cdiv(a.n_out, 128);
-  long long work = tiles128 * gy;
-  long long grid = (long long)cus * 2;
-  if (work < grid) grid = work;
-  grid = (grid + 7) / 8 * 8;
-  if (grid < 8) grid = 8;
-  if (bn == 128) k_gemm_bf<2, 2, 2, 2, MODE><<<(unsigned)grid, 256, 0, s>>>(a);
-  else if (bn == 64) k_gemm_bf<2, 2, 2, 1, MODE><<<(unsigned)grid, 256, 0, s>>>(a);
-  else k_gemm_bf<4, 1, 1, 1, MODE><<<(unsigned)grid, 256, 0, s>>>(a);
-  PCC_LAUNCH_CHECK();
-  return PCC_OK;
-}
 
 template <int MODE>
 static int launch_mfma(const ConvArgs& a_in, int tiles_bound_extra, hipStream_t s) {
@@ -2696,10 +2483,10 @@ static int launch_mfma(const ConvArgs& a_in, int tiles_bound_extra, hipStream_t 
   int ksplit = 1;
   // (round 4: also the K = 1 products with a very deep reduction -- the data gradient of a generative transposed convolution is
   //  dT [n, 125 * cout] x Wflat^T: 500 chunks in one workgroup per 128 rows, 45 workgroups, 0.58 ms for 23 GFLOP)
-  if (split && g_splitk && MODE == MODE_CONV && !a.pair_in && !a.rows && (a.cout & 3) == 0) {
+  if (split && MODE == MODE_CONV && !a.pair_in && !a.rows && (a.cout & 3) == 0) {
     const int depth = (a.hdr ? 27 : 1) * a.ppo;        // chunks of a 3x3x3 map (the maps that reach here; 5x5x5 take the pair form)
     if (tiles(128) * gy < 256 && depth >= 64) {
-      ksplit = depth / g_splitk_chunks;                // ~40 chunks per workgroup
+      ksplit = depth / SPLITK_CHUNKS;                  // ~40 chunks per workgroup
       if (ksplit > 8) ksplit = 8;
       if (ksplit < 2) ksplit = 1;
     }
@@ -2712,22 +2499,6 @@ static int launch_mfma(const ConvArgs& a_in, int tiles_bound_extra, hipStream_t 
     a.dbg = g_dbg;
     a.nt = g_nt;
     prof_note(PCC_FORM_GEMM_H2, 2.0 * a.n_out * a.cin * a.cout, 4.0 * ((double)a.n_out * a.cin + (double)a.n_out * a.cout + (double)a.cin * a.cout));
-    // 128 x 256 tiles for the wide products (the 7x7x7 composites: 5 488 / 21 952 columns): a quarter less operand traffic from
-    // L2, bit-identical results -- and 2 % SLOWER on the benchmark's three levels (2.77 against 2.72 ms per step, round 4: two
-    // workgroups per CU instead of three; the kernel is bound by its product stores, not by the operand stream).  Off; env
-    // PCC_GEMM_WIDE=1 selects it (tests/test_gpu_map_conv.py runs it in a child process).
-    static const bool wide_on = getenv("PCC_GEMM_WIDE") ? atoi(getenv("PCC_GEMM_WIDE")) != 0 : false;
-    const long long gy2 = (a.cout_pad + 255) / 256;
-    if (wide_on && (a.ppo == 4 || a.ppo == 2) && a.cout_pad >= 2048 && (size_t)128 * a.cout * 4 + 1024 < (1ull << 31)) {
-      long long t2 = pcc_cdiv(a.n_out, 128);
-      if (gy2 > 8) t2 = (t2 + 7) / 8 * 8;
-      if (t2 * gy2 >= 1024) {
-        const dim3 gw((unsigned)((t2 * gy2 + 7) / 8 * 8));
-        if (a.ppo == 4) k_gemm_h2<4, 4><<<gw, 256, 0, s>>>(a); else k_gemm_h2<2, 4><<<gw, 256, 0, s>>>(a);
-        PCC_LAUNCH_CHECK();
-        return PCC_OK;
-      }
-    }
     const dim3 g2 = grid(128);
     switch (a.ppo) {
       case 1: k_gemm_h2<1><<<g2, 256, 0, s>>>(a); break;
@@ -2755,9 +2526,8 @@ static int launch_mfma(const ConvArgs& a_in, int tiles_bound_extra, hipStream_t 
   a.dbg = g_dbg;
   a.nt = g_nt;
   ksplit_grid = a.ksplit;
-  if (split && !a.hdr && g_gemm_persistent) return launch_gemm_bf<MODE>(a, s);
   // plain dense products (generative transposed convolutions): the stripped GEMM kernel
-  if (split && g_gemm2 && MODE == MODE_CONV && !a.hdr && !a.pair_in && !a.rows && !a.bias && a.act == 0 && a.ksplit == 1 &&
+  if (split && MODE == MODE_CONV && !a.hdr && !a.pair_in && !a.rows && !a.bias && a.act == 0 && a.ksplit == 1 &&
       bn == 128 && tiles(128) * gy >= want && (size_t)128 * a.cout * 4 < (1ull << 31)) {
     const dim3 g2 = grid(128);
     bool done = true;
@@ -2780,7 +2550,7 @@ static int launch_mfma(const ConvArgs& a_in, int tiles_bound_extra, hipStream_t 
     else k_conv_mfma<WM, WN, TM, TN, MODE, false><<<grid(BMV), 256, 0, s>>>(a);                  \
   } while (0)
   // (a split reduction multiplies the grid: count it, so that split layers keep the large row tile and its weight reuse)
-  const long long ksg = g_splitk_tiles ? a.ksplit : 1;
+  const long long ksg = a.ksplit;
   if (bn == 128) {
     if (tiles(128) * gy * ksg >= want) PCC_LAUNCH_MFMA(2, 2, 2, 2, 128);
     else if (tiles(64) * gy * ksg >= want) PCC_LAUNCH_MFMA(2, 2, 1, 2, 64);
@@ -2893,12 +2663,10 @@ __global__ void __launch_bounds__(256) k_thin_project_mfma(const float* __restri
   }
 }
 
-static bool g_thin_mfma = getenv("PCC_THIN_MFMA") ? atoi(getenv("PCC_THIN_MFMA")) != 0 : true;
-
 template <int CIN>
 static int launch_project(const float* feat, int64_t n_in, const float* wt, int kc, float* t, hipStream_t s) {
   if constexpr (CIN >= 32) {
-    if (g_thin_mfma && kc <= 32) {
+    if (kc <= 32) {
       const long long tiles = pcc_cdiv(n_in, 32);
       long long grid = pcc_cdiv(tiles, 4 * 4);             // ~4 tiles per wave: the weight registers are loaded once per wave
       if (grid > 4096) grid = 4096;
@@ -2914,7 +2682,7 @@ static int launch_project(const float* feat, int64_t n_in, const float* wt, int 
 }
 
 // 4-channel inputs: output rows from which the flattened form (k_conv_in4_bf) replaces the offset-by-offset kernel; negative = never
-static long long g_in4_min_rows = getenv("PCC_IN4_MIN_ROWS") ? atoll(getenv("PCC_IN4_MIN_ROWS")) : 65536;
+static long long g_in4_min_rows = 65536;
 extern "C" int pcc_set_in4_min_rows(int64_t rows) { g_in4_min_rows = rows; return PCC_OK; }
 
 extern "C" int pcc_conv_fwd(const float* feat_in, int64_t n_in, int32_t cin, const float* packed_w,
@@ -3331,7 +3099,6 @@ extern "C" int pcc_conv_fwd_pairs(const float* feat_in, int64_t n_in, int32_t ci
       }
     } else if (split) PCC_TRY(make_planes(a, false, s));
     if (pair_h) {}
-    else if (split && g_gemm_persistent) PCC_TRY(launch_gemm_bf<MODE_CONV>(a, s));
     else if (bn == 128) { if (split) k_conv_mfma_bf<2, 2, 2, 2, MODE_CONV><<<grid, 256, 0, s>>>(a); else if (buf) k_conv_mfma<2, 2, 2, 2, MODE_CONV, true><<<grid, 256, 0, s>>>(a); else k_conv_mfma<2, 2, 2, 2, MODE_CONV, false><<<grid, 256, 0, s>>>(a); }
     else if (bn == 64) { if (split) k_conv_mfma_bf<2, 2, 2, 1, MODE_CONV><<<grid, 256, 0, s>>>(a); else if (buf) k_conv_mfma<2, 2, 2, 1, MODE_CONV, true><<<grid, 256, 0, s>>>(a); else k_conv_mfma<2, 2, 2, 1, MODE_CONV, false><<<grid, 256, 0, s>>>(a); }
     else { if (split) k_conv_mfma_bf<4, 1, 1, 1, MODE_CONV><<<grid, 256, 0, s>>>(a); else if (buf) k_conv_mfma<4, 1, 1, 1, MODE_CONV, true><<<grid, 256, 0, s>>>(a); else k_conv_mfma<4, 1, 1, 1, MODE_CONV, false><<<grid, 256, 0, s>>>(a); }
@@ -3535,7 +3302,6 @@ extern "C" int pcc_convt_fwd_rows(const float* feat_in, int64_t n_in, int32_t ci
       }
     } else if (split) PCC_TRY(make_planes(a, false, s));
     if (pair_h) {}
-    else if (split && g_gemm_persistent) PCC_TRY(launch_gemm_bf<MODE_CONV>(a, s));
     else if (bn == 128) { if (split) k_conv_mfma_bf<2, 2, 2, 2, MODE_CONV><<<grid, 256, 0, s>>>(a); else if (buf) k_conv_mfma<2, 2, 2, 2, MODE_CONV, true><<<grid, 256, 0, s>>>(a); else k_conv_mfma<2, 2, 2, 2, MODE_CONV, false><<<grid, 256, 0, s>>>(a); }
     else if (bn == 64) { if (split) k_conv_mfma_bf<2, 2, 2, 1, MODE_CONV><<<grid, 256, 0, s>>>(a); else if (buf) k_conv_mfma<2, 2, 2, 1, MODE_CONV, true><<<grid, 256, 0, s>>>(a); else k_conv_mfma<2, 2, 2, 1, MODE_CONV, false><<<grid, 256, 0, s>>>(a); }
     else { if (split) k_conv_mfma_bf<4, 1, 1, 1, MODE_CONV><<<grid, 256, 0, s>>>(a); else if (buf) k_conv_mfma<4, 1, 1, 1, MODE_CONV, true><<<grid, 256, 0, s>>>(a); else k_conv_mfma<4, 1, 1, 1, MODE_CONV, false><<<grid, 256, 0, s>>>(a); }
@@ -3975,217 +3741,8 @@ extern "C" int pcc_convt_fwd_csr_grid(const float* feat_in, int64_t n_in, int32_
                             nullptr, 27, ex_bias, &ex, (const long long*)out_keys, arith, d_guard, stream, wg_end);
 }
 
-// ---- chunked form of the CSR generative transposed convolution --------------------------------------------------------
-// The per-pair products T[n_in][K][cout] of a composite 7x7x7 level are 5 GB -- written by the GEMM, read once by the ordered
-// gather-sum.  Input rows are canonical (x-major), so a run of consecutive parents touches a contiguous run of children; the
-// path is therefore cut into parent chunks whose products fit the 256 MiB Infinity Cache: GEMM chunk c -> T (one staging
-// buffer, re-used by every chunk) -> gather-sum of the children chunk c reaches.  A child whose pair list straddles chunks
-// carries its partial sum in `out`; pair ids ascend with the parent row, so every child still adds its pairs in list order
-// and the result is bit-identical to the one-pass form.
-__global__ void __launch_bounds__(256) k_chunk_ranges(const long long* __restrict__ in_keys, long long n_in,
-                                                      const long long* __restrict__ out_keys, long long n_out,
-                                                      long long chunk_rows, int n_chunks, int ts_out, int4* ranges) {
-  auto lower = [&](long long q) {
-    long long lo = 0, hi = n_out;
-    while (lo < hi) {
-      const long long mid = (lo + hi) >> 1;
-      if (out_keys[mid] < q) lo = mid + 1; else hi = mid;
-    }
-    return (int)lo;
-  };
-  const long long reach = 3ll * ts_out;                                  // 7-wide kernel: children within +-3 output pitches
-  for (int c = threadIdx.x; c < n_chunks; c += blockDim.x) {
-    const long long r0 = (long long)c * chunk_rows;
-    const long long r1 = r0 + chunk_rows < n_in ? r0 + chunk_rows : n_in;
-    const long long k0 = in_keys[r0], k1 = in_keys[r1 - 1];
-    const long long x0 = (k0 >> 32) & 0xFFFF, x1 = ((k1 >> 32) & 0xFFFF) + reach + 1;
-    const long long lo_key = (k0 & 0x7FFF000000000000ll) | ((x0 > reach ? x0 - reach : 0ll) << 32);
-    const long long hi_key = (k1 & 0x7FFF000000000000ll) + (x1 << 32);  // + : a carry out of the x field moves on to the next batch
-    ranges[c] = make_int4(lower(lo_key), c == n_chunks - 1 ? (int)n_out : lower(hi_key), 0, 0);
-  }
-  __syncthreads();
-  for (int c = threadIdx.x; c < n_chunks; c += blockDim.x) {
-    const int prev_hi = c ? ranges[c - 1].y : 0;                          // rows below: owned (if their list is empty) by an earlier chunk
-    ranges[c].z = prev_hi;
-    if (prev_hi < ranges[c].x) ranges[c].x = prev_hi;
-  }
-}
-
-template <int VEC>
-__global__ void __launch_bounds__(256) k_convt_gather_csr_chunk(GatherCsrArgs a, const int4* __restrict__ range, int pid_lo,
-                                                                int pid_hi) {
-  typedef typename ThinVec<VEC>::T VT;
-  constexpr int JB = 8;
-  const int4 rg = *range;
-  const int lane = threadIdx.x & 63;
-  const int lpr = 1 << a.lpr_log2;
-  const int rpw = 64 >> a.lpr_log2;
-  const int cl = lane & (lpr - 1);
-  const int cvec = a.cout / VEC;
-  const long long per_block = 4ll * rpw;
-  for (long long base = rg.x + (long long)blockIdx.x * per_block; base < rg.y; base += (long long)gridDim.x * per_block) {
-    const long long o = base + (long long)(threadIdx.x >> 6) * rpw + (lane >> a.lpr_log2);
-    if (o >= rg.y) continue;
-    const int t0 = a.first[o], t1 = a.first[o + 1];
-    bool has_earlier = false, is_last = true;
-    if (t0 == t1) {
-      if (o < rg.z) continue;                                             // empty list: finished by the chunk that owns the row
-    } else {
-      const int first_pid = a.pair_ids[t0], last_pid = a.pair_ids[t1 - 1];
-      if (last_pid < pid_lo || first_pid >= pid_hi) continue;             // finished earlier / starts later
-      has_earlier = first_pid < pid_lo;
-      is_last = last_pid < pid_hi;
-    }
-    unsigned long long present = 0;
-    if (is_last && a.ex_grid.bits) {                                      // (uniform over the row's lane group)
-      unsigned m = pcc_grid_nbr27(a.ex_grid, a.out_keys[o], cl, lpr < 9 ? lpr : 9, nullptr);
-      for (int d = lpr >> 1; d >= 1; d >>= 1) m |= __shfl_xor((int)m, d, lpr);
-      present = m;
-    }
-    for (int cv = cl; cv < cvec; cv += lpr) {
-      VT acc;
-      thin_zero(acc);
-      if (has_earlier) acc = reinterpret_cast<const VT*>(a.out + o * a.cout)[cv];
-      for (int t = t0; t < t1; t += JB) {
-        int pid[JB];
-#pragma unroll
-        for (int u = 0; u < JB; ++u) {
-          const int p = (t + u < t1) ? a.pair_ids[t + u] : -1;
-          pid[u] = (p >= pid_lo && p < pid_hi) ? p - pid_lo : -1;
-        }
-        VT x[JB];
-#pragma unroll
-        for (int u = 0; u < JB; ++u) {
-          thin_zero(x[u]);
-          if (pid[u] >= 0) x[u] = reinterpret_cast<const VT*>(a.T + (long long)pid[u] * a.cout)[cv];
-        }
-#pragma unroll
-        for (int u = 0; u < JB; ++u) thin_acc(acc, x[u]);     // fixed order: pair id ascending, continued from the stored partial
-      }
-      if (is_last) {
-        if (a.ex_tab) {
-          const VT* tb = reinterpret_cast<const VT*>(a.ex_tab);
-          const unsigned m = (unsigned)present;
-          thin_acc(acc, tb[(m & 127u) * cvec + cv]);
-          thin_acc(acc, tb[(128u + ((m >> 7) & 127u)) * cvec + cv]);
-          thin_acc(acc, tb[(256u + ((m >> 14) & 127u)) * cvec + cv]);
-          thin_acc(acc, tb[(384u + ((m >> 21) & 63u)) * cvec + cv]);
-        }
-        VT b;
-        thin_zero(b);
-        if (a.bias) b = reinterpret_cast<const VT*>(a.bias)[cv];
-        thin_acc(acc, b);
-        thin_act(acc, a.act, a.slope);
-      }
-      reinterpret_cast<VT*>(a.out + o * a.cout)[cv] = acc;
-    }
-  }
-}
-
-static long long g_chunk_bytes = getenv("PCC_T_CHUNK_MIB") ? atoll(getenv("PCC_T_CHUNK_MIB")) << 20 : 96ll << 20;
-extern "C" int pcc_set_t_chunk_bytes(int64_t bytes) { g_chunk_bytes = bytes; return PCC_OK; }
-
-static long long chunk_rows_for(int64_t n_in, int32_t K, int32_t cout) {
-  long long rows = g_chunk_bytes / ((long long)K * cout * 4) / 1024 * 1024;      // whole groups of 8 row tiles of 128
-  if (rows < 1024) rows = 1024;
-  return rows < n_in ? rows : (n_in + 1023) / 1024 * 1024;
-}
-
-extern "C" size_t pcc_convt_chunk_t_bytes(int64_t n_in, int32_t K, int32_t cout) {
-  return n_in <= 0 ? 256 : pcc_align_up((size_t)chunk_rows_for(n_in, K, cout) * K * cout * 4);
-}
-extern "C" size_t pcc_convt_chunk_ws_bytes(int64_t n_in, int32_t K, int32_t cout) {
-  return n_in <= 0 ? 256 : pcc_align_up((size_t)pcc_cdiv(n_in, chunk_rows_for(n_in, K, cout)) * sizeof(int4));
-}
-
-extern "C" int pcc_convt_fwd_csr_chunked(const float* feat_in, int64_t n_in, int32_t cin, const float* packed_w,
-                                         const float* bias, int32_t K, int32_t cout, const int32_t* first,
-                                         const int32_t* pair_ids, int64_t n_out, const int64_t* in_keys,
-                                         const int64_t* out_keys, int32_t ts_out, float* T, size_t t_bytes, float* out,
-                                         int32_t act, float slope, const uint64_t* out_bits, const int32_t* out_rank,
-                                         const int32_t* h_out, const float* ex_bias, void* ws, size_t ws_bytes, int32_t arith,
-                                         int32_t* d_guard, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (n_out <= 0 || n_in <= 0) return PCC_OK;
-  PCC_REQUIRE(feat_in && packed_w && first && pair_ids && in_keys && out_keys && T && out && ws,
-              "pcc_convt_fwd_csr_chunked: NULL array");
-  PCC_REQUIRE(K == 343, "pcc_convt_fwd_csr_chunked: 7x7x7 kernels only (K=%d)", K);
-  PCC_REQUIRE(mfma_ok(cin, K * cout), "pcc_convt_fwd_csr_chunked: unsupported shape cin=%d cout=%d", cin, cout);
-  PCC_REQUIRE(act >= 0 && act <= 2, "pcc_convt_fwd_csr_chunked: bad activation");
-  PCC_REQUIRE(n_in * K < (1ll << 31) && n_out < (1ll << 31), "pcc_convt_fwd_csr_chunked: too many rows");
-  PCC_REQUIRE(ts_out >= 1 && ts_out <= 16, "pcc_convt_fwd_csr_chunked: output pitch %d", ts_out);
-  PCC_REQUIRE(!ex_bias || (out_bits && out_rank && h_out), "pcc_convt_fwd_csr_chunked: ex_bias needs the output set's grid index");
-  const long long chunk_rows = chunk_rows_for(n_in, K, cout);
-  const int n_chunks = (int)pcc_cdiv(n_in, chunk_rows);
-  PCC_REQUIRE(t_bytes >= pcc_convt_chunk_t_bytes(n_in, K, cout) && ws_bytes >= pcc_convt_chunk_ws_bytes(n_in, K, cout),
-              "pcc_convt_fwd_csr_chunked: staging buffer or workspace too small");
-  int4* ranges = (int4*)ws;
-  k_chunk_ranges<<<1, 256, 0, s>>>((const long long*)in_keys, n_in, (const long long*)out_keys, n_out, chunk_rows, n_chunks,
-                                   ts_out, ranges);
-  PCC_LAUNCH_CHECK();
-  ConvArgs a;
-  a.wp = packed_w; a.bias = nullptr; a.hdr = nullptr; a.nbr = nullptr; a.rows = nullptr; a.out = T;
-  a.cin = cin; a.cout = K * cout; a.cout_pad = cout_pad_for(K * cout);
-  a.wp_elems = (long long)cin * a.cout_pad;
-  a.cb_log2 = cb_log2_for(cin); a.ppo = cin >> a.cb_log2; a.act = 0; a.slope = 0.f;
-  a.feat = feat_in; a.n_in = n_in; a.n_out = n_in;
-  PCC_TRY(set_arith(a, arith, d_guard, "pcc_convt_fwd_csr_chunked"));
-  const bool split = split_ok(a);
-  // the form the one-pass call would take for all rows (so that both give the same bits)
-  const long long t128 = (pcc_cdiv(n_in, 128) + 7) / 8 * 8;
-  const bool use_h = split && a.arith == PCC_ARITH_H3 && convt_has_h(cin) && (a.ppo == 1 || a.ppo == 2 || a.ppo == 4 || a.ppo == 6 || a.ppo == 8) &&
-                     bn_for(a.cout) == 128 && t128 * (a.cout_pad / 128) >= 512;
-  const unsigned char* planes = nullptr;
-  const float* row_inv = nullptr;
-  if (use_h) {                                                           // planes of every input row, once
-    PCC_TRY(make_planes_h(a, s));
-    planes = a.feath; row_inv = a.frow_inv;
-    a.wh_ok = true;
-  } else if (split) {
-    PCC_TRY(make_planes(a, false, s));
-    planes = a.featb;
-  }
-  GatherCsrArgs g;
-  g.T = T; g.bias = bias; g.first = first; g.pair_ids = pair_ids; g.out = out; g.n_out = n_out; g.cout = cout;
-  g.act = act; g.slope = slope; g.ex_nbr = nullptr; g.ex_bias = ex_bias; g.ex_K = 27;
-  g.ex_grid.bits = nullptr; g.out_keys = nullptr;
-  g.ex_tab = nullptr;
-  if (ex_bias) {
-    g.ex_grid = grid_from_host(out_bits, out_rank, h_out); g.out_keys = (const long long*)out_keys;
-    PCC_TRY(presence_tables(ex_bias, cout, &g.ex_tab, s));
-  }
-  const int vec = (cout % 4 == 0) ? 4 : 1;
-  int l = 0;
-  while ((1 << l) < cout / vec && l < 6) ++l;
-  g.lpr_log2 = l;
-  int dev = 0, cus = 0;
-  PCC_CHECK_HIP(hipGetDevice(&dev));
-  PCC_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const unsigned ggrid = (unsigned)cus * 8;
-  for (int c = 0; c < n_chunks; ++c) {
-    const long long r0 = (long long)c * chunk_rows;
-    const long long rows = r0 + chunk_rows < n_in ? chunk_rows : n_in - r0;
-    a.feat = feat_in + r0 * cin; a.n_in = rows; a.n_out = rows;
-    if (use_h) { a.feath = planes + (size_t)r0 * cin * 4; a.frow_inv = row_inv + r0; }
-    else a.featb = planes ? planes + (size_t)r0 * cin * 6 : nullptr;
-    hipEvent_t e0, e1;
-    if (g_prof_on) PCC_TRY(prof_event(&e0, s));
-    PCC_TRY(launch_mfma<MODE_CONV>(a, 0, s));
-    if (g_prof_on) {
-      PCC_TRY(prof_event(&e1, s));
-      prof_push();
-    }
-    const int pid_lo = (int)(r0 * K), pid_hi = (int)((r0 + rows) * K);
-    if (vec == 4) k_convt_gather_csr_chunk<4><<<ggrid, 256, 0, s>>>(g, ranges + c, pid_lo, pid_hi);
-    else k_convt_gather_csr_chunk<1><<<ggrid, 256, 0, s>>>(g, ranges + c, pid_lo, pid_hi);
-    PCC_LAUNCH_CHECK();
-  }
-  return PCC_OK;
-}
-
 // 3x3x3 convolution to <= 4 channels on a full set, neighbours from the set's grid index (no kernel map):
 //   t[k*cout+co][i] = <feat[i], w_k[co]>  (k_thin_project),  out[o][co] = b + sum_k t[k*cout+co][nbr_k(o)]
-static bool g_thin_grid1 = getenv("PCC_THIN_GRID1") ? atoi(getenv("PCC_THIN_GRID1")) != 0 : true;
 struct ThinGridArgs {
   const float* t; const float* bias; const long long* keys; PccGrid g; float* out; long long n; int cout;
 };
@@ -4419,7 +3976,7 @@ __global__ void __launch_bounds__(256) k_thin_gather_grid1z(ThinGridArgs a) {
 //  0.55 + 0.60 for project + gather).  Moving 9 x 64 B per output through L1 costs more than writing 27 floats per row and
 //  gathering 27 x 4 B: the two-kernel form stays.)
 // one-channel heads over 16 hidden channels: rows from which the z-folded planes are used (negative: never)
-static long long g_thin_z_min_rows = getenv("PCC_THIN_Z_MIN_ROWS") ? atoll(getenv("PCC_THIN_Z_MIN_ROWS")) : (1ll << 20);
+static long long g_thin_z_min_rows = 1ll << 20;
 extern "C" int pcc_set_thin_z_min_rows(int64_t rows) { g_thin_z_min_rows = rows; return PCC_OK; }
 
 extern "C" size_t pcc_thin_grid_ws_bytes(int64_t n, int32_t cout) { return (size_t)27 * cout * (size_t)(n > 0 ? n : 1) * sizeof(float) + 256; }
@@ -4454,7 +4011,7 @@ extern "C" int pcc_conv_thin_grid_fwd(const float* feat, int64_t n, int32_t cin,
   }
   ThinGridArgs a;
   a.t = t; a.bias = bias; a.keys = (const long long*)keys; a.g = grid_from_host(bits, rank, h_grid); a.out = out; a.n = n; a.cout = cout;
-  if (cout == 1 && (size_t)27 * n * 4 <= (size_t)BUF_MAX_BYTES && g_thin_grid1) k_thin_gather_grid1<<<(unsigned)pcc_cdiv(n, 256), 256, 0, s>>>(a);
+  if (cout == 1 && (size_t)27 * n * 4 <= (size_t)BUF_MAX_BYTES) k_thin_gather_grid1<<<(unsigned)pcc_cdiv(n, 256), 256, 0, s>>>(a);
   else if (cout == 1) k_thin_gather_grid<1><<<(unsigned)pcc_cdiv(n, 256), 256, 0, s>>>(a);
   else k_thin_gather_grid<4><<<(unsigned)pcc_cdiv(n, 256), 256, 0, s>>>(a);
   PCC_LAUNCH_CHECK();
@@ -4526,8 +4083,7 @@ extern "C" int pcc_gdn_fwd(const float* x, int64_t n, int32_t c, const float* pa
   PCC_TRY(set_arith(a, arith, nullptr, "pcc_gdn_fwd"));
   // large sets: split folded into the staging (k_gdn_bf), no plane round trip; small ones keep the general kernel (its
   // smaller row tiles fill the chip better below ~30 k rows)
-  static const bool fused = getenv("PCC_GDN_FUSED") ? atoi(getenv("PCC_GDN_FUSED")) != 0 : true;
-  if (fused && split_ok(a) && c % 32 == 0 && (c & 3) == 0 && ((uintptr_t)x & 15) == 0 && n >= 32768) {
+  if (split_ok(a) && c % 32 == 0 && (c & 3) == 0 && ((uintptr_t)x & 15) == 0 && n >= 32768) {
     const int bn = bn_for(c);
     if (bn == 128) {
       const long long gy = a.cout_pad / 128;

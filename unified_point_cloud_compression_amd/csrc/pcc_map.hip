@@ -643,29 +643,22 @@ __global__ void __launch_bounds__(256) k_grid_rank_apply(const unsigned long lon
   }
 }
 
-static int g_grid_rank_fused = getenv("PCC_GRID_RANK_FUSED") ? atoi(getenv("PCC_GRID_RANK_FUSED")) : 1;   // 2: read-out inside the apply pass
-
 // rank[] of a marked bitmap and, with out_keys, the canonical keys of its set bits + their count.  ws: pcc_grid_ws_bytes(words).
 static int grid_rank(const unsigned long long* b, int64_t words, int32_t* rank, const int32_t* h, int tsl, int64_t* out_keys,
                      int64_t* d_count, void* ws, size_t ws_bytes, hipStream_t s) {
   const int64_t nb = pcc_cdiv(words, GR_B);
-  if (g_grid_rank_fused && nb <= GR_SELF_NB && (((uintptr_t)b | (uintptr_t)rank) & 15) == 0) {      // small lattice: one launch
+  if (nb <= GR_SELF_NB && (((uintptr_t)b | (uintptr_t)rank) & 15) == 0) {      // small lattice: one launch
     if (out_keys) k_grid_rank_apply<true, true><<<(unsigned)nb, 256, 0, s>>>(b, words, nullptr, rank, h[0], h[1], h[2], h[3], h[4], h[5], tsl, out_keys, d_count);
     else k_grid_rank_apply<false, true><<<(unsigned)nb, 256, 0, s>>>(b, words, nullptr, rank, 0, 0, 0, 1, 1, 1, 0, nullptr, nullptr);
     PCC_LAUNCH_CHECK();
     return PCC_OK;
   }
-  if (g_grid_rank_fused && nb <= GR_DIRECT_NB && ws_bytes >= (size_t)nb * 4 + 256 && (((uintptr_t)b | (uintptr_t)rank) & 15) == 0) {
+  if (nb <= GR_DIRECT_NB && ws_bytes >= (size_t)nb * 4 + 256 && (((uintptr_t)b | (uintptr_t)rank) & 15) == 0) {
     int* sums = (int*)ws;
     k_grid_rank_reduce<<<(unsigned)nb, 256, 0, s>>>(b, words, sums);
     // (the read-out inside the apply pass -- k_grid_rank_apply<true>, 8 words per thread -- measured 2x slower than the
     //  word-per-thread read-out kernel: 0.61 against 0.27 ms per step; the rank passes alone save the popcount kernel and
     //  its 200 MB round trip on the large lattices)
-    if (out_keys && g_grid_rank_fused > 1) {
-      k_grid_rank_apply<true><<<(unsigned)nb, 256, 0, s>>>(b, words, sums, rank, h[0], h[1], h[2], h[3], h[4], h[5], tsl, out_keys, d_count);
-      PCC_LAUNCH_CHECK();
-      return PCC_OK;
-    }
     k_grid_rank_apply<false><<<(unsigned)nb, 256, 0, s>>>(b, words, sums, rank, 0, 0, 0, 1, 1, 1, 0, nullptr, nullptr);
     PCC_LAUNCH_CHECK();
     if (out_keys) {

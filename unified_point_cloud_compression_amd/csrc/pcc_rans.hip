@@ -920,10 +920,8 @@ extern "C" int pcc_rans_encode_streams(const int32_t* sym, const int32_t* idx, i
 }
 
 // Which LDS decoder runs (form 0 = automatic): wave per stream (2) while one round of workgroups of at most 16 waves covers
-// all streams, lane per stream (1) above that.  Measured on MI355X, profiles/rans_wave_decode_crossover.txt.  env
-// PCC_RANS_FORM (read once) sets the form pcc_rans_decode_streams asks for.
+// all streams, lane per stream (1) above that.  Measured on MI355X, profiles/rans_wave_decode_crossover.txt.
 static constexpr int RANS_WAVES_PER_CU = 16;
-static int g_rans_form = getenv("PCC_RANS_FORM") ? atoi(getenv("PCC_RANS_FORM")) : 0;
 
 extern "C" int pcc_rans_decode_streams_form(const uint8_t* data, int64_t nbytes, const int32_t* idx, int64_t n,
                                             int32_t channels, int32_t n_groups, int32_t n_segments,
@@ -994,6 +992,5 @@ extern "C" int pcc_rans_decode_streams(const uint8_t* data, int64_t nbytes, cons
                                        const int32_t* offsets, const void* dec_table, int64_t dec_bytes, int32_t* sym_out,
                                        int32_t* d_status, void* stream) {
   return pcc_rans_decode_streams_form(data, nbytes, idx, n, channels, n_groups, n_segments, cdf, cdf_stride, sizes, offsets,
-                                      dec_table, dec_bytes, sym_out, d_status, stream,
-                                      g_rans_form >= 0 && g_rans_form <= 2 ? g_rans_form : 0);
+                                      dec_table, dec_bytes, sym_out, d_status, stream, 0);
 }

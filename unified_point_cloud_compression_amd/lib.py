@@ -105,11 +105,6 @@ SIGNATURES = {
                                    _p, _i32, _p, _sz, _p]),
     "pcc_convt_scatter_rows": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p]),
     "pcc_convt_fwd_csr_grid": (C.c_int, [_p, _i64, _i32, _p, _p, _i32, _i32, _p, _p, _i64, _p, _p, _i32, _f32, _p, _p, _p, C.POINTER(_i32), _p, _p, _i32, _p, _p]),
-    "pcc_set_t_chunk_bytes": (C.c_int, [_i64]),
-    "pcc_convt_chunk_t_bytes": (_sz, [_i64, _i32, _i32]),
-    "pcc_convt_chunk_ws_bytes": (_sz, [_i64, _i32, _i32]),
-    "pcc_convt_fwd_csr_chunked": (C.c_int, [_p, _i64, _i32, _p, _p, _i32, _i32, _p, _p, _i64, _p, _p, _i32, _p, _sz, _p, _i32, _f32,
-                                            _p, _p, C.POINTER(_i32), _p, _p, _sz, _i32, _p, _p]),
     "pcc_thin_grid_ws_bytes": (_sz, [_i64, _i32]),
     "pcc_conv_thin_grid_fwd": (C.c_int, [_p, _i64, _i32, _p, _p, _i32, _p, _p, _p, C.POINTER(_i32), _p, _p, _sz, _p]),
     "pcc_gauss_lik_fwd": (C.c_int, [_p, _p, _p, _i64, _p, _p]),
@@ -249,49 +244,36 @@ def workspace(nbytes, device):
     return buf
 
 
-# ---- zero-copy counters --------------------------------------------------------------------------------------
+# ---- device counters -----------------------------------------------------------------------------------------
 # Sizes the host needs next (rows of a derived coordinate set, a canonical-order flag, bytes of a bitstream) are written
-# by the kernels straight into pinned host memory (device-visible at the same address under HIP's unified addressing):
-# the host zeroes the slot, launches, synchronises the stream and reads -- no device allocation, no fill kernel and no
-# device->host copy launch per read (round 1: ~40 `.item()` reads per step, 25-50 us of idle GPU each).
-_pin = {"buf": None, "next": 0, "dev_blocks": {}}
-_PIN_SLOTS, _PIN_WORDS = 1024, 4
-PINNED_COUNTERS = os.environ.get("PCC_PINNED_COUNTERS", "0") != "0"   # measured 0.3 ms/step slower than `.item()` reads (round 2): off
+# by the kernels into small device tensors cut from one zeroed block per device (one fill per 1024 counters instead of one
+# per counter) and read back with a copy; read_many() fetches several of them with one copy.
+_counter_blocks = {}
+_COUNTER_WORDS = 4
 
 
 def counter(n=1, dtype=torch.int64):
-    """Zeroed pinned host tensor of `n` (<= 4) int64 (or 2n int32) words for a kernel to write into."""
-    if not PINNED_COUNTERS:           # default: device counters cut from a zeroed block (one fill per 1024 counters instead of
-        d = torch.cuda.current_device()          # one per counter), read back with a copy; one block per device
-        st = _pin["dev_blocks"].setdefault(d, {"blk": None, "next": 0})
-        blk = st["blk"]
-        if blk is None or st["next"] + _PIN_WORDS > blk.numel():
-            blk = st["blk"] = torch.zeros(1024 * _PIN_WORDS, dtype=torch.int64, device=torch.device("cuda", d))
-            st["next"] = 0
-        t = blk[st["next"]:st["next"] + _PIN_WORDS]
-        st["next"] += _PIN_WORDS
-        return (t if dtype == torch.int64 else t.view(dtype))[:n]
-    if _pin["buf"] is None:
-        _pin["buf"] = torch.zeros((_PIN_SLOTS, _PIN_WORDS), dtype=torch.int64).pin_memory()
-    slot = _pin["buf"][_pin["next"]]
-    _pin["next"] = (_pin["next"] + 1) % _PIN_SLOTS
-    slot.zero_()
-    t = slot if dtype == torch.int64 else slot.view(dtype)
-    return t[:n]
+    """Zeroed device tensor of `n` (<= 4) int64 (or 2n int32) words for a kernel to write into."""
+    d = torch.cuda.current_device()
+    st = _counter_blocks.setdefault(d, {"blk": None, "next": 0})
+    blk = st["blk"]
+    if blk is None or st["next"] + _COUNTER_WORDS > blk.numel():
+        blk = st["blk"] = torch.zeros(1024 * _COUNTER_WORDS, dtype=torch.int64, device=torch.device("cuda", d))
+        st["next"] = 0
+    t = blk[st["next"]:st["next"] + _COUNTER_WORDS]
+    st["next"] += _COUNTER_WORDS
+    return (t if dtype == torch.int64 else t.view(dtype))[:n]
 
 
 def cptr(t):
-    """Pointer of a pinned counter as a kernel argument."""
-    if not (t.is_pinned() or t.is_cuda):
+    """Pointer of a counter as a kernel argument."""
+    if not t.is_cuda:
         raise PccError("counter() tensors only")
     return t.data_ptr()
 
 
 def read(t):
-    """Values of a counter once the kernels that write it have finished."""
-    if t.is_cuda:
-        return t.tolist()
-    torch.cuda.current_stream().synchronize()
+    """Values of a counter once the kernels that write it have finished (the copy waits for them)."""
     return t.tolist()
 
 

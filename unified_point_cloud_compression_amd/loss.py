@@ -6,14 +6,13 @@
 float-scaled weights and torch.isin).
 """
 import math
-import os
 
 import torch
 
 from . import lib as L
 from . import sparse as S
 
-FUSED_FOCAL = os.environ.get("PCC_FUSED_FOCAL", "1") != "0"      # focal loss rows as one kernel per level (training step)
+FUSED_FOCAL = True    # focal loss rows as one kernel per level (training step)
 
 
 def _lookup_rows32(cset, query_keys, nq):

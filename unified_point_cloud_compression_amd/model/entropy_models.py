@@ -14,7 +14,6 @@ The entropy-coder boundary carries rANS byte strings (`strings = [[y_string], [z
 coder is the per-channel GPU rANS of libpcc_hip by default (`entropy_coder="ans"`: single host stream in CompressAI's
 byte layout; `"symbols"`: hand the int32 symbol tensors across, for kernel-level measurements).
 """
-import os
 
 import torch
 import torch.nn as nn
@@ -220,7 +219,7 @@ class MeanScaleHyperprior(CompressionModel):
         """The hyper-latent's rANS encode (a serial recurrence per stream: 0.2 ms on a handful of CUs) started on the side stream
         as soon as its symbols exist, beside the hyper-synthesis and y's quantisation on the main stream.  Returns the job (with
         `.ready`, the event the main stream waits for before it touches the container), or None when nothing was started."""
-        if self.entropy_coder != "pcc_streams" or not self.SIDE_STREAM_DECODE:
+        if self.entropy_coder != "pcc_streams":
             return None
         zj = self.entropy_bottleneck.streams_job(z_sym)
         if zj.adaptive:                                   # its stream count needs a host read first: coded in `_code_streams`
@@ -280,14 +279,12 @@ class MeanScaleHyperprior(CompressionModel):
         _, _, y_lik = self.gaussian_conditional.encode_rows(y._canonical_features(), params, y._cset.keys, scale)
         return y_lik, z_lik
 
-    SIDE_STREAM_DECODE = os.environ.get("PCC_SIDE_DECODE", "1") != "0"
-
     def predecode(self, symbols, shape, device, check=None):
         """What depends on the strings alone, started before the decoder's coordinate work and beside it: the hyper-latent's
         rANS decode (a serial recurrence per stream on a handful of CUs: 0.4 ms during which the main stream builds y's and
         z's coordinate sets, the first level's maps and candidate set) and the upload of y's string, on the side stream.
         Returns a token for `decompress(pre=...)`, or None when the coder is not the GPU one."""
-        if self.entropy_coder != "pcc_streams" or not self.SIDE_STREAM_DECODE or int(shape[0]) <= 0:
+        if self.entropy_coder != "pcc_streams" or int(shape[0]) <= 0:
             return None
         (y_string,), (z_string,) = symbols
         eb = self.entropy_bottleneck

@@ -12,7 +12,6 @@ Module structure, attribute names and Sequential indices equal the reference's (
     all ~40 candidates per parent with the 128-channel up-sampled features; the up-sampled features themselves are then
     computed only for the rows the top-k keeps (`SparseSynthesisTransform.FUSE_UP_PREDICT`).
 """
-import os
 
 import torch
 import torch.nn as nn
@@ -32,7 +31,7 @@ def batch_segments(cset):
 def batch_segments_begin(cs):
     """Queue the batch ranges of a set whose size the host knows (`pcc_batch_bounds`); returns a Pending for `S.resolve` (the
     caller reads it together with whatever else it waits for), or None when there is nothing to read."""
-    if cs.bounds.bmax == 0 or "segments" in cs._derived or cs.bounds.bmax > 10 or cs.n == 0 or not S.BATCH_BOUNDS:
+    if cs.bounds.bmax == 0 or "segments" in cs._derived or cs.bounds.bmax > 10 or cs.n == 0:
         return None
     entries = cs.bounds.bmax + 2
     a, b, c = L.counter(4), L.counter(4), L.counter(4)
@@ -215,13 +214,13 @@ class SparseSynthesisTransform(nn.Module):
     FUSE_UP_PREDICT = True
     # all three heads are fused since round 2 (round 1 left predict_3, 32 -> 16, layer-wise: with the fp32 GEMM its per-pair
     # buffer and the 7-wide probing cost what the narrower convolution saved; with the split-path GEMM it is 0.9 ms ahead)
-    FUSE_MIN_HEAD_CHANNELS = int(os.environ.get("PCC_FUSE_MIN_HEAD", "16"))
+    FUSE_MIN_HEAD_CHANNELS = 16
 
     def _fused_weights(self, gen, c0):
         """(packed composite kernel [343, Cin, Ch], neighbour-existence bias [27, Ch]) of head_conv0(genT(.)), cached per
         parameter version.  Offsets: genT writes parent + off_k, the head reads row + off_j, so parent -> row
         displacement is off_k - off_j, index (ix - jx + 2) per axis in the 7-wide composite."""
-        tag = tuple((p.data_ptr(), p._version) for p in (gen.kernel, gen.bias, c0.kernel)) + (S.WEIGHT_OFFSET_ORDER, S.T_Z_FASTEST)
+        tag = tuple((p.data_ptr(), p._version) for p in (gen.kernel, gen.bias, c0.kernel)) + (S.WEIGHT_OFFSET_ORDER,)
         cache = self.__dict__.setdefault("_fused_cache", {})
         hit = cache.get(id(gen))
         if hit is None or hit[0] != tag:
@@ -237,8 +236,7 @@ class SparseSynthesisTransform(nn.Module):
                     for jy in range(3):
                         for jx in range(3):
                             M[2 - jz:7 - jz, 2 - jy:7 - jy, 2 - jx:7 - jx] += W5 @ V3[jz, jy, jx]
-                if S.T_Z_FASTEST:                                    # offsets numbered z fastest, to match csr_for(zk=True)
-                    M = M.permute(2, 1, 0, 3, 4).contiguous()
+                M = M.permute(2, 1, 0, 3, 4).contiguous()            # offsets numbered z fastest, to match csr_for(zk=True)
                 Mf = torch.nn.Parameter(M.view(343, cin, ch).float(), requires_grad=False)
                 packed = S.PackedConv(transposed=True).get(Mf)
                 cb = (gen.bias.detach().double().reshape(1, cm) @ V.reshape(27 * cm, ch).view(27, cm, ch)).reshape(27, ch)
@@ -291,21 +289,16 @@ class SparseSynthesisTransform(nn.Module):
         feats = x._canonical_features()
         out_set = cs_in.expand(5, ts_out, want_csr=False)
         packedM, cb = self._fused_weights(gen, c0)
-        from_grid = (S.STENCIL_FROM_GRID and out_set.grid() is not None and c2.kernel_size == 3 and c2.stride == 1
+        from_grid = (out_set.grid() is not None and c2.kernel_size == 3 and c2.stride == 1
                      and c2.out_channels <= 4 and c0.out_channels in (4, 8, 16, 32, 64)
                      and 27 * c2.out_channels * c0.out_channels * 4 <= 48 * 1024)
-        chunked = S.T_CHUNKED and cs_in.n * 343 * c0.out_channels * 4 >= S.T_CHUNKED_MIN_BYTES
         # (the one-pass slotted lists are consumed by the grid form of the gather-sum only)
-        csr7 = cs_in.csr_for(out_set.keys, out_set.n, 7, ts_out, zk=S.T_Z_FASTEST, slots=S.CSR_SLOTS and from_grid and not chunked)
+        csr7 = cs_in.csr_for(out_set.keys, out_set.n, 7, ts_out, zk=True, slots=from_grid)
         if from_grid:
             # the candidate set's own bitmap + rank give the 27 neighbours of a row directly: no 3x3x3 kernel map of the
             # (large) candidate set is built, written and re-read for the presence flags and for the 1-channel convolution
-            if chunked:
-                h = S.convt_forward_csr_chunked(feats, packedM, c0.bias, 343, gen.in_channels, c0.out_channels, csr7, cs_in,
-                                                out_set, L.ACT_RELU, cb)
-            else:
-                h = S.convt_forward_csr_grid(feats, packedM, c0.bias, 343, gen.in_channels, c0.out_channels, csr7, out_set,
-                                             L.ACT_RELU, cb)
+            h = S.convt_forward_csr_grid(feats, packedM, c0.bias, 343, gen.in_channels, c0.out_channels, csr7, out_set,
+                                         L.ACT_RELU, cb)
             w2 = c2._packed.get(c2.kernel, state_dict_order=True)
             logit = S.conv_thin_grid_forward(h, w2, c2.bias, c0.out_channels, c2.out_channels, out_set)
         else:

@@ -8,7 +8,6 @@ coordinate manager.
 import ctypes as C
 
 import itertools
-import os
 import weakref
 
 import torch
@@ -116,18 +115,10 @@ EXPAND_BY_GRID = True  # generative expansion through the bitmaps (False: 32-bit
 STRIDE_BY_GRID = True  # strided sets read out of the coarse occupancy bitmap (False: mask + radix sort + unique)
 USE_GRID = True       # neighbour lookup through the bitmap+rank grid index (False: binary search; tests run both)
 GRID_MAX_BYTES = 8 << 30
-BAND_TILES = os.environ.get("PCC_BAND_TILES", "1") != "0"      # stencil kernels over large sets visit their tiles band by band (L2 locality of the dx = +-1 slabs)
+BAND_TILES = True     # stencil kernels over large sets visit their tiles band by band (L2 locality of the dx = +-1 slabs)
 BAND_MIN_ROWS = 1 << 20
 BAND_COUNT = 16
-T_Z_FASTEST = os.environ.get("PCC_T_Z_FASTEST", "1") != "0"        # composite levels: products laid out [row][kx][ky][kz][c]
-T_CHUNKED = os.environ.get("PCC_T_CHUNKED", "0") != "0"            # composite levels: per-pair products staged in cache-sized chunks
-#   (measured round 2: bit-identical, 10 GB less memory, but +3.5 ms per step -- 125 chunk pairs of launches, children near
-#   chunk borders visited twice, and the Infinity Cache does not speed the gather up enough to pay for it: off)
-T_CHUNKED_MIN_BYTES = 256 << 20
-BATCH_BOUNDS = os.environ.get("PCC_BATCH_BOUNDS", "1") != "0"   # batched sets: per-batch row ranges of an expanded set read with its size
-CSR_SLOTS = os.environ.get("PCC_CSR_SLOTS", "1") != "0"      # composite levels: 7-wide pair lists in one pass (per-workgroup slots)
-STENCIL_FROM_GRID = os.environ.get("PCC_STENCIL_FROM_GRID", "1") != "0"   # composite levels: 3x3x3 neighbours from the bitmap, no nbr table
-HEAD_FUSED = os.environ.get("PCC_HEAD_FUSED", "1") != "0"      # occupancy heads with <= 16 hidden channels: conv + ReLU + projection in one kernel
+HEAD_FUSED = True     # occupancy heads with <= 16 hidden channels: conv + ReLU + projection in one kernel
 
 
 _SET_SERIAL = itertools.count()
@@ -399,7 +390,7 @@ class CoordSet:
         L.call("pcc_coords_expand_grid", L.ptr(self.keys), self.n, ksize, h, L.ptr(bits), L.ptr(rank), L.ptr(out),
                L.cptr(cnt), L.ptr(ws), ws.numel(), L.stream())
         # batched sets: the per-batch row ranges of the new set (top-k runs per batch) come back with its size
-        entries = ob.bmax + 2 if (BATCH_BOUNDS and 0 < ob.bmax <= 10) else 0
+        entries = ob.bmax + 2 if 0 < ob.bmax <= 10 else 0
         if entries:
             seg_a, seg_b, seg_c = L.counter(4), L.counter(4), L.counter(4)
             L.call("pcc_batch_bounds", L.ptr(out), L.cptr(cnt), 0, entries, L.cptr(seg_a), L.cptr(seg_b), L.cptr(seg_c), L.stream())
@@ -823,30 +814,6 @@ def convt_forward_csr_grid(feats, packed_w, bias, K, cin, cout, csr, out_set, ac
     L.call("pcc_convt_fwd_csr_grid", L.ptr(feats), n_in, cin, L.ptr(packed_w), L.ptr(b), K, cout, L.ptr(first), L.ptr(pair_ids),
            n_out, L.ptr(T), L.ptr(out), act, float(slope), L.ptr(out_set.keys), L.ptr(g[0]), L.ptr(g[1]), g[2],
            L.ptr(ex_bias.detach().to(torch.float32).contiguous()), L.ptr(wg_end), *L.arith_args(feats.device), L.stream())
-    return out
-
-
-def convt_forward_csr_chunked(feats, packed_w, bias, K, cin, cout, csr, in_set, out_set, act, ex_bias=None, slope=0.01):
-    """`convt_forward_csr` / `convt_forward_csr_grid` without the whole per-pair buffer: parent rows go through in chunks
-    whose products fit the Infinity Cache (staging buffer in the shared workspace), partial sums carried in the output."""
-    feats = feats.contiguous()
-    n_in, n_out = feats.shape[0], out_set.n
-    out = torch.empty((n_out, cout), dtype=torch.float32, device=feats.device)
-    if n_out == 0 or n_in == 0:
-        return out
-    first, pair_ids = csr
-    lib = L.load()
-    tb, wb = lib.pcc_convt_chunk_t_bytes(n_in, K, cout), lib.pcc_convt_chunk_ws_bytes(n_in, K, cout)
-    ws = L.workspace(tb + wb, feats.device)
-    g = out_set.grid() if ex_bias is not None else None
-    if ex_bias is not None and g is None:
-        raise L.PccError("convt_forward_csr_chunked: ex_bias needs the grid index of the output set")
-    b = bias.detach().reshape(-1).contiguous() if bias is not None else None
-    eb = ex_bias.detach().to(torch.float32).contiguous() if ex_bias is not None else None
-    L.call("pcc_convt_fwd_csr_chunked", L.ptr(feats), n_in, cin, L.ptr(packed_w), L.ptr(b), K, cout, L.ptr(first), L.ptr(pair_ids),
-           n_out, L.ptr(in_set.keys), L.ptr(out_set.keys), out_set.ts, ws.data_ptr() + wb, tb, L.ptr(out), act, float(slope),
-           L.ptr(g[0]) if g else None, L.ptr(g[1]) if g else None, g[2] if g else None, L.ptr(eb), ws.data_ptr(), wb,
-           *L.arith_args(feats.device), L.stream())
     return out
 
 
