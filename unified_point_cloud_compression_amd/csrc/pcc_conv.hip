@@ -14,11 +14,11 @@
 //
 // Thin outputs (Cout <= 4: occupancy logits, colours, model/transforms.py:141-160) are gather-bound;
 // they use a VALU kernel with lanes spread over the input channels of a row.
+#include <type_traits>
 #include <vector>
 
 #include "pcc_common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "pcc_mfma.h"
 
 static constexpr int LDS_LD = 36;   // floats per LDS tile row: 32 + 4 pad
 static constexpr int MAXK = 128;    // kernel offsets per segment (K <= 125)
@@ -68,12 +68,6 @@ struct ConvArgs {
 
 __host__ __device__ inline int bn_for(int cout) { return cout >= 128 ? 128 : (cout > 32 ? 64 : 32); }
 
-// BUF: feature rows and weight rows are fetched with buffer loads whose offset is out of range for an absent neighbour
-// (reads 0, no memory access): no per-row branch, no zero fill, 32-bit address arithmetic and a fixed number of loads
-// in flight, so the s_waitcnt distances the compiler derives are exact.  Needs feat and wp below 4 GB each.
-static constexpr unsigned BUF_OOB = 0xFFFF0000u;
-static constexpr long long BUF_MAX_BYTES = 0xFFFE0000ll;
-
 template <int WM, int WN, int TM, int TN, int MODE, bool BUF>
 __global__ void __launch_bounds__(256) k_conv_mfma(ConvArgs a) {
   constexpr int BM = WM * TM * 32;
@@ -88,13 +82,7 @@ __global__ void __launch_bounds__(256) k_conv_mfma(ConvArgs a) {
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
 
-  // ---- XCD-aware work mapping --------------------------------------------------------------------
-  // Workgroups are dealt round-robin over the 8 XCDs (private L2 each).  Neighbouring tiles gather almost the same
-  // input rows, so XCD x is given a CONTIGUOUS range of work ids: its L2 then serves the re-reads that otherwise go
-  // to the fabric 8 times (measured with rocprofv3 FETCH_SIZE: 12-25x the compulsory bytes without this).  The
-  // column blocks of one row tile are adjacent ids (same gathered rows).  Speed only, never correctness.
-  const int cpx = gridDim.x >> 3;                         // grid is a multiple of 8
-  const int wid = (blockIdx.x & 7) * cpx + (blockIdx.x >> 3);
+  const int wid = xcd_work_id();
   const int gy = a.cout_pad / BN;
   int tile_id = wid / gy;
   int colblock = (wid - tile_id * gy) * BN;
@@ -198,9 +186,7 @@ __global__ void __launch_bounds__(256) k_conv_mfma(ConvArgs a) {
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    for (int j = 0; j < TN; ++j) acc[i][j] = acc_zero();
 
   const int wm = w / WN, wn = w % WN;
   const int half = lane >> 5, r31 = lane & 31;
@@ -356,7 +342,7 @@ __global__ void __launch_bounds__(256) k_conv_mfma(ConvArgs a) {
         for (int i = 0; i < TM; ++i)
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
-            const size_t o = (size_t)(i * 32 + (e & 3) + 8 * (e >> 2)) * a.cout + j * 32;
+            const size_t o = (size_t)cfrag_row(i * 32, e, 0) * a.cout + j * 32;
             lane_out[o] = actf(acc[i][j][e] + b, o);
           }
       }
@@ -377,7 +363,7 @@ __global__ void __launch_bounds__(256) k_conv_mfma(ConvArgs a) {
     for (int i = 0; i < TM; ++i) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int r = (wm * TM + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
+        const int r = cfrag_row((wm * TM + i) * 32, e, half);
         if (r >= npos) continue;
         const long long orow = a.rows ? a.rows[pos0 + r] : (pos0 + r);
         float v = acc[i][j][e] + b;
@@ -412,21 +398,6 @@ __global__ void __launch_bounds__(256) k_conv_mfma(ConvArgs a) {
 // showed 5.4 VALU instructions per MFMA and the SIMD issue-bound at 33 % MFMA utilisation; and for the shallow
 // generative GEMMs every column block repeated the split of the same rows.)
 // ------------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-
-__host__ __device__ inline long long bf_plane_elems(long long fp32_elems) { return fp32_elems / 2 * 3; }   // floats holding 3 bf16 planes
-
-__device__ __forceinline__ void bf_split2(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-  const f32x2v v = {x0, x1};
-  h = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2v));
-  const f32x2v r1 = {x0 - __builtin_bit_cast(float, h << 16), x1 - __builtin_bit_cast(float, h & 0xFFFF0000u)};
-  m = __builtin_bit_cast(unsigned, __builtin_convertvector(r1, bf16x2v));
-  const f32x2v r2 = {r1.x - __builtin_bit_cast(float, m << 16), r1.y - __builtin_bit_cast(float, m & 0xFFFF0000u)};
-  l = __builtin_bit_cast(unsigned, __builtin_convertvector(r2, bf16x2v));
-}
-
 // fp32 packed image [rows][32] -> bf16 planes [rows][3][32]
 __global__ void k_split_packed(const float* __restrict__ src, long long pairs, unsigned* __restrict__ dst) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;      // one pair of consecutive channels
@@ -464,9 +435,6 @@ __global__ void k_feat_split(const float* __restrict__ x, long long pairs, int c
 // product (one input row per output row) but not out of a gathered convolution, which is why only the dense products take
 // this form.  The kernels are bound by energy, not by issue slots: the chip holds ~1.3 GHz on them (GRBM_GUI_ACTIVE / 8 /
 // wall), and every phase's cost adds up whether or not it overlaps, so fewer MFMAs is what pays.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ float pow2_scale_exp(float mx, int& e) {      // s = 2^(14 - e), e = floor(log2 mx) (0 for mx = 0)
   e = mx > 0.f ? ilogbf(mx) : 0;
   e = e < -100 ? -100 : (e > 120 ? 120 : e);
@@ -643,8 +611,7 @@ __global__ void __launch_bounds__(256, MINWG) k_conv_mfma_bf(ConvArgs a) {
   __shared__ int s_nact;
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int cpx = gridDim.x >> 3;
-  int wid = (blockIdx.x & 7) * cpx + (blockIdx.x >> 3);
+  int wid = xcd_work_id();
   const int ks_id = wid % a.ksplit;                   // which slice of the reduction (ksplit == 1: the whole of it)
   wid /= a.ksplit;
   const int gy = a.cout_pad / BN;
@@ -659,6 +626,8 @@ __global__ void __launch_bounds__(256, MINWG) k_conv_mfma_bf(ConvArgs a) {
     tile_id = g * 8 + (rem & 7);
   }
 
+  // locate (segment, tile) and compact the active offsets: the passage of k_conv_mfma, kept in step with it by hand (as one
+  // shared function, by reference or by value, it changed the instructions of every instantiation of both kernels)
   int pos0, npos, k_count, koff_begin;
   long long seg_pos_count;
   const int* seg_nbr = nullptr;
@@ -740,9 +709,9 @@ __global__ void __launch_bounds__(256, MINWG) k_conv_mfma_bf(ConvArgs a) {
   constexpr int NA = (BM * 12 + 255) / 256, NB = (BN * 12 + 255) / 256;
   int a_row[NA], a_w[NA], b_row[NB], b_w[NB];
 #pragma unroll
-  for (int j = 0; j < NA; ++j) { const int u = j * 256 + tid; a_row[j] = u / 12; a_w[j] = u - a_row[j] * 12; if (u >= BM * 12) a_row[j] = -1; }
+  for (int j = 0; j < NA; ++j) stage_role(j * 256 + tid, BM, a_row[j], a_w[j]);
 #pragma unroll
-  for (int j = 0; j < NB; ++j) { const int u = j * 256 + tid; b_row[j] = u / 12; b_w[j] = u - b_row[j] * 12; if (u >= BN * 12) b_row[j] = -1; }
+  for (int j = 0; j < NB; ++j) stage_role(j * 256 + tid, BN, b_row[j], b_w[j]);
 
   f32x16 acc[TM][TN];
 #pragma unroll
@@ -750,7 +719,7 @@ __global__ void __launch_bounds__(256, MINWG) k_conv_mfma_bf(ConvArgs a) {
 #pragma unroll
     for (int j = 0; j < TN; ++j)
 #pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;   // acc_zero() (pcc_mfma.h) written out: it costs the 128 x 128 tile 5 instructions
 
   const int wm = w / WN, wn = w % WN;
   const int half = lane >> 5, r31 = lane & 31;
@@ -839,18 +808,14 @@ __global__ void __launch_bounds__(256, MINWG) k_conv_mfma_bf(ConvArgs a) {
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) {           // smallest terms first
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[2][i], bf[0][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[2][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][i], bf[1][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][i], bf[0][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[1][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[0][j], acc[i][j], 0, 0, 0);
+          acc[i][j] = bf6_terms(af[0][i], af[1][i], af[2][i], bf[0][j], bf[1][j], bf[2][j], acc[i][j]);
         }
     }
   }
 
   if (PCC_DBG_ON(a, 1)) { if (acc[0][0][0] != 12345.678f) return; }
   if (a.ksplit > 1) {                                 // raw partial sums; bias / activation are applied by k_splitk_reduce
+    // (the indexing of the epilogue's general loop below)
     float* const part = a.part + (size_t)ks_id * (size_t)a.n_out * a.cout;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -860,7 +825,7 @@ __global__ void __launch_bounds__(256, MINWG) k_conv_mfma_bf(ConvArgs a) {
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-          const int r = (wm * TM + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
+          const int r = cfrag_row((wm * TM + i) * 32, e, half);
           if (r >= npos) continue;
           const long long orow = a.rows ? a.rows[pos0 + r] : (pos0 + r);
           part[orow * a.cout + col] = acc[i][j][e];
@@ -868,11 +833,8 @@ __global__ void __launch_bounds__(256, MINWG) k_conv_mfma_bf(ConvArgs a) {
     }
     return;
   }
-  // ---- epilogue: bias, activation (or GDN), store -------------------------------------------
-  // Full tiles written to consecutive rows take a branch-free path: one base pointer per lane, the activation chosen
-  // once per tile.  (The general loop below costs ~50 instructions per element -- row-list lookups, tail checks and
-  // the activation switch for each of the 64 values a lane holds -- which is as much as the whole MFMA phase of a
-  // 128-deep GEMM tile.)
+  // ---- epilogue: bias, activation (or GDN), store: the epilogue of k_conv_mfma, kept in step with it by hand (a shared function
+  //      over the accumulator array changed the instructions of both kernels, whatever the form of its other arguments)
   if (!a.rows && npos == BM) {
     const size_t lane_off = (size_t)(pos0 + wm * TM * 32 + 4 * half) * a.cout + colblock + wn * TN * 32 + r31;
     float* const lane_out = a.out + lane_off;
@@ -887,7 +849,7 @@ __global__ void __launch_bounds__(256, MINWG) k_conv_mfma_bf(ConvArgs a) {
         for (int i = 0; i < TM; ++i)
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
-            const size_t o = (size_t)(i * 32 + (e & 3) + 8 * (e >> 2)) * a.cout + j * 32;
+            const size_t o = (size_t)cfrag_row(i * 32, e, 0) * a.cout + j * 32;
             lane_out[o] = actf(acc[i][j][e] + b, o);
           }
       }
@@ -908,7 +870,7 @@ __global__ void __launch_bounds__(256, MINWG) k_conv_mfma_bf(ConvArgs a) {
     for (int i = 0; i < TM; ++i) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int r = (wm * TM + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
+        const int r = cfrag_row((wm * TM + i) * 32, e, half);
         if (r >= npos) continue;
         const long long orow = a.rows ? a.rows[pos0 + r] : (pos0 + r);
         float v = acc[i][j][e] + b;
@@ -923,6 +885,23 @@ __global__ void __launch_bounds__(256, MINWG) k_conv_mfma_bf(ConvArgs a) {
       }
     }
   }
+}
+
+// (row tile, first column) of work id `wid` in a dense product with gy column blocks of BN.  Many column blocks (weights > L2):
+// groups of 8 row tiles sweep the column blocks together, so a block's weights are fetched once per group instead of once
+// per row tile (the grid covers whole groups, launch_mfma).
+template <int BN>
+__device__ __forceinline__ int2 dense_tile(int wid, int gy) {   // .x = row tile, .y = first column
+  int tile_id, colblock;
+  if (gy > 8) {
+    const int g = wid / (8 * gy), rem = wid - g * 8 * gy;
+    colblock = (rem >> 3) * BN;
+    tile_id = g * 8 + (rem & 7);
+  } else {
+    tile_id = wid / gy;
+    colblock = (wid - tile_id * gy) * BN;
+  }
+  return make_int2(tile_id, colblock);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -942,18 +921,10 @@ __global__ void __launch_bounds__(256, 3) k_gemm_bf2(ConvArgs a) {
   __shared__ __attribute__((aligned(16))) uint4 As[BM * LDU];
   __shared__ __attribute__((aligned(16))) uint4 Bs[BN * LDU];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int cpx = gridDim.x >> 3;
-  const int wid = (blockIdx.x & 7) * cpx + (blockIdx.x >> 3);
+  const int wid = xcd_work_id();
   const int gy = a.cout_pad / BN;
-  int tile_id, colblock;
-  if (gy > 8) {                                         // groups of 8 row tiles sweep the column blocks together (weights > L2)
-    const int g = wid / (8 * gy), rem = wid - g * 8 * gy;
-    colblock = (rem >> 3) * BN;
-    tile_id = g * 8 + (rem & 7);
-  } else {
-    tile_id = wid / gy;
-    colblock = (wid - tile_id * gy) * BN;
-  }
+  const int2 tc = dense_tile<BN>(wid, gy);
+  const int tile_id = tc.x, colblock = tc.y;
   const long long p0 = (long long)tile_id * BM;
   if (p0 >= a.n_out) return;
   const int npos = (int)min((long long)BM, a.n_out - p0);
@@ -990,9 +961,7 @@ __global__ void __launch_bounds__(256, 3) k_gemm_bf2(ConvArgs a) {
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    for (int j = 0; j < 2; ++j) acc[i][j] = acc_zero();
 
   const int wm = w >> 1, wn = w & 1;
   const int half = lane >> 5, r31 = lane & 31;
@@ -1024,6 +993,7 @@ __global__ void __launch_bounds__(256, 3) k_gemm_bf2(ConvArgs a) {
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {           // smallest terms first (same order as k_conv_mfma_bf: identical results)
+          // bf6_terms (pcc_mfma.h) written out: the probe hook sits between its terms
           if (!PCC_DBG_ON(a, 8)) {                  // (timing experiment: three of the six terms)
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[2][i], bf[0][j], acc[i][j], 0, 0, 0);
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[2][j], acc[i][j], 0, 0, 0);
@@ -1052,7 +1022,7 @@ __global__ void __launch_bounds__(256, 3) k_gemm_bf2(ConvArgs a) {
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const unsigned so = (unsigned)(i * 32 + (e & 3) + 8 * (e >> 2)) * ncol * 4u;      // scalar
+        const unsigned so = (unsigned)cfrag_row(i * 32, e, 0) * ncol * 4u;      // scalar
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           const float v = acc[i][j][e];          // (a bit_cast of the vector element itself compiles to element 0)
@@ -1069,7 +1039,7 @@ __global__ void __launch_bounds__(256, 3) k_gemm_bf2(ConvArgs a) {
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int r = wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
+        const int r = cfrag_row(wm * 64 + i * 32, e, half);
         if (r >= npos) continue;
         obase[(size_t)r * ncol + (unsigned)(wn * 64 + j * 32 + r31)] = acc[i][j][e];
       }
@@ -1090,8 +1060,7 @@ __global__ void __launch_bounds__(256, 3) k_gdn_bf(ConvArgs a) {
   __shared__ __attribute__((aligned(16))) uint4 As[BM * LDU];
   __shared__ __attribute__((aligned(16))) uint4 Bs[BN * LDU];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int cpx = gridDim.x >> 3;
-  const int wid = (blockIdx.x & 7) * cpx + (blockIdx.x >> 3);
+  const int wid = xcd_work_id();
   const int gy = a.cout_pad / BN;
   const int tile_id = wid / gy;
   const int colblock = (wid - tile_id * gy) * BN;
@@ -1106,15 +1075,13 @@ __global__ void __launch_bounds__(256, 3) k_gdn_bf(ConvArgs a) {
 #pragma unroll
   for (int q = 0; q < NX; ++q) { const int u = q * 256 + tid; x_row[q] = u >> 3; x_j[q] = u & 7; }
 #pragma unroll
-  for (int q = 0; q < NB; ++q) { const int u = q * 256 + tid; b_row[q] = u / 12; b_w[q] = u - b_row[q] * 12; if (u >= BN * 12) b_row[q] = -1; }
+  for (int q = 0; q < NB; ++q) stage_role(q * 256 + tid, BN, b_row[q], b_w[q]);
 
   f32x16 acc[TM][TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    for (int j = 0; j < TN; ++j) acc[i][j] = acc_zero();
   const int wm = w / WN, wn = w % WN;
   const int half = lane >> 5, r31 = lane & 31;
 
@@ -1134,7 +1101,7 @@ __global__ void __launch_bounds__(256, 3) k_gdn_bf(ConvArgs a) {
     const unsigned wbase = (unsigned)(cbi * a.cout_pad + colblock) * 192u;
 #pragma unroll
     for (int q = 0; q < NB; ++q) {
-      const unsigned off = b_row[q] >= 0 ? wbase + (unsigned)(q * 256 + tid) * 16u : BUF_OOB;
+      const unsigned off = b_row[q] >= 0 ? wbase + (unsigned)(q * 256 + tid) * 16u : BUF_OOB;     // load_b_unit (pcc_mfma.h) written out: the helper reorders this kernel
       bv[q] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsB, off, 0, 0));
     }
   };
@@ -1144,13 +1111,8 @@ __global__ void __launch_bounds__(256, 3) k_gdn_bf(ConvArgs a) {
     __syncthreads();   // previous chunk's fragment reads are done
 #pragma unroll
     for (int q = 0; q < NX; ++q) {
-      unsigned h0, m0, l0, h1, m1, l1;
-      bf_split2(fabsf(xv[q].x), fabsf(xv[q].y), h0, m0, l0);
-      bf_split2(fabsf(xv[q].z), fabsf(xv[q].w), h1, m1, l1);
       const int o = x_row[q] * (LDU * 2) + x_j[q];                    // 8-byte slots: plane p of the row starts at slot 8 p
-      As64[o] = (unsigned long long)h0 | ((unsigned long long)h1 << 32);
-      As64[o + 8] = (unsigned long long)m0 | ((unsigned long long)m1 << 32);
-      As64[o + 16] = (unsigned long long)l0 | ((unsigned long long)l1 << 32);
+      stage_split4(As64, o, fabsf(xv[q].x), fabsf(xv[q].y), fabsf(xv[q].z), fabsf(xv[q].w));
     }
 #pragma unroll
     for (int q = 0; q < NB; ++q)
@@ -1174,6 +1136,7 @@ __global__ void __launch_bounds__(256, 3) k_gdn_bf(ConvArgs a) {
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) {           // smallest terms first (the order of k_conv_mfma_bf)
+          // bf6_terms (pcc_mfma.h) written out: through the helper the TM = 1 kernels schedule differently
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[2][i], bf[0][j], acc[i][j], 0, 0, 0);
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[2][j], acc[i][j], 0, 0, 0);
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][i], bf[1][j], acc[i][j], 0, 0, 0);
@@ -1193,7 +1156,7 @@ __global__ void __launch_bounds__(256, 3) k_gdn_bf(ConvArgs a) {
     for (int i = 0; i < TM; ++i)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int r = (wm * TM + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
+        const int r = cfrag_row((wm * TM + i) * 32, e, half);
         if (r >= npos) continue;
         const size_t o = (size_t)(pos0 + r) * a.cout + col;
         const float v = acc[i][j][e] + b;
@@ -1233,8 +1196,7 @@ __global__ void __launch_bounds__(256, 3) k_conv_in4_bf(ConvArgs a, const unsign
   __shared__ __attribute__((aligned(16))) uint4 As[BM * LDU];
   __shared__ __attribute__((aligned(16))) uint4 Bs[BN * LDU];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int cpx = gridDim.x >> 3;
-  const int wid = (blockIdx.x & 7) * cpx + (blockIdx.x >> 3);
+  const int wid = xcd_work_id();
   const int gy = a.cout_pad / BN;
   const int tile_id = wid / gy;
   const int colblock = (wid - tile_id * gy) * BN;
@@ -1249,15 +1211,13 @@ __global__ void __launch_bounds__(256, 3) k_conv_in4_bf(ConvArgs a, const unsign
 #pragma unroll
   for (int q = 0; q < NX; ++q) { const int u = q * 256 + tid; x_row[q] = u >> 3; x_j[q] = u & 7; }
 #pragma unroll
-  for (int q = 0; q < NB; ++q) { const int u = q * 256 + tid; b_row[q] = u / 12; b_w[q] = u - b_row[q] * 12; if (u >= BN * 12) b_row[q] = -1; }
+  for (int q = 0; q < NB; ++q) stage_role(q * 256 + tid, BN, b_row[q], b_w[q]);
 
   f32x16 acc[TM][TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    for (int j = 0; j < TN; ++j) acc[i][j] = acc_zero();
   const int wm = w / WN, wn = w % WN;
   const int half = lane >> 5, r31 = lane & 31;
 
@@ -1283,8 +1243,7 @@ __global__ void __launch_bounds__(256, 3) k_conv_in4_bf(ConvArgs a, const unsign
     const unsigned wbase = (unsigned)(c * a.cout_pad + colblock) * 192u;
 #pragma unroll
     for (int q = 0; q < NB; ++q) {
-      const unsigned off = b_row[q] >= 0 ? wbase + (unsigned)(q * 256 + tid) * 16u : BUF_OOB;
-      bv[q] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsB, off, 0, 0));
+      bv[q] = load_b_unit(rsB, wbase, b_row[q], q, tid);
     }
   };
   load_idx(0);
@@ -1295,13 +1254,8 @@ __global__ void __launch_bounds__(256, 3) k_conv_in4_bf(ConvArgs a, const unsign
     __syncthreads();   // previous chunk's fragment reads are done
 #pragma unroll
     for (int q = 0; q < NX; ++q) {
-      unsigned h0, m0, l0, h1, m1, l1;
-      bf_split2(__uint_as_float(xv[q].x), __uint_as_float(xv[q].y), h0, m0, l0);
-      bf_split2(__uint_as_float(xv[q].z), __uint_as_float(xv[q].w), h1, m1, l1);
       const int o = x_row[q] * (LDU * 2) + x_j[q];                    // 8-byte slots: plane p of the row starts at slot 8 p
-      As64[o] = (unsigned long long)h0 | ((unsigned long long)h1 << 32);
-      As64[o + 8] = (unsigned long long)m0 | ((unsigned long long)m1 << 32);
-      As64[o + 16] = (unsigned long long)l0 | ((unsigned long long)l1 << 32);
+      stage_split4(As64, o, __uint_as_float(xv[q].x), __uint_as_float(xv[q].y), __uint_as_float(xv[q].z), __uint_as_float(xv[q].w));
     }
 #pragma unroll
     for (int q = 0; q < NB; ++q)
@@ -1328,12 +1282,7 @@ __global__ void __launch_bounds__(256, 3) k_conv_in4_bf(ConvArgs a, const unsign
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) {           // smallest terms first
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[2][i], bf[0][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[2][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][i], bf[1][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][i], bf[0][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[1][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[0][j], acc[i][j], 0, 0, 0);
+          acc[i][j] = bf6_terms(af[0][i], af[1][i], af[2][i], bf[0][j], bf[1][j], bf[2][j], acc[i][j]);
         }
     }
   }
@@ -1346,7 +1295,7 @@ __global__ void __launch_bounds__(256, 3) k_conv_in4_bf(ConvArgs a, const unsign
     for (int i = 0; i < TM; ++i)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int r = (wm * TM + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
+        const int r = cfrag_row((wm * TM + i) * 32, e, half);
         if (r >= npos) continue;
         a.out[(size_t)(pos0 + r) * a.cout + col] = act1(acc[i][j][e] + b, a.act, a.slope);
       }
@@ -1375,18 +1324,10 @@ __global__ void __launch_bounds__(256, 3) k_gemm_h2(ConvArgs a) {
   __shared__ __attribute__((aligned(16))) uint4 Bs[BN * LDU];
   __shared__ __attribute__((aligned(16))) float rs[BM];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int cpx = gridDim.x >> 3;
-  const int wid = (blockIdx.x & 7) * cpx + (blockIdx.x >> 3);
+  const int wid = xcd_work_id();
   const int gy = (a.cout_pad + BN - 1) / BN;
-  int tile_id, colblock;
-  if (gy > 8) {
-    const int g = wid / (8 * gy), rem = wid - g * 8 * gy;
-    colblock = (rem >> 3) * BN;
-    tile_id = g * 8 + (rem & 7);
-  } else {
-    tile_id = wid / gy;
-    colblock = (wid - tile_id * gy) * BN;
-  }
+  const int2 tc = dense_tile<BN>(wid, gy);
+  const int tile_id = tc.x, colblock = tc.y;
   const long long p0 = (long long)tile_id * BM;
   if (p0 >= a.n_out) return;
   const int npos = (int)min((long long)BM, a.n_out - p0);
@@ -1426,9 +1367,7 @@ __global__ void __launch_bounds__(256, 3) k_gemm_h2(ConvArgs a) {
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    for (int j = 0; j < TN; ++j) acc[i][j] = acc_zero();
 
   const int wm = w >> 1, wn = w & 1;
   const int half = lane >> 5, r31 = lane & 31;
@@ -1467,9 +1406,7 @@ __global__ void __launch_bounds__(256, 3) k_gemm_h2(ConvArgs a) {
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) {           // small terms first
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1][i], bf[0][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0][i], bf[1][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0][i], bf[0][j], acc[i][j], 0, 0, 0);
+          acc[i][j] = h3_terms(af[0][i], af[1][i], bf[0][j], bf[1][j], acc[i][j]);
         }
     }
   }
@@ -1488,6 +1425,8 @@ __global__ void __launch_bounds__(256, 3) k_gemm_h2(ConvArgs a) {
   // (32-deep products have hardly any operand to protect, and as a pure stream non-temporal stores are the slower ones --
   //  4.2 against 5.0 TB/s, tools/gemm_nt_probe.sh: the hint is taken from 64 input channels on; PCC_NT bit 6 forces it.)
   const bool nt = (a.nt & 1) != 0 && (NCH >= 2 || (a.nt & 64));
+  // The scaled store below (row scales from LDS, rr * cs, nt / plain / out-of-range buffer stores, range guard) is mirrored by
+  // k_pair_h2, kept in step by hand: one function template over acc[2][TN] and cs[TN] changed all ten instantiations of the two.
   const int row_lim = npos - wm * 64 - 4 * half;
   const int col_lim = (int)ncol - colblock - wn * 32 * TN - r31;
   float guard_mr = 0.f, guard_mc = 0.f;
@@ -1535,8 +1474,7 @@ __global__ void __launch_bounds__(256, 3) k_pair_h2(ConvArgs a) {
   __shared__ __attribute__((aligned(16))) uint4 Bs[BN * LDU];
   __shared__ __attribute__((aligned(16))) float rs[BM];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int cpx = gridDim.x >> 3;
-  const int wid = (blockIdx.x & 7) * cpx + (blockIdx.x >> 3);
+  const int wid = xcd_work_id();
   const int gy = a.cout_pad / BN;
   const int tile_id = wid / gy;
   const int colblock = (wid - tile_id * gy) * BN;
@@ -1577,9 +1515,7 @@ __global__ void __launch_bounds__(256, 3) k_pair_h2(ConvArgs a) {
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    for (int j = 0; j < 2; ++j) acc[i][j] = acc_zero();
 
   const int wm = w >> 1, wn = w & 1;
   const int half = lane >> 5, r31 = lane & 31;
@@ -1617,13 +1553,12 @@ __global__ void __launch_bounds__(256, 3) k_pair_h2(ConvArgs a) {
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1][i], bf[0][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0][i], bf[1][j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0][i], bf[0][j], acc[i][j], 0, 0, 0);
+          acc[i][j] = h3_terms(af[0][i], af[1][i], bf[0][j], bf[1][j], acc[i][j]);
         }
     }
   }
-  // ---- stores: the tile's 128 product rows are consecutive rows of T (padding pairs included: they are zero)
+  // ---- stores: the tile's 128 product rows are consecutive rows of T (padding pairs included: they are zero).  The scaled store
+  //      of k_gemm_h2 without its row check, kept in step with it by hand (see there)
   const unsigned ncol = (unsigned)a.cout;
   float* const obase = a.out + (size_t)p0 * ncol + colblock;
   const __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc(
@@ -1658,6 +1593,36 @@ __global__ void __launch_bounds__(256, 3) k_pair_h2(ConvArgs a) {
       }
     }
   if (a.guard && guard_mr * fmaxf(cs[0], cs[1]) * (8.f * (float)a.cin) > a.guard_lim) atomicOr(a.guard, 1);   // range guard, as in k_gemm_h2
+}
+
+// the chunk counts NCH = cin / 32 the unrolled products (k_gemm_bf2, k_gemm_h2, k_pair_h2) are built for
+static bool nch_ok(int nch) { return nch == 1 || nch == 2 || nch == 4 || nch == 6 || nch == 8; }
+// f(integral_constant<NCH>) for the chunk count nch, one of nch_ok()
+template <typename F>
+static void with_nch(int nch, F f) {
+  switch (nch) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+  }
+}
+
+static int launch_gemm_bf2(const ConvArgs& a, dim3 grid, hipStream_t s) {
+  with_nch(a.ppo, [&](auto nch) { k_gemm_bf2<decltype(nch)::value><<<grid, 256, 0, s>>>(a); });
+  PCC_LAUNCH_CHECK();
+  return PCC_OK;
+}
+static int launch_gemm_h2(const ConvArgs& a, dim3 grid, hipStream_t s) {
+  with_nch(a.ppo, [&](auto nch) { k_gemm_h2<decltype(nch)::value><<<grid, 256, 0, s>>>(a); });
+  PCC_LAUNCH_CHECK();
+  return PCC_OK;
+}
+static int launch_pair_h2(const ConvArgs& a, dim3 grid, hipStream_t s) {
+  with_nch(a.ppo, [&](auto nch) { k_pair_h2<decltype(nch)::value><<<grid, 256, 0, s>>>(a); });
+  PCC_LAUNCH_CHECK();
+  return PCC_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1860,7 +1825,6 @@ __global__ void __launch_bounds__(256) k_thin_gather(ThinGatherArgs a) {
 // layout (lane = row, 16-byte k-quads) and never meets a workgroup barrier in its main loop.  No padding to a
 // 32-wide column tile, offsets with no neighbour in the wave's 32 rows are skipped by ballot.
 // ------------------------------------------------------------------------------------------
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct Wave16Args {
   const float* feat; const float* wl; const float* bias; const int* hdr; const int* nbr; const int* rows;
@@ -2186,6 +2150,14 @@ static int split_planes(float* packed, int64_t fp32_elems, int cin, hipStream_t 
   PCC_LAUNCH_CHECK();
   return PCC_OK;
 }
+// the scaled fp16 planes and column scales behind the bf16 planes of a pack of K offsets (K = 1: the flat operand of a dense product)
+static int split_planes_h(float* packed, int64_t fp32_elems, int K, int cin, int cout_pad, hipStream_t s) {
+  float* const planes = packed + fp32_elems + bf_plane_elems(fp32_elems);
+  k_split_packed_h<<<dim3((unsigned)pcc_cdiv(cout_pad, 128), (unsigned)K), 128, 0, s>>>(packed, cin >> 5, cout_pad, (unsigned char*)planes,
+                                                                                       planes + fp32_elems);
+  PCC_LAUNCH_CHECK();
+  return PCC_OK;
+}
 static int conv_kind(int K, int cin, int cout) {
   if (cout <= 4) {
     const bool pow2 = cin == 4 || cin == 8 || cin == 16 || cin == 32 || cin == 64;
@@ -2201,6 +2173,17 @@ static int conv_kind(int K, int cin, int cout) {
 // planes and the 1/scale of every (offset, column), fp32 image | bf16 planes | fp16 planes | K*cout_pad scales
 static bool conv_has_h(int K, int cin, int cout) {
   return K >= 64 && cin % 32 == 0 && cin <= 256 && cout % 4 == 0 && bn_for(cout) == 128;
+}
+// The fields every MFMA launch fills: an identity map (no header, one output row per input row or pair) of a K-offset pack.
+// Callers with a kernel map set hdr / nbr / rows afterwards; pair products set pair_in / tile_k / n_tiles.
+static ConvArgs conv_args(const float* feat, long long n_in, int cin, const float* wp, int K, int cout, const float* bias,
+                          float* out, long long n_out, int act = 0, float slope = 0.f) {
+  ConvArgs a;
+  a.feat = feat; a.wp = wp; a.bias = bias; a.hdr = nullptr; a.nbr = nullptr; a.rows = nullptr; a.out = out;
+  a.n_out = n_out; a.cin = cin; a.cout = cout; a.cout_pad = cout_pad_for(cout);
+  a.n_in = n_in; a.wp_elems = (long long)K * cin * a.cout_pad;
+  a.cb_log2 = cb_log2_for(cin); a.ppo = cin >> a.cb_log2; a.act = act; a.slope = slope;
+  return a;
 }
 extern "C" int64_t pcc_conv_packed_elems(int32_t K, int32_t cin, int32_t cout) {
   if (K <= 0 || cin <= 0 || cout <= 0) return 0;
@@ -2331,9 +2314,7 @@ static int pack_weights_impl(const float* W, int32_t K, int32_t cin, int32_t cou
       }
       if (conv_has_h(K, cin, cout)) {
         const int cp = cout_pad_for(cout);
-        float* const planes = packed + base + bf_plane_elems(base);
-        k_split_packed_h<<<dim3((unsigned)pcc_cdiv(cp, 128), (unsigned)K), 128, 0, s>>>(packed, cin >> 5, cp, (unsigned char*)planes, planes + base);
-        PCC_LAUNCH_CHECK();
+        PCC_TRY(split_planes_h(packed, base, K, cin, cp, s));
       }
       break;
     }
@@ -2378,14 +2359,22 @@ extern "C" int pcc_prof_enable(int32_t on) {
   return PCC_OK;
 }
 
-static int prof_event(hipEvent_t* ev, hipStream_t s) {
+static int prof_event(hipStream_t s) {
   if (g_ev_used == g_ev_pool.size()) {
     hipEvent_t e;
     PCC_CHECK_HIP(hipEventCreate(&e));
     g_ev_pool.push_back(e);
   }
-  *ev = g_ev_pool[g_ev_used++];
-  PCC_CHECK_HIP(hipEventRecord(*ev, s));
+  PCC_CHECK_HIP(hipEventRecord(g_ev_pool[g_ev_used++], s));
+  return PCC_OK;
+}
+// event pair around a launch while pcc_prof_enable is on (and `when`)
+static int prof_begin(hipStream_t s, bool when = true) { return (g_prof_on && when) ? prof_event(s) : PCC_OK; }
+static int prof_end(hipStream_t s, bool when = true, int form = -1) {   // form >= 0: noted between the end event and the record
+  if (!(g_prof_on && when)) return PCC_OK;
+  PCC_TRY(prof_event(s));
+  if (form >= 0) prof_note(form, 0.0, 0.0);
+  prof_push();
   return PCC_OK;
 }
 
@@ -2494,21 +2483,12 @@ static int launch_mfma(const ConvArgs& a_in, int tiles_bound_extra, hipStream_t 
   // dense products of the generative transposed convolutions whose pack carries fp16 planes: three-term fp16 form
   if (split && a.arith == PCC_ARITH_H3 && a.wh_ok && MODE == MODE_CONV && !a.hdr && !a.pair_in && !a.rows && !a.bias && a.act == 0 && ksplit == 1 &&
       bn == 128 && (tiles(128) * gy >= want || a.feath) && (size_t)128 * a.cout * 4 < (1ull << 31) &&
-      (a.ppo == 1 || a.ppo == 2 || a.ppo == 4 || a.ppo == 6 || a.ppo == 8)) {      // (caller's planes: the caller chose the form)
+      nch_ok(a.ppo)) {      // (caller's planes: the caller chose the form)
     if (!a.feath) PCC_TRY(make_planes_h(a, s));
     a.dbg = g_dbg;
     a.nt = g_nt;
     prof_note(PCC_FORM_GEMM_H2, 2.0 * a.n_out * a.cin * a.cout, 4.0 * ((double)a.n_out * a.cin + (double)a.n_out * a.cout + (double)a.cin * a.cout));
-    const dim3 g2 = grid(128);
-    switch (a.ppo) {
-      case 1: k_gemm_h2<1><<<g2, 256, 0, s>>>(a); break;
-      case 2: k_gemm_h2<2><<<g2, 256, 0, s>>>(a); break;
-      case 4: k_gemm_h2<4><<<g2, 256, 0, s>>>(a); break;
-      case 6: k_gemm_h2<6><<<g2, 256, 0, s>>>(a); break;
-      default: k_gemm_h2<8><<<g2, 256, 0, s>>>(a); break;
-    }
-    PCC_LAUNCH_CHECK();
-    return PCC_OK;
+    return launch_gemm_h2(a, grid(128), s);
   }
   if (split && a.featb) {
     PCC_REQUIRE(ksplit == 1, "launch_mfma: caller planes with a split reduction");
@@ -2529,18 +2509,8 @@ static int launch_mfma(const ConvArgs& a_in, int tiles_bound_extra, hipStream_t 
   // plain dense products (generative transposed convolutions): the stripped GEMM kernel
   if (split && MODE == MODE_CONV && !a.hdr && !a.pair_in && !a.rows && !a.bias && a.act == 0 && a.ksplit == 1 &&
       bn == 128 && tiles(128) * gy >= want && (size_t)128 * a.cout * 4 < (1ull << 31)) {
-    const dim3 g2 = grid(128);
-    bool done = true;
     prof_note(PCC_FORM_GEMM_BF2, 2.0 * a.n_out * a.cin * a.cout, 4.0 * ((double)a.n_out * a.cin + (double)a.n_out * a.cout + (double)a.cin * a.cout));
-    switch (a.ppo) {
-      case 1: k_gemm_bf2<1><<<g2, 256, 0, s>>>(a); break;
-      case 2: k_gemm_bf2<2><<<g2, 256, 0, s>>>(a); break;
-      case 4: k_gemm_bf2<4><<<g2, 256, 0, s>>>(a); break;
-      case 6: k_gemm_bf2<6><<<g2, 256, 0, s>>>(a); break;
-      case 8: k_gemm_bf2<8><<<g2, 256, 0, s>>>(a); break;
-      default: done = false;
-    }
-    if (done) { PCC_LAUNCH_CHECK(); return PCC_OK; }
+    if (nch_ok(a.ppo)) return launch_gemm_bf2(a, grid(128), s);
   }
   prof_note(split ? PCC_FORM_CONV_BF : PCC_FORM_CONV_F32, (!a.hdr && !a.pair_in) ? 2.0 * a.n_out * a.cin * a.cout : 0.0, 0.0);
 #define PCC_LAUNCH_MFMA(WM, WN, TM, TN, BMV)                                                     \
@@ -2567,6 +2537,37 @@ static int launch_mfma(const ConvArgs& a_in, int tiles_bound_extra, hipStream_t 
     PCC_LAUNCH_CHECK();
   }
   return PCC_OK;
+}
+
+// The gathered pair GEMM of pcc_conv_fwd_pairs and pcc_convt_fwd_rows: a (pair mode, form set) in, T = a.out written.
+static int launch_pair_product(ConvArgs& a, int K, long long tiles, hipStream_t s) {
+  PCC_TRY(prof_begin(s));
+  const int bn = bn_for(a.cout);
+  const long long gy = a.cout_pad / bn;
+  const dim3 grid((unsigned)((tiles * gy + 7) / 8 * 8));
+  const bool buf = g_mfma_buf && a.n_in * a.cin * 4 <= BUF_MAX_BYTES && a.wp_elems * 4 <= BUF_MAX_BYTES;
+  const bool split = split_ok(a);
+  const bool pair_h = split && a.arith == PCC_ARITH_H3 && conv_has_h(K, a.cin, a.cout) && (size_t)a.n_in * a.cin * 4 <= (size_t)BUF_MAX_BYTES &&
+                      nch_ok(a.ppo);
+  prof_note(pair_h ? PCC_FORM_PAIR_H2 : split ? PCC_FORM_PAIR_BF : PCC_FORM_CONV_F32, 0.0, 0.0);
+#define PCC_LAUNCH_PAIR(WM, WN, TM, TN)                                                         \
+  do {                                                                                          \
+    if (split) k_conv_mfma_bf<WM, WN, TM, TN, MODE_CONV><<<grid, 256, 0, s>>>(a);               \
+    else if (buf) k_conv_mfma<WM, WN, TM, TN, MODE_CONV, true><<<grid, 256, 0, s>>>(a);         \
+    else k_conv_mfma<WM, WN, TM, TN, MODE_CONV, false><<<grid, 256, 0, s>>>(a);                 \
+  } while (0)
+  if (pair_h) {                                   // scaled fp16 pairs, three MFMA terms (k_pair_h2)
+    PCC_TRY(make_planes_h(a, s));
+    PCC_TRY(launch_pair_h2(a, grid, s));
+  } else {
+    if (split) PCC_TRY(make_planes(a, false, s));
+    if (bn == 128) PCC_LAUNCH_PAIR(2, 2, 2, 2);
+    else if (bn == 64) PCC_LAUNCH_PAIR(2, 2, 2, 1);
+    else PCC_LAUNCH_PAIR(4, 1, 1, 1);
+    PCC_LAUNCH_CHECK();
+  }
+#undef PCC_LAUNCH_PAIR
+  return prof_end(s);
 }
 
 static bool g_wave16_zrun = getenv("PCC_WAVE16_ZRUN") ? atoi(getenv("PCC_WAVE16_ZRUN")) != 0 : true;
@@ -2643,7 +2644,7 @@ __global__ void __launch_bounds__(256) k_thin_project_mfma(const float* __restri
     if (row < n_in) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int k = (e & 3) + 8 * (e >> 2) + 4 * half;
+        const int k = cfrag_row(0, e, half);
         if (k < kc) t[(long long)k * n_in + row] = acc[e];
       }
     }
@@ -2698,15 +2699,11 @@ extern "C" int pcc_conv_fwd(const float* feat_in, int64_t n_in, int32_t cin, con
   PCC_REQUIRE(n_in < (1ll << 31) && n_out < (1ll << 31), "pcc_conv_fwd: too many rows");
   const int kind = conv_kind(K, cin, cout);
   PCC_REQUIRE(kind != KIND_NONE, "pcc_conv_fwd: unsupported shape cin=%d cout=%d", cin, cout);
-  hipEvent_t e0, e1;
-  const bool timed = g_prof_on && (kind == KIND_MFMA || kind == KIND_WAVE16);   // the roofline kernels: MFMA launches
-  if (timed) PCC_TRY(prof_event(&e0, s));
+  const bool timed = kind == KIND_MFMA || kind == KIND_WAVE16;   // the roofline kernels: MFMA launches
+  PCC_TRY(prof_begin(s, timed));
   if (kind == KIND_MFMA) {
-    ConvArgs a;
-    a.feat = feat_in; a.wp = packed_w; a.bias = bias; a.hdr = hdr; a.nbr = nbr; a.rows = rows; a.out = out;
-    a.n_out = n_out; a.cin = cin; a.cout = cout; a.cout_pad = cout_pad_for(cout);
-    a.n_in = n_in; a.wp_elems = (long long)K * cin * a.cout_pad;
-    a.cb_log2 = cb_log2_for(cin); a.ppo = cin >> a.cb_log2; a.act = act; a.slope = slope;
+    ConvArgs a = conv_args(feat_in, n_in, cin, packed_w, K, cout, bias, out, n_out, act, slope);
+    a.hdr = hdr; a.nbr = nbr; a.rows = rows;
     PCC_TRY(set_arith(a, arith, d_guard, "pcc_conv_fwd"));
     const bool in4 = g_in4_min_rows >= 0 && arith != PCC_ARITH_F32;
     // the input layer: 4 channels, K * 4 <= 512 flattened into one reduction axis (k_conv_in4_bf); plain conv maps of >= 64 k
@@ -2763,10 +2760,7 @@ extern "C" int pcc_conv_fwd(const float* feat_in, int64_t n_in, int32_t cin, con
     else k_conv_thin<4, 1><<<(unsigned)pcc_cdiv(waves, 4), 256, 0, s>>>(t);
     PCC_LAUNCH_CHECK();
   }
-  if (timed) {
-    PCC_TRY(prof_event(&e1, s));
-    prof_push();
-  }
+  PCC_TRY(prof_end(s, timed));
   return PCC_OK;
 }
 
@@ -2894,15 +2888,11 @@ extern "C" int pcc_conv_head_fwd(const float* feat, int64_t n, int32_t cin, cons
   a.feat = feat; a.wl = packed_w0; a.bias = bias0; a.hdr = hdr; a.nbr = nbr; a.rows = nullptr; a.out = nullptr;
   a.n_out = n; a.n_in = n; a.K = 27; a.cout = cmid; a.act = PCC_ACT_RELU; a.slope = 0.f;
   a.tiles = tiles; a.n_tiles = n_tiles; a.w2 = w2; a.t = (float*)ws;
-  hipEvent_t e0, e1;
-  if (g_prof_on) PCC_TRY(prof_event(&e0, s));
+  PCC_TRY(prof_begin(s));
   if (cin == 16) PCC_TRY(launch_wave16<16>(a, s));
   else if (cin == 32) PCC_TRY(launch_wave16<32>(a, s));
   else PCC_TRY(launch_wave16<64>(a, s));
-  if (g_prof_on) {
-    PCC_TRY(prof_event(&e1, s));
-    prof_push();
-  }
+  PCC_TRY(prof_end(s));
   ThinGatherArgs g;
   g.t = (const float*)ws; g.bias = bias2; g.hdr = hdr; g.nbr = nbr; g.rows = nullptr; g.out = logits; g.n_in = n; g.n_out = n;
   g.cout = 1; g.act = PCC_ACT_NONE; g.slope = 0.f;
@@ -3071,42 +3061,10 @@ extern "C" int pcc_conv_fwd_pairs(const float* feat_in, int64_t n_in, int32_t ci
   PCC_REQUIRE(padded_pairs % PAIR_BM == 0 && padded_pairs < (1ll << 31), "pcc_conv_fwd_pairs: bad pair count");
   PCC_REQUIRE(act >= 0 && act <= 2, "pcc_conv_fwd_pairs: bad activation");
   if (padded_pairs > 0) {
-    ConvArgs a;
-    a.feat = feat_in; a.wp = packed_w; a.bias = nullptr; a.hdr = nullptr; a.nbr = nullptr; a.rows = nullptr; a.out = T;
-    a.n_out = padded_pairs; a.cin = cin; a.cout = cout; a.cout_pad = cout_pad_for(cout);
-    a.n_in = n_in; a.wp_elems = (long long)K * cin * a.cout_pad;
-    a.cb_log2 = cb_log2_for(cin); a.ppo = cin >> a.cb_log2; a.act = 0; a.slope = 0.f;
+    ConvArgs a = conv_args(feat_in, n_in, cin, packed_w, K, cout, nullptr, T, padded_pairs);
     a.pair_in = pair_in; a.tile_k = tile_k; a.n_tiles = (const long long*)d_info + 1;
     PCC_TRY(set_arith(a, arith, d_guard, "pcc_conv_fwd_pairs"));
-    hipEvent_t e0, e1;
-    if (g_prof_on) PCC_TRY(prof_event(&e0, s));
-    const int bn = bn_for(cout);
-    const long long gy = a.cout_pad / bn;
-    const dim3 grid((unsigned)((padded_pairs / PAIR_BM * gy + 7) / 8 * 8));
-    const bool buf = g_mfma_buf && n_in * cin * 4 <= BUF_MAX_BYTES && a.wp_elems * 4 <= BUF_MAX_BYTES;
-    const bool split = split_ok(a);
-    const bool pair_h = split && a.arith == PCC_ARITH_H3 && conv_has_h(K, cin, cout) && (size_t)n_in * cin * 4 <= (size_t)BUF_MAX_BYTES &&
-                        (a.ppo == 1 || a.ppo == 2 || a.ppo == 4 || a.ppo == 6 || a.ppo == 8);
-    prof_note(pair_h ? PCC_FORM_PAIR_H2 : split ? PCC_FORM_PAIR_BF : PCC_FORM_CONV_F32, 0.0, 0.0);
-    if (pair_h) {                                   // scaled fp16 pairs, three MFMA terms (k_pair_h2)
-      PCC_TRY(make_planes_h(a, s));
-      switch (a.ppo) {
-        case 1: k_pair_h2<1><<<grid, 256, 0, s>>>(a); break;
-        case 2: k_pair_h2<2><<<grid, 256, 0, s>>>(a); break;
-        case 4: k_pair_h2<4><<<grid, 256, 0, s>>>(a); break;
-        case 6: k_pair_h2<6><<<grid, 256, 0, s>>>(a); break;
-        default: k_pair_h2<8><<<grid, 256, 0, s>>>(a); break;
-      }
-    } else if (split) PCC_TRY(make_planes(a, false, s));
-    if (pair_h) {}
-    else if (bn == 128) { if (split) k_conv_mfma_bf<2, 2, 2, 2, MODE_CONV><<<grid, 256, 0, s>>>(a); else if (buf) k_conv_mfma<2, 2, 2, 2, MODE_CONV, true><<<grid, 256, 0, s>>>(a); else k_conv_mfma<2, 2, 2, 2, MODE_CONV, false><<<grid, 256, 0, s>>>(a); }
-    else if (bn == 64) { if (split) k_conv_mfma_bf<2, 2, 2, 1, MODE_CONV><<<grid, 256, 0, s>>>(a); else if (buf) k_conv_mfma<2, 2, 2, 1, MODE_CONV, true><<<grid, 256, 0, s>>>(a); else k_conv_mfma<2, 2, 2, 1, MODE_CONV, false><<<grid, 256, 0, s>>>(a); }
-    else { if (split) k_conv_mfma_bf<4, 1, 1, 1, MODE_CONV><<<grid, 256, 0, s>>>(a); else if (buf) k_conv_mfma<4, 1, 1, 1, MODE_CONV, true><<<grid, 256, 0, s>>>(a); else k_conv_mfma<4, 1, 1, 1, MODE_CONV, false><<<grid, 256, 0, s>>>(a); }
-    PCC_LAUNCH_CHECK();
-    if (g_prof_on) {
-      PCC_TRY(prof_event(&e1, s));
-      prof_push();
-    }
+    PCC_TRY(launch_pair_product(a, K, padded_pairs / PAIR_BM, s));
   }
   PairReduceArgs r;
   r.T = T; r.bias = bias; r.pos = pos; r.out = out; r.n_out = n_out; r.K = K; r.cout = cout; r.act = act; r.slope = slope;
@@ -3273,44 +3231,10 @@ extern "C" int pcc_convt_fwd_rows(const float* feat_in, int64_t n_in, int32_t ci
   const int64_t tiles_cap = padded_cap / PAIR_BM;
   k_pair_tile_k<<<(unsigned)pcc_cdiv(tiles_cap, 256), 256, 0, s>>>(pstart, K, tiles_cap, tile_k);
   PCC_LAUNCH_CHECK();
-  {
-    ConvArgs a;
-    a.feat = feat_in; a.wp = packed_w; a.bias = nullptr; a.hdr = nullptr; a.nbr = nullptr; a.rows = nullptr; a.out = T;
-    a.n_out = padded_cap; a.cin = cin; a.cout = cout; a.cout_pad = cout_pad_for(cout);
-    a.n_in = n_in; a.wp_elems = (long long)K * cin * a.cout_pad;
-    a.cb_log2 = cb_log2_for(cin); a.ppo = cin >> a.cb_log2; a.act = 0; a.slope = 0.f;
-    a.pair_in = pair_in; a.tile_k = tile_k; a.n_tiles = info + 1;
-    PCC_TRY(set_arith(a, arith, d_guard, "pcc_convt_fwd_rows"));
-    hipEvent_t e0, e1;
-    if (g_prof_on) PCC_TRY(prof_event(&e0, s));
-    const int bn = bn_for(cout);
-    const long long gy = a.cout_pad / bn;
-    const dim3 grid((unsigned)((tiles_cap * gy + 7) / 8 * 8));
-    const bool buf = g_mfma_buf && n_in * cin * 4 <= BUF_MAX_BYTES && a.wp_elems * 4 <= BUF_MAX_BYTES;
-    const bool split = split_ok(a);
-    const bool pair_h = split && a.arith == PCC_ARITH_H3 && conv_has_h(K, cin, cout) && (size_t)n_in * cin * 4 <= (size_t)BUF_MAX_BYTES &&
-                        (a.ppo == 1 || a.ppo == 2 || a.ppo == 4 || a.ppo == 6 || a.ppo == 8);
-    prof_note(pair_h ? PCC_FORM_PAIR_H2 : split ? PCC_FORM_PAIR_BF : PCC_FORM_CONV_F32, 0.0, 0.0);
-    if (pair_h) {                                   // scaled fp16 pairs, three MFMA terms (k_pair_h2)
-      PCC_TRY(make_planes_h(a, s));
-      switch (a.ppo) {
-        case 1: k_pair_h2<1><<<grid, 256, 0, s>>>(a); break;
-        case 2: k_pair_h2<2><<<grid, 256, 0, s>>>(a); break;
-        case 4: k_pair_h2<4><<<grid, 256, 0, s>>>(a); break;
-        case 6: k_pair_h2<6><<<grid, 256, 0, s>>>(a); break;
-        default: k_pair_h2<8><<<grid, 256, 0, s>>>(a); break;
-      }
-    } else if (split) PCC_TRY(make_planes(a, false, s));
-    if (pair_h) {}
-    else if (bn == 128) { if (split) k_conv_mfma_bf<2, 2, 2, 2, MODE_CONV><<<grid, 256, 0, s>>>(a); else if (buf) k_conv_mfma<2, 2, 2, 2, MODE_CONV, true><<<grid, 256, 0, s>>>(a); else k_conv_mfma<2, 2, 2, 2, MODE_CONV, false><<<grid, 256, 0, s>>>(a); }
-    else if (bn == 64) { if (split) k_conv_mfma_bf<2, 2, 2, 1, MODE_CONV><<<grid, 256, 0, s>>>(a); else if (buf) k_conv_mfma<2, 2, 2, 1, MODE_CONV, true><<<grid, 256, 0, s>>>(a); else k_conv_mfma<2, 2, 2, 1, MODE_CONV, false><<<grid, 256, 0, s>>>(a); }
-    else { if (split) k_conv_mfma_bf<4, 1, 1, 1, MODE_CONV><<<grid, 256, 0, s>>>(a); else if (buf) k_conv_mfma<4, 1, 1, 1, MODE_CONV, true><<<grid, 256, 0, s>>>(a); else k_conv_mfma<4, 1, 1, 1, MODE_CONV, false><<<grid, 256, 0, s>>>(a); }
-    PCC_LAUNCH_CHECK();
-    if (g_prof_on) {
-      PCC_TRY(prof_event(&e1, s));
-      prof_push();
-    }
-  }
+  ConvArgs a = conv_args(feat_in, n_in, cin, packed_w, K, cout, nullptr, T, padded_cap);
+  a.pair_in = pair_in; a.tile_k = tile_k; a.n_tiles = info + 1;
+  PCC_TRY(set_arith(a, arith, d_guard, "pcc_convt_fwd_rows"));
+  PCC_TRY(launch_pair_product(a, K, tiles_cap, s));
   CsrReduceArgs r;
   r.T = T; r.bias = bias; r.first = first; r.slot = slot; r.out = out; r.n_out = n_out; r.cout = cout; r.act = act; r.slope = slope;
   int l = 0;
@@ -3373,9 +3297,7 @@ extern "C" int pcc_convt_pack_weights(const float* W, int32_t K, int32_t cin, in
   PCC_TRY(split_planes(packed, base, cin, s));
   if (convt_has_h(cin)) {
     const int cp = cout_pad_for(K * cout);
-    float* const planes = packed + base + bf_plane_elems(base);
-    k_split_packed_h<<<(unsigned)pcc_cdiv(cp, 128), 128, 0, s>>>(packed, cin >> 5, cp, (unsigned char*)planes, planes + base);
-    PCC_LAUNCH_CHECK();
+    PCC_TRY(split_planes_h(packed, base, 1, cin, cp, s));
   }
   return PCC_OK;
 }
@@ -3447,20 +3369,12 @@ extern "C" int pcc_convt_fwd(const float* feat_in, int64_t n_in, int32_t cin, co
   PCC_REQUIRE(act >= 0 && act <= 2, "pcc_convt_fwd: bad activation");
   PCC_REQUIRE(n_in < (1ll << 31) && n_out < (1ll << 31), "pcc_convt_fwd: too many rows");
   // 1) dense GEMM  T[n_in, K*cout] = feat[n_in, cin] @ Wflat[cin, K*cout]
-  ConvArgs a;
-  a.feat = feat_in; a.wp = packed_w; a.bias = nullptr; a.hdr = nullptr; a.nbr = nullptr; a.rows = nullptr; a.out = T;
-  a.n_out = n_in; a.cin = cin; a.cout = K * cout; a.cout_pad = cout_pad_for(K * cout);
-  a.n_in = n_in; a.wp_elems = (long long)cin * a.cout_pad;
-  a.cb_log2 = cb_log2_for(cin); a.ppo = cin >> a.cb_log2; a.act = 0; a.slope = 0.f;
+  ConvArgs a = conv_args(feat_in, n_in, cin, packed_w, 1, K * cout, nullptr, T, n_in);
   a.wh_ok = convt_has_h(cin);
   PCC_TRY(set_arith(a, arith, d_guard, "pcc_convt_fwd"));
-  hipEvent_t e0, e1;
-  if (g_prof_on) PCC_TRY(prof_event(&e0, s));
+  PCC_TRY(prof_begin(s));
   PCC_TRY(launch_mfma<MODE_CONV>(a, 0, s));
-  if (g_prof_on) {
-    PCC_TRY(prof_event(&e1, s));
-    prof_push();
-  }
+  PCC_TRY(prof_end(s));
   // 2) ordered gather-sum through the transposed map
   GatherArgs g;
   g.T = T; g.bias = bias; g.hdr = hdr; g.nbr = nbr; g.rows = rows; g.out = out; g.n_out = n_out; g.K = K; g.cout = cout;
@@ -3658,20 +3572,12 @@ static int convt_fwd_csr_impl(const float* feat_in, int64_t n_in, int32_t cin, c
   PCC_REQUIRE(!ex_nbr || (ex_bias && ex_K >= 1), "pcc_convt_fwd_csr: ex_nbr needs ex_bias and ex_K");
   PCC_REQUIRE(act >= 0 && act <= 2, "pcc_convt_fwd_csr: bad activation");
   PCC_REQUIRE(n_in * K < (1ll << 31) && n_out < (1ll << 31), "pcc_convt_fwd_csr: too many rows");
-  ConvArgs a;
-  a.feat = feat_in; a.wp = packed_w; a.bias = nullptr; a.hdr = nullptr; a.nbr = nullptr; a.rows = nullptr; a.out = T;
-  a.n_out = n_in; a.cin = cin; a.cout = K * cout; a.cout_pad = cout_pad_for(K * cout);
-  a.n_in = n_in; a.wp_elems = (long long)cin * a.cout_pad;
-  a.cb_log2 = cb_log2_for(cin); a.ppo = cin >> a.cb_log2; a.act = 0; a.slope = 0.f;
+  ConvArgs a = conv_args(feat_in, n_in, cin, packed_w, 1, K * cout, nullptr, T, n_in);
   a.wh_ok = convt_has_h(cin);
   PCC_TRY(set_arith(a, arith, d_guard, "pcc_convt_fwd_csr"));
-  hipEvent_t e0, e1;
-  if (g_prof_on) PCC_TRY(prof_event(&e0, s));
+  PCC_TRY(prof_begin(s));
   PCC_TRY(launch_mfma<MODE_CONV>(a, 0, s));
-  if (g_prof_on) {
-    PCC_TRY(prof_event(&e1, s));
-    prof_push();
-  }
+  PCC_TRY(prof_end(s));
   GatherCsrArgs g;
   g.T = T; g.bias = bias; g.first = first; g.pair_ids = pair_ids; g.out = out; g.n_out = n_out; g.cout = cout;
   g.act = act; g.slope = slope; g.ex_nbr = ex_nbr; g.ex_bias = ex_bias; g.ex_K = ex_K; g.nt = g_nt;
@@ -3692,19 +3598,14 @@ static int convt_fwd_csr_impl(const float* feat_in, int64_t n_in, int32_t cin, c
   // pair slots per batch of independent loads: narrow outputs (the last level, ~4 pairs per row) take 4, the others 8
   // (measurement: the gather-sum of a composite level is event-timed too -- with the dense products it is the SURVEY 8d unit)
   const bool timed_gather = g_prof_on && ex_grid;
-  hipEvent_t g0, g1;
-  if (timed_gather) PCC_TRY(prof_event(&g0, s));
+  PCC_TRY(prof_begin(s, timed_gather));
   // (round 4 probe: 8 slots on the last level as well -- 1.698 vs 1.703 ms per composite level: the gather-sum is bound by the
   //  memory system's rate on 64-byte pieces, not by loads in flight)
   if (vec == 4 && l <= 2) k_convt_gather_csr<4, 4><<<gg, 256, 0, s>>>(g);
   else if (vec == 4) k_convt_gather_csr<4, 8><<<gg, 256, 0, s>>>(g);
   else k_convt_gather_csr<1, 8><<<gg, 256, 0, s>>>(g);
   PCC_LAUNCH_CHECK();
-  if (timed_gather) {
-    PCC_TRY(prof_event(&g1, s));
-    prof_note(PCC_FORM_GATHER_CSR, 0.0, 0.0);
-    prof_push();
-  }
+  PCC_TRY(prof_end(s, timed_gather, PCC_FORM_GATHER_CSR));
   return PCC_OK;
 }
 
@@ -4075,11 +3976,7 @@ extern "C" int pcc_gdn_fwd(const float* x, int64_t n, int32_t c, const float* pa
   if (n <= 0) return PCC_OK;
   PCC_REQUIRE(x && packed && beta_eff && out && x != out, "pcc_gdn_fwd: bad arguments");
   PCC_REQUIRE(mfma_ok(c, c), "pcc_gdn: channel count %d unsupported", c);
-  ConvArgs a;
-  a.feat = x; a.wp = packed; a.bias = beta_eff; a.hdr = nullptr; a.nbr = nullptr; a.rows = nullptr; a.out = out;
-  a.n_out = n; a.cin = c; a.cout = c; a.cout_pad = cout_pad_for(c);
-  a.n_in = n; a.wp_elems = (long long)c * a.cout_pad;
-  a.cb_log2 = cb_log2_for(c); a.ppo = c >> a.cb_log2; a.act = 0; a.slope = 0.f;
+  ConvArgs a = conv_args(x, n, c, packed, 1, c, beta_eff, out, n);
   PCC_TRY(set_arith(a, arith, nullptr, "pcc_gdn_fwd"));
   // large sets: split folded into the staging (k_gdn_bf), no plane round trip; small ones keep the general kernel (its
   // smaller row tiles fill the chip better below ~30 k rows)

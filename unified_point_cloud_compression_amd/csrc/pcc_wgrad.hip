@@ -9,8 +9,8 @@
 #include <stdlib.h>
 
 #include "pcc_common.h"
+#include "pcc_mfma.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 static constexpr int WG_PAIRS = 32;         // pairs staged per step
 static constexpr int WG_SLICE = 4096;       // positions per workgroup slice
@@ -107,9 +107,7 @@ __global__ void __launch_bounds__(256) k_wgrad(WgradArgs a) {
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    for (int j = 0; j < 2; ++j) acc[i][j] = acc_zero();
   bool sub_on[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -224,7 +222,7 @@ __global__ void __launch_bounds__(256) k_wgrad(WgradArgs a) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const float v = ((red[(0 * 16 + e) * 64 + lane] + red[(1 * 16 + e) * 64 + lane]) + red[(2 * 16 + e) * 64 + lane]) + red[(3 * 16 + e) * 64 + lane];
-        const int ci = m0 + (e & 3) + 8 * (e >> 2) + 4 * half;
+        const int ci = cfrag_row(m0, e, half);
         if (ci < a.cin && co < a.cout) dst[(long long)ci * a.cout + co] = v;
       }
     }
@@ -237,7 +235,7 @@ __global__ void __launch_bounds__(256) k_wgrad(WgradArgs a) {
       const int co = n0 + (wn * 2 + j) * 32 + r31;
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int ci = m0 + (wm * 2 + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
+        const int ci = cfrag_row(m0 + (wm * 2 + i) * 32, e, half);
         if (ci < a.cin && co < a.cout) dst[(long long)ci * a.cout + co] = acc[i][j][e];
       }
     }
@@ -253,17 +251,6 @@ __global__ void __launch_bounds__(256) k_wgrad(WgradArgs a) {
 // 8-byte reads per operand, rows 22 dwords apart -- are conflict-free as well.  Tile, slices, compaction of the pair list and the
 // fixed summation order are those of k_wgrad<false>.
 // ------------------------------------------------------------------------------------------
-typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 wg_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float wg_f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void wg_split2(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-  const wg_f32x2 v = {x0, x1};
-  h = __builtin_bit_cast(unsigned, __builtin_convertvector(v, wg_bf16x2));
-  const wg_f32x2 r1 = {x0 - __builtin_bit_cast(float, h << 16), x1 - __builtin_bit_cast(float, h & 0xFFFF0000u)};
-  m = __builtin_bit_cast(unsigned, __builtin_convertvector(r1, wg_bf16x2));
-  const wg_f32x2 r2 = {r1.x - __builtin_bit_cast(float, m << 16), r1.y - __builtin_bit_cast(float, m & 0xFFFF0000u)};
-  l = __builtin_bit_cast(unsigned, __builtin_convertvector(r2, wg_bf16x2));
-}
 
 static constexpr int WB_ROW = 88;                    // bytes per channel row of a transposed image
 static constexpr int WB_PLANE = 128 * WB_ROW;        // one plane: 128 channels
@@ -317,9 +304,7 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_bf(WgradArgs a) {
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    for (int j = 0; j < 2; ++j) acc[i][j] = acc_zero();
   bool sub_on[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -356,11 +341,11 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_bf(WgradArgs a) {
       for (int j = 0; j < 4; ++j) {
         unsigned h, m, l;
         const int off = (c + j) * WB_ROW + pp * 4;
-        wg_split2(xa[j], xb[j], h, m, l);
+        bf_split2(xa[j], xb[j], h, m, l);
         *reinterpret_cast<unsigned*>(Xt + off) = h;
         *reinterpret_cast<unsigned*>(Xt + WB_PLANE + off) = m;
         *reinterpret_cast<unsigned*>(Xt + 2 * WB_PLANE + off) = l;
-        wg_split2(ga[j], gb[j], h, m, l);
+        bf_split2(ga[j], gb[j], h, m, l);
         *reinterpret_cast<unsigned*>(Gt + off) = h;
         *reinterpret_cast<unsigned*>(Gt + WB_PLANE + off) = m;
         *reinterpret_cast<unsigned*>(Gt + 2 * WB_PLANE + off) = l;
@@ -372,20 +357,20 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_bf(WgradArgs a) {
   auto compute = [&]() {
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
-      wg_bf16x8 af[3][2], bf[3][2];
+      bf16x8 af[3][2], bf[3][2];
 #pragma unroll
       for (int p = 0; p < 3; ++p) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
           const unsigned char* src = Xt + p * WB_PLANE + (bm[i] * 32 + r31) * WB_ROW + kb * 32 + half * 16;
           const uint2 lo = *reinterpret_cast<const uint2*>(src), hi = *reinterpret_cast<const uint2*>(src + 8);
-          af[p][i] = __builtin_bit_cast(wg_bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y));
+          af[p][i] = __builtin_bit_cast(bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y));
         }
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           const unsigned char* src = Gt + p * WB_PLANE + (bn[j] * 32 + r31) * WB_ROW + kb * 32 + half * 16;
           const uint2 lo = *reinterpret_cast<const uint2*>(src), hi = *reinterpret_cast<const uint2*>(src + 8);
-          bf[p][j] = __builtin_bit_cast(wg_bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y));
+          bf[p][j] = __builtin_bit_cast(bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y));
         }
       }
 #pragma unroll
@@ -393,12 +378,7 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_bf(WgradArgs a) {
 #pragma unroll
         for (int j = 0; j < 2; ++j)
           if (sub_on[i][j]) {                          // smallest terms first (planes: 0 = h, 1 = m, 2 = l)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[2][i], bf[0][j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[2][j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][i], bf[1][j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][i], bf[0][j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[1][j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[0][j], acc[i][j], 0, 0, 0);
+            acc[i][j] = bf6_terms(af[0][i], af[1][i], af[2][i], bf[0][j], bf[1][j], bf[2][j], acc[i][j]);
           }
     }
   };
@@ -482,7 +462,7 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_bf(WgradArgs a) {
       const int co = n0 + bn[j] * 32 + r31;
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int ci = m0 + bm[i] * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
+        const int ci = cfrag_row(m0 + bm[i] * 32, e, half);
         if (ci < a.cin && co < a.cout) dst[(long long)ci * a.cout + co] = acc[i][j][e];
       }
     }
@@ -694,7 +674,6 @@ __global__ void __launch_bounds__(256) k_wgrad_reduce_wide(const float* __restri
 // offsets w, w + 4, ... (<= 7) of a 64-row group: their inverse-neighbour indices are read row-per-lane (one coalesced load
 // per offset) and handed to the (row, column) lanes of each 4-row MFMA step by a cross-lane read.  No LDS, no barrier.
 // ------------------------------------------------------------------------------------------
-typedef float wg_f32x4 __attribute__((ext_vector_type(4)));
 static constexpr int WS16_KPW = 7;                  // offsets per wave
 static constexpr int WS16_MAX_BLOCKS = 1024;
 
@@ -740,11 +719,11 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_self16(WgradThinArgs a) {
     spb[u] = __builtin_amdgcn_readfirstlane(sg.z);
     spc[u] = k < a.K ? __builtin_amdgcn_readfirstlane(sg.w) : 0;
   }
-  wg_f32x4 acc[WS16_KPW][NB];
+  f32x4 acc[WS16_KPW][NB];
 #pragma unroll
   for (int u = 0; u < WS16_KPW; ++u)
 #pragma unroll
-    for (int b = 0; b < NB; ++b) acc[u][b] = wg_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int b = 0; b < NB; ++b) acc[u][b] = f32x4{0.f, 0.f, 0.f, 0.f};
   constexpr int DEPTH = 4;                              // 4-row MFMA steps whose gradient rows are in flight
   for (long long r0 = lo; r0 < hi; r0 += 64) {
     const long long i = r0 + lane;                      // row-per-lane: the inverse neighbours of this wave's offsets
