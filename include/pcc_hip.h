@@ -689,6 +689,9 @@ int pcc_prof_collect(double* h_conv_ms, int64_t* h_conv_launches);
 int pcc_prof_collect_forms(double* h_ms, int64_t* h_launches, double* h_flops, double* h_bytes);
 /* forms of the timed launches recorded so far, in launch order (up to cap entries); returns their number; no reset */
 int64_t pcc_prof_sequence(int32_t* h_forms, int64_t cap);
+/* row tile, column tile and reduction split (BM, BN, ksplit as launched; 0, 0, 1 for a form without such a choice) of the same
+ * launches: h_tiles [cap][3], same order and count as pcc_prof_sequence; no reset */
+int64_t pcc_prof_sequence_tiles(int32_t* h_tiles, int64_t cap);
 
 #ifdef __cplusplus
 }

@@ -2341,13 +2341,15 @@ static size_t g_ev_used = 0;
 static int64_t g_launches = 0;
 // which kernel form a timed launch took, with the work the library itself knows (dense products: rows x columns x depth;
 // gathered forms report 0 -- their pair counts live on the device, the caller accounts them)
-struct ProfRec { int form; double flops, bytes; };
+// bm / bn / ksplit: the row tile, column tile and reduction split as launched (0, 0, 1: a form without such a choice)
+struct ProfRec { int form; double flops, bytes; int bm, bn, ksplit; };
 static std::vector<ProfRec> g_prof_recs;
-static ProfRec g_form = {PCC_FORM_OTHER, 0.0, 0.0};
-static void prof_note(int form, double flops, double bytes) { g_form = {form, flops, bytes}; }
+static ProfRec g_form = {PCC_FORM_OTHER, 0.0, 0.0, 0, 0, 1};
+static void prof_note(int form, double flops, double bytes) { g_form = {form, flops, bytes, 0, 0, 1}; }
+static void prof_tile(int bm, int bn, int ksplit) { g_form.bm = bm; g_form.bn = bn; g_form.ksplit = ksplit; }   // after prof_note
 static void prof_push() {
   g_prof_recs.push_back(g_form);
-  g_form = {PCC_FORM_OTHER, 0.0, 0.0};
+  g_form = {PCC_FORM_OTHER, 0.0, 0.0, 0, 0, 1};
   ++g_launches;
 }
 
@@ -2397,6 +2399,15 @@ extern "C" int pcc_prof_collect(double* h_conv_ms, int64_t* h_conv_launches) {
 extern "C" int64_t pcc_prof_sequence(int32_t* h_forms, int64_t cap) {
   const int64_t n = (int64_t)g_prof_recs.size();
   for (int64_t i = 0; i < n && i < cap && h_forms; ++i) h_forms[i] = g_prof_recs[(size_t)i].form;
+  return n;
+}
+
+extern "C" int64_t pcc_prof_sequence_tiles(int32_t* h_tiles, int64_t cap) {
+  const int64_t n = (int64_t)g_prof_recs.size();
+  for (int64_t i = 0; i < n && i < cap && h_tiles; ++i) {
+    const ProfRec& r = g_prof_recs[(size_t)i];
+    h_tiles[3 * i] = r.bm; h_tiles[3 * i + 1] = r.bn; h_tiles[3 * i + 2] = r.ksplit;
+  }
   return n;
 }
 
@@ -2488,6 +2499,7 @@ static int launch_mfma(const ConvArgs& a_in, int tiles_bound_extra, hipStream_t 
     a.dbg = g_dbg;
     a.nt = g_nt;
     prof_note(PCC_FORM_GEMM_H2, 2.0 * a.n_out * a.cin * a.cout, 4.0 * ((double)a.n_out * a.cin + (double)a.n_out * a.cout + (double)a.cin * a.cout));
+    prof_tile(128, 128, 1);
     return launch_gemm_h2(a, grid(128), s);
   }
   if (split && a.featb) {
@@ -2510,11 +2522,15 @@ static int launch_mfma(const ConvArgs& a_in, int tiles_bound_extra, hipStream_t 
   if (split && MODE == MODE_CONV && !a.hdr && !a.pair_in && !a.rows && !a.bias && a.act == 0 && a.ksplit == 1 &&
       bn == 128 && tiles(128) * gy >= want && (size_t)128 * a.cout * 4 < (1ull << 31)) {
     prof_note(PCC_FORM_GEMM_BF2, 2.0 * a.n_out * a.cin * a.cout, 4.0 * ((double)a.n_out * a.cin + (double)a.n_out * a.cout + (double)a.cin * a.cout));
-    if (nch_ok(a.ppo)) return launch_gemm_bf2(a, grid(128), s);
+    if (nch_ok(a.ppo)) {
+      prof_tile(128, 128, 1);
+      return launch_gemm_bf2(a, grid(128), s);
+    }
   }
   prof_note(split ? PCC_FORM_CONV_BF : PCC_FORM_CONV_F32, (!a.hdr && !a.pair_in) ? 2.0 * a.n_out * a.cin * a.cout : 0.0, 0.0);
 #define PCC_LAUNCH_MFMA(WM, WN, TM, TN, BMV)                                                     \
   do {                                                                                           \
+    prof_tile(BMV, bn, a.ksplit);                                                                \
     if (split) k_conv_mfma_bf<WM, WN, TM, TN, MODE><<<grid(BMV), 256, 0, s>>>(a);                \
     else if (buf) k_conv_mfma<WM, WN, TM, TN, MODE, true><<<grid(BMV), 256, 0, s>>>(a);          \
     else k_conv_mfma<WM, WN, TM, TN, MODE, false><<<grid(BMV), 256, 0, s>>>(a);                  \
@@ -2552,12 +2568,14 @@ static int launch_pair_product(ConvArgs& a, int K, long long tiles, hipStream_t 
   prof_note(pair_h ? PCC_FORM_PAIR_H2 : split ? PCC_FORM_PAIR_BF : PCC_FORM_CONV_F32, 0.0, 0.0);
 #define PCC_LAUNCH_PAIR(WM, WN, TM, TN)                                                         \
   do {                                                                                          \
+    prof_tile(128, bn, 1);                                                                      \
     if (split) k_conv_mfma_bf<WM, WN, TM, TN, MODE_CONV><<<grid, 256, 0, s>>>(a);               \
     else if (buf) k_conv_mfma<WM, WN, TM, TN, MODE_CONV, true><<<grid, 256, 0, s>>>(a);         \
     else k_conv_mfma<WM, WN, TM, TN, MODE_CONV, false><<<grid, 256, 0, s>>>(a);                 \
   } while (0)
   if (pair_h) {                                   // scaled fp16 pairs, three MFMA terms (k_pair_h2)
     PCC_TRY(make_planes_h(a, s));
+    prof_tile(128, 128, 1);
     PCC_TRY(launch_pair_h2(a, grid, s));
   } else {
     if (split) PCC_TRY(make_planes(a, false, s));
@@ -2585,6 +2603,7 @@ static int launch_wave16(const Wave16Args& a, hipStream_t s) {
     attr_set |= 1ull << (dev & 63);
   }
   prof_note(PCC_FORM_WAVE16, 0.0, 0.0);
+  prof_tile(32, 16, 1);
   const long long tiles = pcc_cdiv(a.n_out, 32) + (a.rows ? PCC_MAP_MAX_SEG : 0);
   long long want = pcc_cdiv(tiles, 8);
   want = (want + 7) / 8 * 8;                                     // multiple of 8: one contiguous tile range per XCD
@@ -2716,6 +2735,7 @@ extern "C" int pcc_conv_fwd(const float* feat_in, int64_t n_in, int32_t cin, con
       const long long gy = a.cout_pad / 128;
       const unsigned grid = (unsigned)((pcc_cdiv(n_out, 128) * gy + 7) / 8 * 8);
       prof_note(PCC_FORM_CONV_BF, 0.0, 0.0);
+      prof_tile(128, 128, 1);
       k_conv_in4_bf<2><<<grid, 256, 0, s>>>(a, (const unsigned*)wpl, K);
       PCC_LAUNCH_CHECK();
     } else

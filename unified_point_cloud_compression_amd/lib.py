@@ -160,6 +160,7 @@ SIGNATURES = {
     "pcc_prof_enable": (C.c_int, [_i32]),
     "pcc_prof_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(_i64)]),
     "pcc_prof_sequence": (_i64, [C.POINTER(_i32), _i64]),
+    "pcc_prof_sequence_tiles": (_i64, [C.POINTER(_i32), _i64]),
     "pcc_prof_collect_forms": (C.c_int, [C.POINTER(C.c_double), C.POINTER(_i64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 
