@@ -9,8 +9,10 @@ two builds are compared in
   - the `llvm-objdump -d` instruction text and encodings (addresses dropped: a kernel may sit elsewhere in its object), and
   - .vgpr_count, .sgpr_count, .agpr_count, .private_segment_fixed_size, .group_segment_fixed_size, .kernarg_segment_size
     of the `llvm-readelf --notes` metadata.
-Device functions (code symbols without a kernel descriptor) are listed and compared the same way.  Exit status 0 when the
-kernel names are the same set and every kernel is identical, 1 otherwise.
+Device functions (code symbols without a kernel descriptor) are listed and compared the same way.  A kernel found in more than
+one object file of a build (a template kernel launched from two sources is compiled twice) is counted and named for each build.
+Exit status 0 when the kernel names are the same set, every kernel is identical and no kernel of the new build sits in more than
+one object file, 1 otherwise.
 """
 import argparse
 import difflib
@@ -83,8 +85,9 @@ def metadata(co, llvm):
 
 
 def load(csrc, arch, llvm):
-    """kernels {name: (object, instructions, fields)}, device functions {name: (object, instructions)}, objects without code"""
-    kernels, funcs, empty = {}, {}, []
+    """kernels {name: (object, instructions, fields)}, device functions {name: (object, instructions)}, objects without code,
+    {kernel name: [objects]} of the kernels found in more than one object file"""
+    kernels, funcs, empty, where = {}, {}, [], {}
     with tempfile.TemporaryDirectory() as tmp:
         for obj in sorted(glob.glob(os.path.join(csrc, "*.o"))):
             base = os.path.basename(obj)
@@ -97,10 +100,11 @@ def load(csrc, arch, llvm):
                 if name in meta:
                     if name in kernels and kernels[name][1:] != (ins, {f: meta[name].get(f) for f in FIELDS}):
                         sys.exit("%s: kernel %s differs between %s and %s of the same build" % (csrc, name, kernels[name][0], base))
-                    kernels[name] = (base, ins, {f: meta[name].get(f) for f in FIELDS})
+                    kernels.setdefault(name, (base, ins, {f: meta[name].get(f) for f in FIELDS}))
+                    where.setdefault(name, []).append(base)
                 else:
                     funcs[name] = (base, ins)
-    return kernels, funcs, empty
+    return kernels, funcs, empty, {n: objs for n, objs in where.items() if len(objs) > 1}
 
 
 def demangle(names, llvm):
@@ -124,8 +128,8 @@ def main():
     ap.add_argument("--llvm", default="/opt/rocm/llvm/bin")
     ap.add_argument("--diff", type=int, default=20, help="lines of instruction diff printed per differing kernel")
     args = ap.parse_args()
-    pk, pf, pe = load(args.parent_csrc, args.arch, args.llvm)
-    nk, nf, ne = load(args.new_csrc, args.arch, args.llvm)
+    pk, pf, pe, pdup = load(args.parent_csrc, args.arch, args.llvm)
+    nk, nf, ne, ndup = load(args.new_csrc, args.arch, args.llvm)
     dm = demangle(sorted(set(pk) | set(nk) | set(pf) | set(nf)), args.llvm)
 
     print("Kernel identity, parent build against new build: the %s code object of every csrc/*.o unbundled, kernels keyed by mangled"
@@ -138,6 +142,10 @@ def main():
         print(title + ":" + ("" if names else " none"))
         for n in names:
             print("  %s: %s" % (src[n][0], dm.get(n, n)))
+    for title, dup in (("parent", pdup), ("new", ndup)):
+        print("kernels in more than one object file of the %s build: %d" % (title, len(dup)))
+        for n in sorted(dup):
+            print("  %s: %s" % (", ".join(dup[n]), dm.get(n, n)))
     moved = sorted(n for n in set(pk) & set(nk) if pk[n][0] != nk[n][0])
     print("kernels in another object file than in the parent: %d" % len(moved))
     routes = {}
@@ -179,7 +187,7 @@ def main():
     common = len(set(pk) & set(nk))
     print("%d of %d surviving kernels identical (instruction text and encodings, %s)"
           % (common - len(differing), common, ", ".join(FIELDS)))
-    ok = not differing and set(pk) == set(nk) and not fbad
+    ok = not differing and set(pk) == set(nk) and not fbad and not ndup
     return 0 if ok else 1
 
 

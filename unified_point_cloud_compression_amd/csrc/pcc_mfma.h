@@ -35,7 +35,7 @@ __device__ __forceinline__ int cfrag_row(int base, int e, int half) { return bas
 
 __device__ __forceinline__ f32x16 acc_zero() { return f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; }
 
-// ---- exact split of fp32 into three bf16 planes, x = h + m + l (pcc_conv.hip, "split" path) ------------------
+// ---- exact split of fp32 into three bf16 planes, x = h + m + l (pcc_conv_bf.hip, "split" path) ---------------
 __host__ __device__ inline long long bf_plane_elems(long long fp32_elems) { return fp32_elems / 2 * 3; }   // floats holding 3 bf16 planes
 
 __device__ __forceinline__ void bf_split2(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
