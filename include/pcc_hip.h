@@ -666,6 +666,71 @@ int pcc_aug_batch(const float* points, const float* colors, int64_t table_rows, 
                   int32_t* out_coords, float* out_feats, int64_t out_rows, int32_t* d_outside, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 10   PLY vertex bodies (reference evaluate.py:30-37,105 and data/utils/RawLoader.py:47 read ASCII PLY frames;
+ *      utils.py:503 save_ply and model/model.py:409 write them).  The header is parsed and written by the caller
+ *      (ply.py); these entry points see the body bytes only, uploaded on their own so that their base is aligned.
+ * ---------------------------------------------------------------------------------------- */
+#define PCC_PLY_MAX_PROPS 32      /* vertex properties of a file, and selected properties of a call */
+#define PCC_PLY_TILE_BYTES 4096   /* body bytes per workgroup of the token passes */
+#define PCC_PLY_STAGE_BYTES 16384 /* most body bytes a workgroup of the binary reader stages in LDS */
+#define PCC_PLY_TOKEN_MAX 40      /* longest token the device converts */
+#define PCC_PLY_I8 0
+#define PCC_PLY_U8 1
+#define PCC_PLY_I16 2
+#define PCC_PLY_U16 3
+#define PCC_PLY_I32 4
+#define PCC_PLY_U32 5
+#define PCC_PLY_F32 6
+#define PCC_PLY_F64 7
+/* Property table of the two readers: h_table [nsel][5] int32 on the HOST = (where, type PCC_PLY_*, destination array,
+ * destination column, colour scale 0/1) per selected property; `where` is the byte offset in a record (binary) or the
+ * property's index in the vertex element (ASCII).  Destination arrays: 0 = cloud [n, cloud_cols] row-major (3 or 6
+ * columns), 1 = normals [n,3] row-major (nullable), 2 = extra [extra_cols][n], one contiguous run per column.  Integer types
+ * and double convert to fp32 round-to-nearest; with the colour scale (uchar only) the value is the fp32 quotient k / 255.
+ * The table is validated before any launch (fields inside the record, columns inside their arrays, no destination twice):
+ * PCC_EINVAL otherwise; it reaches the kernels by value. */
+/* records per workgroup of the binary reader for this record size (0: unsupported size) */
+int32_t pcc_ply_block_records(int32_t stride);
+/* evaluate.py:30-37 for binary files: n records of `stride` bytes from body (16-byte aligned; n * stride <= body_bytes or
+ * PCC_EINVAL), fields at any byte offset, either endianness.  n = 0 launches nothing. */
+int pcc_ply_unpack_binary(const uint8_t* body, int64_t body_bytes, int64_t n, int32_t stride, const int32_t* h_table, int32_t nsel,
+                          int32_t big_endian, float* cloud, int32_t cloud_cols, float* normals, float* extra, int32_t extra_cols,
+                          void* stream);
+/* bytes per tile of pcc_ply_count_tokens (PCC_PLY_TILE_BYTES) */
+int32_t pcc_ply_tile_bytes(void);
+/* evaluate.py:30-37 / RawLoader.py:47, pass 1: a token starts at a byte that is not whitespace (blank, \t, \r, \n) and whose
+ * predecessor is whitespace or the start of the body; tile_counts [ceil(body_bytes / tile)] = token starts per tile.  The
+ * caller scans them (exclusive) into tile_base. */
+int pcc_ply_count_tokens(const uint8_t* body, int64_t body_bytes, int32_t* tile_counts, void* stream);
+/* pass 2: token t is property t % nprops of vertex t / nprops; tokens from n * nprops on (face data) are ignored, so are
+ * unselected properties.  starts [n * nprops] int32 is scratch (the byte offset of every token).  Integer-typed properties
+ * are read exactly ([+-]digits; a decimal point or an exponent there, or a value outside the type, is an error); float-typed
+ * ones take sign, digits, optional point, optional exponent, and are converted when that is exact arithmetic: at most 15
+ * significant digits and a power of ten within +-22 make m * 10^e (or m / 10^e) one correctly rounded fp64 operation, then
+ * rounded to fp32 -- the bits of float32(float(token)).  Anything else is not guessed: a longer significand, a larger
+ * exponent, a token over PCC_PLY_TOKEN_MAX bytes, nan / inf go to fallback [fallback_cap][2] int64 = (token ordinal, byte
+ * offset) for the host to convert.  status [4] int64 (device): [0] tokens in the body, [1] fallback tokens met (more than
+ * fallback_cap: the list overflowed), [2] -1 or (ordinal << 32 | byte offset) of the first token that is no number.
+ * A body with fewer than n * nprops tokens converts what it has; the caller sees status[0].  Every read is bounded by
+ * body_bytes. */
+int pcc_ply_parse_ascii(const uint8_t* body, int64_t body_bytes, int64_t n, int32_t nprops, const int32_t* h_table, int32_t nsel,
+                        const int32_t* tile_base, int32_t* starts, float* cloud, int32_t cloud_cols, float* normals, float* extra,
+                        int32_t extra_cols, int64_t* status, int64_t* fallback, int32_t fallback_cap, void* stream);
+/* utils.py:503 save_ply as a binary little-endian body: records x y z [nx ny nz] [r g b] from cloud [n, 3|6] (and normals
+ * [n,3], nullable); coordinates as fp32 or (coords_int) int32, colours as uchar clamp(rint(255 f), 0, 255), the rule of
+ * pcc_decode_finish.  *d_flag (device int32, zeroed here) is set when coords_int meets a coordinate that is not an integer
+ * of int32 range.  out: 16-byte aligned, out_bytes >= n * record size. */
+int pcc_ply_pack_binary(const float* cloud, int32_t cloud_cols, const float* normals, int64_t n, int32_t coords_int, uint8_t* out,
+                        int64_t out_bytes, int32_t* d_flag, void* stream);
+/* utils.py:503 / model/model.py:409 as text, pass 1: lengths[i] = bytes of line i, "x y z[ r g b]\n" with integer
+ * coordinates and 8-bit colour levels; *d_flag (zeroed here) is set when a coordinate is not an integer of int32 range. */
+int pcc_ply_row_lengths(const float* cloud, int32_t cloud_cols, int64_t n, int32_t* lengths, int32_t* d_flag, void* stream);
+/* pass 2: the characters.  row_offsets [n + 1] int64 = the caller's exclusive scan of the lengths (last entry: the body's
+ * size); a row whose offsets do not hold its text, or lie outside out_bytes, is not written. */
+int pcc_ply_format_ascii(const float* cloud, int32_t cloud_cols, int64_t n, const int64_t* row_offsets, uint8_t* out, int64_t out_bytes,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * measurement support: per-launch HIP-event timing of the conv kernel (bench.py roofline)
  * ---------------------------------------------------------------------------------------- */
 int pcc_prof_enable(int32_t on);

@@ -9,10 +9,20 @@ Layout
   model/                  UnifiedModel.compress()/decompress() counterpart of the reference's model/
   data.py                 training batches: cube slicing, colour jitter, rotation, collation on the GPU (reference data/)
   frames.py               frame/block sharding across GPUs (one process per GPU, RCCL gather)
+  ply.py                  PLY point clouds in and out: header in Python, body converted on the GPU
 """
 import sys
 
-__all__ = ["install_shims"]
+__all__ = ["install_shims", "ply", "read_ply", "read_ply_header", "write_ply", "PlyHeader", "PlyCloud"]
+
+
+def __getattr__(name):
+    """`ply` and its entry points, imported on first use (ply.py imports torch; `import package` alone does not)."""
+    if name in __all__[1:]:
+        import importlib
+        mod = importlib.import_module(".ply", __name__)
+        return mod if name == "ply" else getattr(mod, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def install_shims(force=False):

@@ -157,6 +157,14 @@ SIGNATURES = {
     "pcc_cube_regroup": (C.c_int, [_p, _p, _p, _i64, _p, _p, _p]),
     "pcc_aug_gray_sums": (C.c_int, [_p, _i64, _p, _p, _i32, _p, _p, _i32, _p, _p, _p]),
     "pcc_aug_batch": (C.c_int, [_p, _p, _i64, _p, _p, _i32, _p, _p, _i32, _p, _p, _p, _i64, _p, _p]),
+    "pcc_ply_block_records": (_i32, [_i32]),
+    "pcc_ply_unpack_binary": (C.c_int, [_p, _i64, _i64, _i32, C.POINTER(_i32), _i32, _i32, _p, _i32, _p, _p, _i32, _p]),
+    "pcc_ply_tile_bytes": (_i32, []),
+    "pcc_ply_count_tokens": (C.c_int, [_p, _i64, _p, _p]),
+    "pcc_ply_parse_ascii": (C.c_int, [_p, _i64, _i64, _i32, C.POINTER(_i32), _i32, _p, _p, _p, _i32, _p, _p, _i32, _p, _p, _i32, _p]),
+    "pcc_ply_pack_binary": (C.c_int, [_p, _i32, _p, _i64, _i32, _p, _i64, _p, _p]),
+    "pcc_ply_row_lengths": (C.c_int, [_p, _i32, _i64, _p, _p, _p]),
+    "pcc_ply_format_ascii": (C.c_int, [_p, _i32, _i64, _p, _p, _i64, _p]),
     "pcc_prof_enable": (C.c_int, [_i32]),
     "pcc_prof_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(_i64)]),
     "pcc_prof_sequence": (_i64, [C.POINTER(_i32), _i64]),
