@@ -731,6 +731,36 @@ int pcc_ply_format_ascii(const float* cloud, int32_t cloud_cols, int64_t n, cons
                          void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 11   voxel-grid down-sampling with averaged attributes (reference data/utils/RawLoader.py:48-57: Open3D's
+ *      voxel_down_sample(factor), then the division by the factor and the rounding).
+ * ---------------------------------------------------------------------------------------- */
+#define PCC_VOXEL_MAX_ATTRS 32    /* attribute columns averaged beside the point */
+#define PCC_VOXEL_WAVE_RUN 32     /* a run of this many rows or more is summed by a whole wave, a shorter one by four lanes */
+#define PCC_VOXEL_SPLIT_RUN 2048  /* a run of this many rows or more is summed by several workgroups into fp64 partials */
+#define PCC_VOXEL_TILE_ROWS 1024  /* sorted rows per workgroup of that split pass */
+/* Per point of [n,3] fp32 and per axis idx = floor(((double)p - origin) / voxel_size): one fp64 subtraction and one true
+ * fp64 division (no reciprocal), so a float64 restatement gives the same integer.  keys[i] = the three indices, each biased
+ * by 2^15 into a 16-bit field, x most significant (the layout of pcc_cube_keys: integer order is (ix, iy, iz) order).
+ * *d_bad (device int32, zeroed here) != 0 when a point is not finite or an index lies outside [-2^15, 2^15).  PCC_EINVAL,
+ * before anything is launched, unless 0 <= n < 2^31 and voxel_size and the origin are finite, voxel_size > 0. */
+int pcc_voxel_keys(const float* points, int64_t n, double origin_x, double origin_y, double origin_z, double voxel_size,
+                   int64_t* keys, int32_t* d_bad, void* stream);
+/* Means per run of equal keys.  perm: the permutation of pcc_sort_keys over those keys; uniq_keys / first / *d_count: what
+ * pcc_unique_sorted made of the sorted keys (the count stays on the device: the grids are sized for n runs).  For every run
+ * r < *d_count: counts[r], index[r] = the three unbiased fields of uniq_keys[r], mean_points[r] and mean_attrs[r] = the mean
+ * over the run's rows of points [n,3] and of attrs [n,c] fp32 (0 <= c <= PCC_VOXEL_MAX_ATTRS; c = 0: both attribute
+ * pointers may be NULL).  Outputs hold n rows; rows from *d_count on are not written.  Every sum is fp64, the mean one fp64
+ * division rounded once to fp32; no floating-point atomics, and the order of the additions depends on n and the run
+ * layout only: equal inputs give equal bits.  Runs below PCC_VOXEL_WAVE_RUN rows share a wave sixteen at a time, longer ones
+ * take a whole wave each, runs of PCC_VOXEL_SPLIT_RUN rows or more are summed tile by tile into ws (fp64 partials) by a
+ * first launch and added in tile order.  Every index read from perm / first is checked against n before it is used. */
+size_t pcc_voxel_means_ws_bytes(int64_t n, int32_t c);
+int pcc_voxel_means(const float* points, const float* attrs /*nullable*/, int32_t c, int64_t n, const int32_t* perm,
+                    const int64_t* uniq_keys, const int32_t* first, const int64_t* d_count, int32_t* index /*[n,3]*/,
+                    int32_t* counts /*[n]*/, float* mean_points /*[n,3]*/, float* mean_attrs /*[n,c], nullable*/, void* ws,
+                    size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * measurement support: per-launch HIP-event timing of the conv kernel (bench.py roofline)
  * ---------------------------------------------------------------------------------------- */
 int pcc_prof_enable(int32_t on);

@@ -10,6 +10,7 @@ Layout
   data.py                 training batches: cube slicing, colour jitter, rotation, collation on the GPU (reference data/)
   frames.py               frame/block sharding across GPUs (one process per GPU, RCCL gather)
   ply.py                  PLY point clouds in and out: header in Python, body converted on the GPU
+  voxelize.py             voxel-grid down-sampling with averaged attributes (Open3D's voxel_down_sample), reproducible bits
 """
 import sys
 

@@ -165,6 +165,9 @@ SIGNATURES = {
     "pcc_ply_pack_binary": (C.c_int, [_p, _i32, _p, _i64, _i32, _p, _i64, _p, _p]),
     "pcc_ply_row_lengths": (C.c_int, [_p, _i32, _i64, _p, _p, _p]),
     "pcc_ply_format_ascii": (C.c_int, [_p, _i32, _i64, _p, _p, _i64, _p]),
+    "pcc_voxel_keys": (C.c_int, [_p, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p, _p]),
+    "pcc_voxel_means_ws_bytes": (_sz, [_i64, _i32]),
+    "pcc_voxel_means": (C.c_int, [_p, _p, _i32, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "pcc_prof_enable": (C.c_int, [_i32]),
     "pcc_prof_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(_i64)]),
     "pcc_prof_sequence": (_i64, [C.POINTER(_i32), _i64]),
