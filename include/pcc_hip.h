@@ -592,6 +592,48 @@ int pcc_octree_decode_host(const uint8_t* h_data, int64_t nbytes, int32_t* h_cel
                            int32_t* h_depth);
 
 /* ------------------------------------------------------------------------------------------
+ * 8f-3b lossless geometry of a whole block on the device: a breadth-first octree whose levels are the
+ *       voxel set's own stride chain, in origin-relative cells 0 <= x, y, z < 2^15 (single batch).  A node's symbol is its
+ *       child-occupancy byte 1..255, bit j = child (dx, dy, dz) with j = dx<<2 | dy<<1 | dz (ascending key order); its context
+ *       is the 6-bit pattern of face neighbours present in the node's own level (bit 0/1: -x/+x, 2/3: -y/+y, 4/5: -z/+z).
+ *       The symbols travel through pcc_rans_encode_streams / pcc_rans_decode_streams as an [nodes, 1] matrix, idx = context.
+ *       None of these reads a bitstream; symbols outside 1..255 set *d_bad (device int32, zeroed by the caller) and count as 1.
+ * pcc_geom_occ_ctx       ctx[i] (and, with sym non-NULL, the byte sym[i]) of every node of a canonical level at `pitch`.
+ *                        bits / rank / h_grid: the level's grid index (pcc_grid_build layout, pitch h_grid[6] == pitch), or NULL:
+ *                        binary search over keys.  child_*: the canonical set at pitch / 2 and its grid index (or NULL), needed
+ *                        for the bytes only.
+ * pcc_geom_hist          hist[pcc_geom_hist_words() = 64 * 256 + 8] (uint32, zeroed here): hist[ctx * 256 + byte] counts, then
+ *                        the popcount histogram (entry k: nodes with k + 1 children).  Integer atomics, reduced in LDS per
+ *                        workgroup first: the sums do not depend on arrival order.
+ * pcc_geom_child_offsets off[n + 1] = exclusive scan of the nodes' child counts (off[n] = *d_total, device int64): the host
+ *                        compares the total with the stream header before anything is sized by it.  n < 2^27.
+ *                        ws: pcc_geom_offsets_ws_bytes(n); a short buffer returns PCC_EWS.
+ * pcc_geom_expand        out_keys[off[i] + r] = key of the r-th child of node i (child pitch = node pitch / 2), parent-major;
+ *                        writes at or past `cap` (>= n) are dropped.  Canonical order: pcc_keys_canonicalize_grid / pcc_sort_keys.
+ * pcc_geom_finish        cell keys + origin -> absolute keys (nullable) and int32 [n, 3] rows (x, y, z) (nullable).
+ * pcc_geom_tables        the decoder's tables of one level without a host round trip: from the adaptive counts state[64 * 256]
+ *                        (uint64, device) and the level's popcount histogram h_pop[8] (HOST, from the stream header), the integer
+ *                        rule of DESIGN.md 7e -> cdf int32 [64, 257] and the decoder table blob of pcc_rans_build_dec_table
+ *                        (pcc_geom_dec_table_bytes() bytes, its padding zeroed by the caller), both on the device.
+ * pcc_geom_state_update  state = (state >> 1) + hist (the first 64 * 256 words of a pcc_geom_hist result).
+ * ---------------------------------------------------------------------------------------- */
+int pcc_geom_occ_ctx(const int64_t* keys, int64_t n, int32_t pitch, const uint64_t* bits, const int32_t* rank,
+                     const int32_t* h_grid, const int64_t* child_keys, int64_t n_child, const uint64_t* child_bits,
+                     const int32_t* child_rank, const int32_t* h_child, int32_t* sym /*nullable*/, int32_t* ctx, void* stream);
+int32_t pcc_geom_hist_words(void);
+int pcc_geom_hist(const int32_t* sym, const int32_t* ctx, int64_t n, uint32_t* hist, int32_t* d_bad, void* stream);
+size_t pcc_geom_offsets_ws_bytes(int64_t n);
+int pcc_geom_child_offsets(const int32_t* sym, int64_t n, int32_t* off /*[n+1]*/, int64_t* d_total, int32_t* d_bad, void* ws,
+                           size_t ws_bytes, void* stream);
+int pcc_geom_expand(const int64_t* keys, const int32_t* sym, const int32_t* off, int64_t n, int32_t child_pitch,
+                    int64_t* out_keys, int64_t cap, void* stream);
+int pcc_geom_finish(const int64_t* keys, int64_t n, int32_t ox, int32_t oy, int32_t oz, int64_t* out_keys /*nullable*/,
+                    int32_t* out_xyz /*nullable [n,3]*/, void* stream);
+int64_t pcc_geom_dec_table_bytes(void);
+int pcc_geom_tables(const uint64_t* state, const uint32_t* h_pop, int32_t* cdf, void* dec_table, void* stream);
+int pcc_geom_state_update(uint64_t* state, const uint32_t* hist, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * 8f-4  nearest-neighbour association of the distortion report (replaces the two Open3D KD-trees and the per-point
  *       Python loop of PointCloudMetric.__init__, metrics/metric.py:36-43).  Exact, integer coordinates.
  *       a_xyz [n_a,3] int32 queries (any order; canonical order is fastest); b_xyz [n_b,3] int32 SORTED BY x ascending

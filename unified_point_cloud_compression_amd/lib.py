@@ -145,6 +145,16 @@ SIGNATURES = {
     "pcc_octree_max_bytes": (_i64, [_i64, _i32]),
     "pcc_octree_encode_host": (C.c_int, [_p, _i64, _i32, _p, _i64, C.POINTER(_i64)]),
     "pcc_octree_decode_host": (C.c_int, [_p, _i64, _p, _i64, C.POINTER(_i64), C.POINTER(_i32)]),
+    "pcc_geom_occ_ctx": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p]),
+    "pcc_geom_hist_words": (_i32, []),
+    "pcc_geom_hist": (C.c_int, [_p, _p, _i64, _p, _p, _p]),
+    "pcc_geom_offsets_ws_bytes": (_sz, [_i64]),
+    "pcc_geom_child_offsets": (C.c_int, [_p, _i64, _p, _p, _p, _p, _sz, _p]),
+    "pcc_geom_expand": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _i64, _p]),
+    "pcc_geom_finish": (C.c_int, [_p, _i64, _i32, _i32, _i32, _p, _p, _p]),
+    "pcc_geom_dec_table_bytes": (_i64, []),
+    "pcc_geom_tables": (C.c_int, [_p, C.POINTER(C.c_uint32), _p, _p, _p]),
+    "pcc_geom_state_update": (C.c_int, [_p, _p, _p]),
     "pcc_conv_pairs_supported": (C.c_int, [_i32, _i32, _i32]),
     "pcc_pair_plan_ws_bytes": (_sz, [_i64, _i32]),
     "pcc_pair_plan_rank": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _sz, _p]),

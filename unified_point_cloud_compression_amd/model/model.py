@@ -97,24 +97,27 @@ class UnifiedModel(CompressionModel):
         return out
 
     @torch.no_grad()
-    def compress_block(self, x_block, q, coords=None):
+    def compress_block(self, x_block, q, coords=None, sets=None):
         """One block through g_a and the entropy model: (strings, shape, k, latent coordinates) -- the body of the block loop
         of `compress` (`model/model.py:137-176`).  The matrix products of g_a and h_a run in the three-term fp16 form under
         its range guard: should a layer's operands leave the range the form's error bound covers, THIS
         block is coded again with those products in the six-term 24-bit form.  The hyper-synthesis never changes form (its
-        scope is pinned, `MeanScaleHyperprior._gaussian_params`): the decoder reproduces its bits whatever happened here."""
+        scope is pinned, `MeanScaleHyperprior._gaussian_params`): the decoder reproduces its bits whatever happened here.
+        sets (list): receives the block's input coordinate set (`compress_lossless_geometry` codes it)."""
         try:
-            return self._compress_block(x_block, q, coords)
+            return self._compress_block(x_block, q, coords, sets)
         except L.RangeGuardTripped:
             with L.arith_scope(L.ARITH_BF6):
-                return self._compress_block(x_block, q, coords)
+                return self._compress_block(x_block, q, coords, sets)
 
-    def _compress_block(self, x_block, q, coords=None):
+    def _compress_block(self, x_block, q, coords=None, sets=None):
         if isinstance(coords, tuple):                       # (FrameRows, features): the frame went through `frame_intake`
             coords[0]._pcc_chain = self.stride_chain()
             x = SparseTensor._from_frame(x_block, coords[0], coords[1])
         else:
             x = self.block_input(x_block, coords=coords)
+        if sets is not None:
+            sets.append(x._cset)
         y, k = self.g_a(x)
         _, symbols, shape = self.entropy_model.compress(y, q)
         return symbols, shape, k, y.C
@@ -231,6 +234,69 @@ class UnifiedModel(CompressionModel):
             guard.zero_()
             with L.arith_scope(L.ARITH_BF6):
                 blocks = [self.g_s(y_hat, k=block_k, trace=trace, probe=probe) for y_hat, block_k in latents]
+            out = self._finish(blocks, device)
+        return out
+
+    # ---- lossless geometry, lossy colour: the voxels travel in a geometry stream of their own ---------
+    @torch.no_grad()
+    def compress_lossless_geometry(self, pointcloud, q, block_size=1024):
+        """-> (strings, shapes, geometry, q_vals), one entry per block of `partition`: the latents' strings as `compress` codes
+        them and `geometry[i]` = `encode_geometry` of the block's input set.  Neither k nor the latent coordinates are
+        returned: `decompress_lossless_geometry` derives both from the decoded voxels."""
+        from ..geometry import encode_geometry
+        if not pointcloud.is_cuda:
+            raise L.PccError("compress_lossless_geometry expects the point cloud on the GPU")
+        strings, shapes, geometry, q_vals = [], [], [], []
+        for x_block in self.blocks_of(pointcloud, block_size):
+            sets = []
+            symbols, shape, _, _ = self.compress_block(x_block, q, sets=sets)
+            strings.append(symbols)
+            shapes.append(shape)
+            geometry.append(encode_geometry(sets[-1]))
+            q_vals.append(q)
+        return strings, shapes, geometry, q_vals
+
+    @torch.no_grad()
+    def decompress_lossless_geometry(self, strings, shape, geometry, q_vals):
+        """-> [N, 6]: per block its unique input voxels in canonical order with the decoded colours.  The voxel set is
+        decoded, its stride-2, -4, -8 (y's) and -32 (z's) sets are taken from it, the entropy model runs exactly as in
+        `decompress`, and the synthesis runs at the given geometry (`SparseSynthesisTransform.forward_at`) under the same
+        range guard: when it trips, g_s alone is evaluated again in the six-term form."""
+        from ..geometry import decode_geometry, parse_header
+        device = self.g_s.down_conv.kernel.device
+        status, blocks, latents = [], [], []
+        for i, (block_symbols, block_shape, geom) in enumerate(zip(strings, shape, geometry)):
+            # (the stride-32 set cannot have more rows than there are voxels: a shape that says otherwise is refused before
+            #  anything is sized by it; the exact count is checked once the sets exist)
+            n_vox = parse_header(geom)["n"]
+            if not 0 <= int(block_shape[0]) <= n_vox:
+                raise L.PccError(f"bitstream says {int(block_shape[0])} hyper-latent rows for {n_vox} voxels")
+            pre = self.entropy_model.predecode(block_symbols, block_shape, device, check=status)
+            x_cset = decode_geometry(geom, device, as_set=True)
+            chain = x_cset.stride_chain_begin((2, 4, 8, 32))
+            if chain is not None:
+                S.resolve(chain)
+            s2 = x_cset.stride(2)
+            s4 = s2.stride(4)
+            y_cset = s4.stride(8)
+            z_cset = y_cset.stride(32)
+            if z_cset.n != int(block_shape[0]):
+                raise L.PccError(f"bitstream says {int(block_shape[0])} hyper-latent rows, the geometry gives {z_cset.n}")
+            self.entropy_model.plan_synthesis(z_cset, y_cset)
+            pre = self.entropy_model.predecode_upload(pre, block_symbols, device)
+            y_hat = self.entropy_model.decompress([y_cset, z_cset], block_symbols, block_shape, q_vals[i], check=status, pre=pre)
+            sets = (s4, s2, x_cset)
+            blocks.append(self.g_s.forward_at(y_hat, sets))
+            latents.append((y_hat, sets))
+        out = self._finish(blocks, device)
+        guard = L.h_guard(device)
+        flags = torch.cat([s.reshape(-1)[:1].to(torch.int32) for s in status] + [guard]).tolist()   # one deferred read: rANS containers + range guard
+        if any(flags[:-1]):
+            raise L.PccError("malformed rANS container in the bitstream")
+        if flags[-1] and L.arith() == L.ARITH_H3:
+            guard.zero_()
+            with L.arith_scope(L.ARITH_BF6):
+                blocks = [self.g_s.forward_at(y_hat, sets) for y_hat, sets in latents]
             out = self._finish(blocks, device)
         return out
 

@@ -262,16 +262,22 @@ class SparseSynthesisTransform(nn.Module):
             ok = out_set.n >= self.FUSE_NARROW_MIN_RATIO * cs.n
         return ok
 
-    def plan(self, cs):
-        """Coordinate-only work of the first level that depends on y's coordinates alone: the 5x5x5 map + pair list of
-        `up_1[0]` and the candidate set of `up_1`'s generative convolution.  Returns Pendings for the caller to resolve
-        together with whatever else it is waiting for (`UnifiedModel.decompress`: the hyper-latent's coordinate set)."""
+    def _plan_leading(self, cs):
+        """Kernel maps and pair plans of `up_1`'s leading stride-1 convolutions over y's set (shared by `plan` and
+        `forward_at`); returns the pair plans' Pendings."""
         pend = []
         for m in list(self.up_1)[:-1]:
             if isinstance(m, ME.MinkowskiConvolution) and m.stride == 1 and m.kernel_volume > 1:
                 kmap = cs.kernel_map(cs, m.kernel_size)
                 if S.wants_pairs(m.kernel_volume, m.in_channels, m.out_channels):
                     pend.append(kmap.pair_plan_begin())
+        return pend
+
+    def plan(self, cs):
+        """Coordinate-only work of the first level that depends on y's coordinates alone: the 5x5x5 map + pair list of
+        `up_1[0]` and the candidate set of `up_1`'s generative convolution.  Returns Pendings for the caller to resolve
+        together with whatever else it is waiting for (`UnifiedModel.decompress`: the hyper-latent's coordinate set)."""
+        pend = self._plan_leading(cs)
         gen = self.up_1[-1]
         if isinstance(gen, ME.MinkowskiGenerativeConvolutionTranspose) and cs.ts % gen.stride == 0 and cs.n > 0:
             pend.append(cs.expand_begin(gen.kernel_size, cs.ts // gen.stride, want_csr=False))
@@ -339,6 +345,51 @@ class SparseSynthesisTransform(nn.Module):
         if probe is not None:
             probe("kept", lvl, kept, None, None, xk)
         return SparseTensor._from_canonical(kept, xk), pred, mask
+
+    @staticmethod
+    def _rows_form(gen):
+        return bool(L.load().pcc_conv_pairs_supported(125, gen.in_channels, gen.out_channels))
+
+    def forward_at(self, y, sets):
+        """y (stride 8) -> colour features at GIVEN geometry: `sets` = the stride-4, stride-2 and stride-1 CoordSets of the
+        voxels (lossless-geometry decoding).  Per level the `up` block's leading modules, then the generative transposed
+        convolution restricted to the given rows -- the tail of `_up_predict_fused`, same kernels in the same order -- then
+        `color_conv`.  No occupancy heads, no top-k; the only sizes the host reads are the pair counts the pair-GEMM's plan
+        needs, all three levels' in one read (the rows are known up front) together with `up_1`'s 5x5x5 pair list."""
+        ups = (self.up_1, self.up_2, self.up_3)
+        if len(sets) != 3:
+            raise L.PccError("forward_at takes the stride-4, stride-2 and stride-1 coordinate sets")
+        pend = self._plan_leading(y._cset) if y._cset.n > 0 else []
+        cs_in, lists = y._cset, []
+        for up, kept in zip(ups, sets):
+            gen = up[-1]
+            if not (isinstance(gen, ME.MinkowskiGenerativeConvolutionTranspose) and gen.kernel_size == 5 and gen.stride == 2
+                    and kept.ts * 2 == cs_in.ts):
+                raise L.PccError(f"forward_at: level at pitch {kept.ts} does not fit a 5x5x5 stride-2 generative convolution from pitch {cs_in.ts}")
+            total = L.counter() if (self._rows_form(gen) and kept.n > 0) else None
+            csr5 = cs_in.csr_for(kept.keys, kept.n, 5, kept.ts, total=total) if (kept.n > 0 and cs_in.n > 0) else None
+            lists.append((csr5, total))
+            pend.append(S.Pending(total, lambda v: int(v[0])) if total is not None else None)
+            cs_in = kept
+        pairs = S.resolve(*pend)[-3:]
+        x = y
+        for up, kept, (csr5, total), n_pairs in zip(ups, sets, lists, pairs):
+            for m in list(up)[:-1]:
+                x = m(x)
+            gen = up[-1]
+            feats = x._canonical_features()
+            if "_packed_conv" not in gen.__dict__:
+                gen.__dict__["_packed_conv"] = S.PackedConv(transposed=False)
+            packed = gen._packed_conv.get(gen.kernel, state_dict_order=True)
+            if csr5 is None:
+                xk = torch.zeros((kept.n, gen.out_channels), dtype=torch.float32, device=feats.device)
+            elif total is not None:
+                xk = S.convt_forward_rows(feats, packed, gen.bias, 125, gen.in_channels, gen.out_channels, csr5, kept.n, pairs_bound=n_pairs)
+            else:       # narrow shapes: slot map of the given rows + the generic convolution
+                xk = S.conv_forward(feats, packed, gen.bias, 125, gen.in_channels, gen.out_channels,
+                                    S.map_from_csr(csr5, x._cset.n, kept.n, 5), kept.n)
+            x = SparseTensor._from_canonical(kept, xk)
+        return self.color_conv(x)
 
     def forward(self, y, coords=None, k=None, trace=None, probe=None):
         """y (stride 8) -> x (stride 1) features at the k-selected voxels (`model/transforms.py:170-225`).
