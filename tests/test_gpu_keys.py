@@ -218,3 +218,41 @@ def test_batch_ranges_from_the_bounds_kernel_equal_searchsorted(batch):
     ex = cs.expand(5, 1)                                   # size read together with its ranges
     assert ex._derived.get("segments") == ref(ex)
     assert ex._derived["segments"][-1] == ex.n
+
+
+def test_stride_chain_equals_stride_link_by_link():
+    """`stride_chain_begin` (every link queued before the one read, row counts kept on the device between the links) from the
+    set's own keys and from a shuffled copy of the rows with duplicates: every link's keys, row count and grid index equal
+    what `stride()` gives link by link on a fresh set, and the links sit in the `_derived` caches the modules look them up in."""
+    S, L = _S()
+    strides = (2, 4, 8, 32)
+    C = co.unpack_keys(cloud_keys(11, 40, 0.03, 1, batch=2))
+    C[:, 1:] -= 13                                      # some negative coordinates
+    keys = np.unique(co.pack_keys(C))
+    assert 2000 < len(keys) < 10000
+    b = S.Bounds(1, C[:, 1:].min(0), C[:, 1:].max(0))
+    want, cur = [], S.CoordSet(t(keys), len(keys), 1, b)
+    for m in strides:
+        cur = cur.stride(m)
+        want.append(cur)
+    assert [w.n for w in want] == [len(np.unique(co.stride_keys(keys, m))) for m in strides]
+    rng = np.random.default_rng(5)
+    rows = rng.permutation(np.concatenate([keys, keys[rng.integers(0, len(keys), 700)]]))
+    own = S.CoordSet(t(keys), len(keys), 1, b)
+    user = S.CoordSet(t(keys), len(keys), 1, b)
+    rows_t = t(rows)
+    last_own, last_user = S.resolve(own.stride_chain_begin(strides),
+                                    user.stride_chain_begin(strides, keys=rows_t, n_keys=len(rows)))
+    for root, last in ((own, last_own), (user, last_user)):
+        cur = root
+        for m, w in zip(strides, want):
+            assert ("stride", m) in cur._derived
+            cur = cur._derived[("stride", m)]
+            assert cur.ts == m and cur.n == w.n and cur._on_lattice
+            assert torch.equal(cur.keys[:cur.n], w.keys[:w.n])
+            assert (cur.bounds.bmax, cur.bounds.lo, cur.bounds.hi) == (w.bounds.bmax, w.bounds.lo, w.bounds.hi)
+            bits, rank, h = cur.grid()
+            fresh = w.grid()
+            assert torch.equal(bits, fresh[0]) and torch.equal(rank, fresh[1]) and list(h) == list(fresh[2])
+        assert cur is last
+        assert root.stride(2) is root._derived[("stride", 2)]          # stride() finds the chain's sets: nothing is rebuilt

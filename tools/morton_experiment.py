@@ -2,6 +2,7 @@
 """Experiment: does a physical Z-curve (Morton) row order speed up the big stride-1 convolutions?
 Builds the decoder-sized candidate sets of the bench frame, times pcc_conv_fwd with rows in canonical (key) order and
 with rows + kernel map permuted into Morton order, and checks the results are the same rows."""
+import copy
 import os
 import sys
 
@@ -59,8 +60,7 @@ for name, src, ts, cin, cout in (("L2 128->64", s4, 2, 128, 64), ("L3 32->16", s
     inv[perm] = torch.arange(n, device=dev)
     d2 = dense[:, perm].long()
     d2 = torch.where(d2 >= 0, inv[d2.clamp(min=0)], d2).int().contiguous()
-    km2 = S.KernelMap()
-    km2.__dict__.update(kmap.__dict__)
+    km2 = copy.copy(kmap)
     km2.nbr = d2.view(-1)
     xm = x[perm].contiguous()
     t1 = timeit(lambda: S.conv_forward(xm, pk, None, 27, cin, cout, km2, n))

@@ -169,10 +169,6 @@ def _key_of(x, y, z):
     return ((x + S.BIAS) << 32) | ((y + S.BIAS) << 16) | (z + S.BIAS)
 
 
-def _grid_args(g):
-    return (L.ptr(g[0]), L.ptr(g[1]), g[2]) if g else (None, None, None)
-
-
 def _input_set(x):
     """Canonical, de-duplicated pitch-1 single-batch CoordSet of the input, with exact bounds."""
     if isinstance(x, S.CoordSet):
@@ -185,10 +181,9 @@ def _input_set(x):
         b = S.bounds_of(x.coords())               # a set's own bounds may be conservative; the header needs the minimum
         if b.bmax > 0:
             raise L.PccError("encode_geometry codes one block: batched input is not supported")
-        cs = S.CoordSet(x.keys, x.n, 1, b)        # a set of our own: the caller's object is not touched
+        cs = S.CoordSet(x.keys, x.n, 1, b, on_lattice=True)        # a set of our own: the caller's object is not touched
         if b.lo == x.bounds.lo and b.hi == x.bounds.hi:
-            cs._grid = x._grid                    # same lattice: its grid index is shared, read-only
-        cs._on_lattice = True
+            cs.share_grid(x)
         return cs
     if not torch.is_tensor(x) or x.dim() != 2 or x.shape[1] < 3:
         raise L.PccError("encode_geometry: an [N, >= 3] tensor or a CoordSet is required")
@@ -211,8 +206,7 @@ def _level_sets(cs, origin, depth):
         base = cs
     else:
         keys = cs.keys[:cs.n] - ((origin[0] << 32) + (origin[1] << 16) + origin[2])
-        base = S.CoordSet(keys, cs.n, 1, S.Bounds(0, (0, 0, 0), ext))
-        base._on_lattice = True
+        base = S.CoordSet(keys, cs.n, 1, S.Bounds(0, (0, 0, 0), ext), on_lattice=True)
     strides = [1 << s for s in range(1, depth)]
     if strides:
         pend = base.stride_chain_begin(strides)
@@ -275,8 +269,8 @@ def encode_geometry(x, segment_nodes=SEGMENT_NODES, timings=None):
             if timings is not None:
                 ev.append([torch.cuda.Event(enable_timing=True) for _ in range(3)])
                 ev[l][0].record()
-            L.call("pcc_geom_occ_ctx", L.ptr(node.keys), node.n, node.ts, *_grid_args(node.grid() if (l and S.USE_GRID) else None),
-                   L.ptr(child.keys), child.n, *_grid_args(child.grid() if S.USE_GRID else None), sym.data_ptr() + 4 * at[l], ctx.data_ptr() + 4 * at[l],
+            L.call("pcc_geom_occ_ctx", L.ptr(node.keys), node.n, node.ts, *S.grid_args(node.grid() if (l and S.USE_GRID) else None),
+                   L.ptr(child.keys), child.n, *S.grid_args(child.grid() if S.USE_GRID else None), sym.data_ptr() + 4 * at[l], ctx.data_ptr() + 4 * at[l],
                    L.stream())
             if timings is not None:
                 ev[l][1].record()
@@ -356,17 +350,14 @@ def _canonical_children(keys, n, pitch, depth_level, dev, counts_ptr):
     the distinct count keep the cube's corner cell, so a level decoded from a damaged stream still holds in-lattice keys only."""
     lib = L.load()
     side = 1 << depth_level
-    h = (C.c_int32 * 8)(0, 0, 0, side, side, side, pitch, 1)
-    words = lib.pcc_grid_words(h)
-    if S.USE_GRID and words < (1 << 31) and words * 12 <= S.GRID_MAX_BYTES // 4:
-        bits = torch.empty(words, dtype=torch.int64, device=dev)
-        rank = torch.empty(words, dtype=torch.int32, device=dev)
+    lat = S.Lattice((0, 0, 0), (side, side, side), pitch, 1)
+    if S.USE_GRID and lat.fits(S.GRID_MAX_BYTES // 4):
+        bits, rank, ws = lat.alloc(dev)
         out = torch.full((n,), _key_of(0, 0, 0), dtype=torch.int64, device=dev)
         first = torch.empty(n, dtype=torch.int32, device=dev)
-        ws = L.workspace(lib.pcc_grid_ws_bytes(words), dev)
-        L.call("pcc_keys_canonicalize_grid", L.ptr(keys), n, h, L.ptr(bits), L.ptr(rank), L.ptr(out), L.ptr(first), counts_ptr,
+        L.call("pcc_keys_canonicalize_grid", L.ptr(keys), n, lat.h, L.ptr(bits), L.ptr(rank), L.ptr(out), L.ptr(first), counts_ptr,
                L.ptr(ws), ws.numel(), L.stream())
-        return out, (bits, rank, h)
+        return out, S.GridIndex(bits, rank, lat.h)
     out = torch.empty(n, dtype=torch.int64, device=dev)
     mask = 0
     for sh in (32, 16, 0):
@@ -435,7 +426,7 @@ def decode_geometry(data, device, as_set=False, timings=None):
             if evs:
                 evs[0].record()
             ctx = torch.empty(m, dtype=torch.int32, device=dev)
-            L.call("pcc_geom_occ_ctx", L.ptr(keys), m, pitch, *_grid_args(grid), None, 0, None, None, None, None, L.ptr(ctx), L.stream())
+            L.call("pcc_geom_occ_ctx", L.ptr(keys), m, pitch, *S.grid_args(grid), None, 0, None, None, None, None, L.ptr(ctx), L.stream())
             if evs:
                 evs[1].record()
             if lv["raw"]:
@@ -490,6 +481,4 @@ def decode_geometry(data, device, as_set=False, timings=None):
         if not as_set:
             return xyz
         lo_hi = back[16 * depth:].reshape(2, 3).tolist()
-        cs = S.CoordSet(akeys, n, 1, S.Bounds(0, lo_hi[0], lo_hi[1]))
-        cs._on_lattice = True
-        return cs
+        return S.CoordSet(akeys, n, 1, S.Bounds(0, lo_hi[0], lo_hi[1]), on_lattice=True)

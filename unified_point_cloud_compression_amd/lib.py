@@ -288,7 +288,9 @@ def counter(n=1, dtype=torch.int64):
 
 
 def cptr(t):
-    """Pointer of a counter as a kernel argument."""
+    """Pointer of a counter as a kernel argument (None -> NULL)."""
+    if t is None:
+        return None
     if not t.is_cuda:
         raise PccError("counter() tensors only")
     return t.data_ptr()

@@ -77,8 +77,8 @@ def _set_normals(cs, radius, with_counts=False):
     normals = torch.empty((cs.n, 3), dtype=torch.float32, device=cs.device)
     counts = torch.empty(cs.n, dtype=torch.int32, device=cs.device) if with_counts else None
     if cs.n:
-        g = cs.grid() if S.USE_GRID else None
-        L.call("pcc_normals_grid", L.ptr(cs.keys), cs.n, L.ptr(g[0]) if g else None, g[2] if g else None, lim, L.ptr(normals),
+        bits, _, h = S.grid_args(cs.grid() if S.USE_GRID else None)
+        L.call("pcc_normals_grid", L.ptr(cs.keys), cs.n, bits, h, lim, L.ptr(normals),
                L.ptr(counts) if counts is not None else None, L.stream())
     return normals, counts
 

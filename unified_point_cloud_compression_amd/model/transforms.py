@@ -33,14 +33,12 @@ def batch_segments_begin(cs):
     caller reads it together with whatever else it waits for), or None when there is nothing to read."""
     if cs.bounds.bmax == 0 or "segments" in cs._derived or cs.bounds.bmax > 10 or cs.n == 0:
         return None
-    entries = cs.bounds.bmax + 2
-    a, b, c = L.counter(4), L.counter(4), L.counter(4)
-    L.call("pcc_batch_bounds", L.ptr(cs.keys), None, cs.n, entries, L.cptr(a), L.cptr(b), L.cptr(c), L.stream())
+    segs, decode = S.batch_bounds_begin(cs.keys, None, cs.n, cs.bounds.bmax + 2)
 
     def finish(v):
-        cs._derived["segments"] = [int(x) for x in (list(v[0]) + list(v[1]) + list(v[2]))[:entries]]
+        cs._derived["segments"] = decode(v)
         return cs._derived["segments"]
-    return S.Pending([a, b, c], finish)
+    return S.Pending(segs, finish)
 
 
 def batch_segments_many(csets):

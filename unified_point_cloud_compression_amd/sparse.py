@@ -8,6 +8,7 @@ coordinate manager.
 import ctypes as C
 
 import itertools
+import typing
 import weakref
 
 import torch
@@ -45,8 +46,59 @@ class Bounds:
         return Bounds(self.bmax, [v + lo_off * step for v in self.lo], [v + hi_off * step for v in self.hi])
 
 
+class Lattice:
+    """Bounding lattice of a set at one pitch: the 8-int header (lo x3, dims x3, pitch, batches) every grid entry point of
+    the library takes, and the sizes that follow from it."""
+
+    __slots__ = ("h", "dims", "cells", "words")
+
+    def __init__(self, lo, dims, pitch, batches):
+        self.dims = tuple(dims)
+        self.cells = batches * dims[0] * dims[1] * dims[2]
+        self.h = (C.c_int32 * 8)(lo[0], lo[1], lo[2], dims[0], dims[1], dims[2], pitch, batches)
+        self.words = L.load().pcc_grid_words(self.h)
+
+    @classmethod
+    def of(cls, bounds, pitch):
+        """The lattice at `pitch` that covers `bounds`."""
+        return cls(bounds.lo, [(bounds.hi[i] - bounds.lo[i]) // pitch + 1 for i in range(3)], pitch, bounds.bmax + 1)
+
+    def fits(self, limit=None):
+        """May a bitmap + rank over this lattice be allocated?  (limit: bytes, GRID_MAX_BYTES by default.)"""
+        return self.words < (1 << 31) and self.words * 12 <= (GRID_MAX_BYTES if limit is None else limit)
+
+    def alloc(self, device):
+        """(bits int64 [words], rank int32 [words], workspace) for the entry points that fill a grid index."""
+        bits = torch.empty(self.words, dtype=torch.int64, device=device)
+        rank = torch.empty(self.words, dtype=torch.int32, device=device)
+        return bits, rank, L.workspace(L.load().pcc_grid_ws_bytes(self.words), device)
+
+
+class GridIndex(typing.NamedTuple):
+    """Occupancy bitmap + rank over a set's lattice: what `CoordSet.grid` returns."""
+    bits: torch.Tensor
+    rank: torch.Tensor
+    h: typing.Any            # the lattice header (`Lattice.h`)
+
+    @property
+    def args(self):
+        """The three kernel arguments (d_bits, d_rank, h_grid)."""
+        return L.ptr(self.bits), L.ptr(self.rank), self.h
+
+
+def grid_args(g):
+    """Kernel arguments of an optional grid index (three NULLs: the kernel searches the keys instead)."""
+    return g.args if g else (None, None, None)
+
+
 class KernelMap:
     """Device-resident kernel map: header, neighbour table, optional position->row list."""
+
+    def __init__(self, n_in, n_out, ksize, transposed, hdr, nbr, rows=None, d_pairs=None):
+        self.n_in, self.n_out, self.K, self.ksize, self.transposed = n_in, n_out, ksize ** 3, ksize, bool(transposed)
+        self.hdr, self.nbr, self.rows, self.d_pairs = hdr, nbr, rows, d_pairs
+        self._pairs = None
+        self._plan = None            # pair plan: None = not started, else a Pending (queued, or done with the plan / None)
 
     def pairs(self):
         """Number of (in,out) pairs P (FLOP = 2*P*Cin*Cout); reads one device int64."""
@@ -56,13 +108,11 @@ class KernelMap:
 
     def pair_plan_begin(self):
         """Queue the ranking pass of the pair plan; returns a Pending (see `resolve`) that completes it."""
-        if hasattr(self, "_plan"):
-            return _ready(self._plan)
-        if hasattr(self, "_plan_pending"):
-            return self._plan_pending
+        if self._plan is not None:
+            return self._plan
         if not (self.rows is None and not self.transposed and self.n_out > 0 and self.K * self.n_out + self.K * 128 < (1 << 31)):
-            self._plan = None
-            return _ready(None)
+            self._plan = _ready(None)
+            return self._plan
         dev = self.hdr.device
         lib = L.load()
         pos = torch.empty(self.K * self.n_out, dtype=torch.int32, device=dev)
@@ -76,24 +126,23 @@ class KernelMap:
             padded, _, pairs = (int(x) for x in v)
             if self._pairs is None:
                 self._pairs = pairs
-            self._plan = None
-            if pairs <= PAIR_MAX_DENSITY * self.K * self.n_out:
-                pair_in = torch.empty(max(padded, 1), dtype=torch.int32, device=dev)
-                tile_k = torch.empty(max(padded // 128, 1), dtype=torch.int32, device=dev)
-                L.call("pcc_pair_plan_fill", L.ptr(self.nbr), L.ptr(pos), L.ptr(pstart), self.n_out, self.K, padded,
-                       L.ptr(pair_in), L.ptr(tile_k), L.stream())
-                self._plan = (pos, pair_in, tile_k, info, padded)
-            del self._plan_pending
-            return self._plan
-        self._plan_pending = Pending(info, finish)
-        return self._plan_pending
+            if pairs > PAIR_MAX_DENSITY * self.K * self.n_out:
+                return None
+            pair_in = torch.empty(max(padded, 1), dtype=torch.int32, device=dev)
+            tile_k = torch.empty(max(padded // 128, 1), dtype=torch.int32, device=dev)
+            L.call("pcc_pair_plan_fill", L.ptr(self.nbr), L.ptr(pos), L.ptr(pstart), self.n_out, self.K, padded,
+                   L.ptr(pair_in), L.ptr(tile_k), L.stream())
+            return pos, pair_in, tile_k, info, padded
+        self._plan = Pending(info, finish)
+        return self._plan
 
     def pair_plan(self):
         """Compacted pair lists of a conv map (pcc_conv_fwd_pairs), built on first use; None when the map is too dense
         for the pair form to pay (or is not a plain conv map)."""
-        if not hasattr(self, "_plan"):
-            resolve(self.pair_plan_begin())
-        return self._plan
+        p = self.pair_plan_begin()
+        if not p.done:
+            resolve(p)
+        return p.result
 
     def dense(self):
         """[K, n_out] int32 table with -1 holes (tests)."""
@@ -130,7 +179,7 @@ class Pending:
     sizes with one device->host copy: the host reads of a step are batched per level instead of one per derived object
     (round 2: ~33 reads per step, each leaving the GPU idle until the host had queued the next kernels)."""
 
-    __slots__ = ("counter", "finish", "result", "done", "keys_out", "cap")
+    __slots__ = ("counter", "finish", "result", "done")
 
     def __init__(self, counter, finish):
         self.counter, self.finish, self.result, self.done = counter, finish, None, False
@@ -153,8 +202,7 @@ def resolve(*pendings):
             else:
                 v = vals[at]
                 at += 1
-            p.result = p.finish(v)
-            p.done = True
+            p.result, p.done, p.finish = p.finish(v), True, None     # (finish dropped: it refers to the object that keeps p)
     return [p.result if p is not None else None for p in pendings]
 
 
@@ -164,10 +212,43 @@ def _ready(value):
     return p
 
 
+def _stride_launch(src, n_src, d_n, bounds, new_stride, cap, any_order=False):
+    """Queue unique(floor(c/m)*m) of the rows src[:n_src] (d_n: a counter() holding their number while the host has not read
+    it; n_src is then the capacity) into a buffer of `cap` keys.  bounds: those of the rows.  Returns (keys, row counter,
+    strided bounds, GridIndex of the new set or None).  any_order: the rows are not a canonical set (unsorted, duplicates, a
+    count on the device), which only the bitmap path takes."""
+    dev = src.device
+    nb = bounds.strided(new_stride)
+    lat = Lattice.of(nb, new_stride)
+    cnt = L.counter()
+    out = torch.empty(cap, dtype=torch.int64, device=dev)
+    if USE_GRID and STRIDE_BY_GRID and n_src > 0 and lat.fits():
+        # through the occupancy bitmap of the coarse lattice: no sort, and the coarse set's grid index for free
+        bits, rank, ws = lat.alloc(dev)
+        L.call("pcc_coords_stride_grid", L.ptr(src), n_src, L.cptr(d_n), lat.h, L.ptr(bits), L.ptr(rank),
+               L.ptr(out), L.cptr(cnt), L.ptr(ws), ws.numel(), L.stream())
+        return out, cnt, nb, GridIndex(bits, rank, lat.h)
+    if any_order:
+        raise L.PccError("stride_begin(keys=...) needs the bitmap path")
+    ws = L.workspace(L.load().pcc_stride_ws_bytes(n_src), dev)
+    L.call("pcc_coords_stride", L.ptr(src), n_src, new_stride, bounds.bit_mask(), L.ptr(out), L.cptr(cnt), L.ptr(ws), ws.numel(),
+           L.stream())
+    return out, cnt, nb, None
+
+
+def batch_bounds_begin(keys, d_n, n, entries):
+    """Queue `pcc_batch_bounds` over a canonical key array of n rows (d_n: a counter() holding the count instead): the first
+    `entries` batch range boundaries.  Returns (the three 4-word counters to read, decode(their values) -> [int] * entries)."""
+    segs = [L.counter(4), L.counter(4), L.counter(4)]
+    L.call("pcc_batch_bounds", L.ptr(keys), L.cptr(d_n), n, entries, L.cptr(segs[0]), L.cptr(segs[1]),
+           L.cptr(segs[2]), L.stream())
+    return segs, lambda v: [int(x) for x in (list(v[0]) + list(v[1]) + list(v[2]))[:entries]]
+
+
 class CoordSet:
     """Canonical coordinate set at one tensor stride."""
 
-    def __init__(self, keys, n, tensor_stride, bounds):
+    def __init__(self, keys, n, tensor_stride, bounds, grid=None, on_lattice=False):
         self.keys = keys                    # int64 [>=n] device, ascending
         self.n = int(n)
         self.ts = int(tensor_stride)
@@ -175,14 +256,18 @@ class CoordSet:
         self._C = None
         self._derived = {}
         self._maps = {}
-        self._grid = None
+        self._grid = grid                   # GridIndex (one that came with the keys, or built on first use); False: too large
         self._bands = None
-        self._on_lattice = False            # every row a multiple of the tensor stride: sets derived by the library are, user sets are checked
+        self._on_lattice = on_lattice       # every row a multiple of the tensor stride: sets derived by the library are, user sets are checked
         self.uid = next(_SET_SERIAL)
 
     @property
     def device(self):
         return self.keys.device
+
+    def share_grid(self, other):
+        """Same keys on the same lattice as `other`: its grid index (built or not) is shared, read-only."""
+        self._grid = other._grid
 
     def coords(self):
         """int32 [n,4] (b,x,y,z) view, tagged so SparseTensor(coordinates=x.C) re-wraps in O(1).  The tensor refers to
@@ -200,21 +285,16 @@ class CoordSet:
 
     def grid(self):
         """Occupancy bitmap + rank over the bounding lattice (the lookup structure of every map whose input is this
-        set).  Returns (bits, rank, h_grid) or None when the lattice would be unreasonably large."""
+        set).  Returns a GridIndex (bits, rank, h_grid) or None when the lattice would be unreasonably large."""
         if self._grid is None:
-            b = self.bounds
-            dims = [(b.hi[i] - b.lo[i]) // self.ts + 1 for i in range(3)]
-            h = (C.c_int32 * 8)(b.lo[0], b.lo[1], b.lo[2], dims[0], dims[1], dims[2], self.ts, b.bmax + 1)
-            words = L.load().pcc_grid_words(h)
-            if self.n == 0 or words >= (1 << 31) or words * 12 > GRID_MAX_BYTES:
+            lat = Lattice.of(self.bounds, self.ts)
+            if self.n == 0 or not lat.fits():
                 self._grid = False
             else:
-                bits = torch.empty(words, dtype=torch.int64, device=self.device)
-                rank = torch.empty(words, dtype=torch.int32, device=self.device)
-                ws = L.workspace(L.load().pcc_grid_ws_bytes(words), self.device)
-                L.call("pcc_grid_build", L.ptr(self.keys), self.n, h, L.ptr(bits), L.ptr(rank), L.ptr(ws), ws.numel(),
+                bits, rank, ws = lat.alloc(self.device)
+                L.call("pcc_grid_build", L.ptr(self.keys), self.n, lat.h, L.ptr(bits), L.ptr(rank), L.ptr(ws), ws.numel(),
                        L.stream())
-                self._grid = (bits, rank, h)
+                self._grid = GridIndex(bits, rank, lat.h)
         return self._grid or None
 
     def band_tiles(self):
@@ -247,44 +327,16 @@ class CoordSet:
         key = ("stride", new_stride)
         if key in self._derived:
             return _ready(self._derived[key])
-        dev = self.device
-        lib = L.load()
         src, n_src = (self.keys, self.n) if keys is None else (keys, n_keys)
-        nb = self.bounds.strided(new_stride)
-        dims = [(nb.hi[i] - nb.lo[i]) // new_stride + 1 for i in range(3)]
-        h = (C.c_int32 * 8)(nb.lo[0], nb.lo[1], nb.lo[2], dims[0], dims[1], dims[2], new_stride, nb.bmax + 1)
-        words = lib.pcc_grid_words(h)
-        cnt = L.counter()
-        cap = max(min(self.n, n_src), 1)
-        out = torch.empty(cap, dtype=torch.int64, device=dev)
-        by_grid = USE_GRID and STRIDE_BY_GRID and n_src > 0 and words < (1 << 31) and words * 12 <= GRID_MAX_BYTES
-        if by_grid:
-            # through the occupancy bitmap of the coarse lattice: no sort, and the coarse set's grid index for free
-            bits = torch.empty(words, dtype=torch.int64, device=dev)
-            rank = torch.empty(words, dtype=torch.int32, device=dev)
-            ws = L.workspace(lib.pcc_grid_ws_bytes(words), dev)
-            L.call("pcc_coords_stride_grid", L.ptr(src), n_src, L.cptr(d_n) if d_n is not None else None, h, L.ptr(bits), L.ptr(rank), L.ptr(out),
-                   L.cptr(cnt), L.ptr(ws), ws.numel(), L.stream())
-        else:
-            if keys is not None:
-                raise L.PccError("stride_begin(keys=...) needs the bitmap path")
-            ws = L.workspace(lib.pcc_stride_ws_bytes(self.n), dev)
-            L.call("pcc_coords_stride", L.ptr(self.keys), self.n, new_stride, self.bounds.bit_mask(), L.ptr(out),
-                   L.cptr(cnt), L.ptr(ws), ws.numel(), L.stream())
+        out, cnt, nb, grid = _stride_launch(src, n_src, d_n, self.bounds, new_stride, max(min(self.n, n_src), 1),
+                                            any_order=keys is not None)
 
         def finish(v):
-            n = int(v[0])
-            cs = CoordSet(out, n, new_stride, nb)
-            cs._on_lattice = True
-            if by_grid:
-                cs._grid = (bits, rank, h)
-            self._derived[key] = cs
+            cs = self._derived[key] = CoordSet(out, int(v[0]), new_stride, nb, grid=grid, on_lattice=True)
             return cs
         if known_n is not None:
             return _ready(finish([known_n]))
-        p = Pending(cnt, finish)
-        p.keys_out, p.cap = out, cap
-        return p
+        return Pending(cnt, finish)
 
     def stride(self, new_stride):
         """Output set of a strided conv (a2-i): unique(floor(c/m)*m)."""
@@ -301,24 +353,22 @@ class CoordSet:
         if not (USE_GRID and STRIDE_BY_GRID and self.n > 0):
             return None
         src, n_src = (self.keys, self.n) if keys is None else (keys, n_keys)
-        parts = []
+        links = []
         d_n = None
         for m in strides:
-            t = CoordSet(self.keys, self.n, self.ts, self.bounds)          # carrier of the bounds; its own cache is discarded
-            pend = t.stride_begin(m, keys=src, n_keys=n_src, d_n=d_n)
-            parts.append((m, pend))
+            cap = max(min(self.n, n_src), 1)
+            out, cnt, nb, grid = _stride_launch(src, n_src, d_n, self.bounds, m, cap, any_order=True)
+            links.append((m, out, cnt, nb, grid))
             # the next link reads the rows this one writes, with their count still on the device (capacity = this link's)
-            src, n_src, d_n = pend.keys_out, pend.cap, pend.counter
+            src, n_src, d_n = out, cap, cnt
 
         def finish(vals):
             parent = self
-            for (m, pend), v in zip(parts, vals):
-                if not pend.done:
-                    pend.result, pend.done = pend.finish(v), True
-                parent._derived[("stride", m)] = pend.result
-                parent = pend.result
+            for (m, out, _, nb, grid), v in zip(links, vals):
+                parent._derived[("stride", m)] = cs = CoordSet(out, int(v[0]), m, nb, grid=grid, on_lattice=True)
+                parent = cs
             return parent
-        return Pending([p.counter for _, p in parts], finish)
+        return Pending([link[2] for link in links], finish)
 
     def csr_for(self, out_keys, n_out, ksize, ts_out, zk=False, total=None, slots=False):
         """CSR pair lists (first[n_out+1], pair_ids) of the transposed conv from this set onto the GIVEN output rows
@@ -340,33 +390,16 @@ class CoordSet:
                 first = torch.empty(n_out, dtype=torch.int32, device=dev)
                 pair_ids = torch.empty(elems, dtype=torch.int32, device=dev)         # worst-case capacity; only the written part is touched
                 wg_end = torch.empty((n_out + 255) // 256, dtype=torch.int32, device=dev)
-                L.call("pcc_coords_expand_grid_csr_slots", L.ptr(out_keys), n_out, ksize, ts_out, L.ptr(g[0]), L.ptr(g[1]), g[2], self.n,
-                       L.ptr(first), L.ptr(pair_ids), L.ptr(wg_end), L.cptr(total) if total is not None else None, 1 if zk else 0,
-                       L.stream())
+                L.call("pcc_coords_expand_grid_csr_slots", L.ptr(out_keys), n_out, ksize, ts_out, *g.args, self.n,
+                       L.ptr(first), L.ptr(pair_ids), L.ptr(wg_end), L.cptr(total), 1 if zk else 0, L.stream())
                 return first, pair_ids, wg_end
         first = torch.empty(n_out + 1, dtype=torch.int32, device=dev)
         pair_ids = torch.empty(max(self.n * K, 1), dtype=torch.int32, device=dev)
         ws = L.workspace(L.load().pcc_expand_grid_csr_ws_bytes(n_out), dev)
         # zk: pair ids number the kernel offsets z fastest (for product buffers laid out [row][kx][ky][kz][c])
         L.call("pcc_coords_expand_grid_csr_zk" if zk else "pcc_coords_expand_grid_csr", L.ptr(out_keys), n_out, ksize, ts_out,
-               L.ptr(g[0]), L.ptr(g[1]), g[2], self.n, L.ptr(first), L.ptr(pair_ids), L.cptr(total) if total is not None else None,
-               L.ptr(ws), ws.numel(), L.stream())
+               *g.args, self.n, L.ptr(first), L.ptr(pair_ids), L.cptr(total), L.ptr(ws), ws.numel(), L.stream())
         return first, pair_ids
-
-    def _expand_lattice(self, ksize, ts_out):
-        ob = self.bounds.expanded(ksize, ts_out)
-        dims = [(ob.hi[i] - ob.lo[i]) // ts_out + 1 for i in range(3)]
-        cells = (ob.bmax + 1) * dims[0] * dims[1] * dims[2]
-        h = (C.c_int32 * 8)(ob.lo[0], ob.lo[1], ob.lo[2], dims[0], dims[1], dims[2], ts_out, ob.bmax + 1)
-        return ob, cells, h, L.load().pcc_grid_words(h)
-
-    def _expand_by_grid(self, ksize, ts_out):
-        K = ksize ** 3
-        _, _, _, words = self._expand_lattice(ksize, ts_out)
-        if (USE_CSR and USE_GRID and EXPAND_BY_GRID and self.n > 0 and ksize in (2, 3, 5) and words < (1 << 31)
-                and words * 12 <= GRID_MAX_BYTES and self.n * K < (1 << 31)):
-            return self.grid()
-        return None
 
     def expand_begin(self, ksize, ts_out, want_csr=True):
         """Queue the generative expansion through the bitmaps; returns a Pending yielding the CoordSet, or None when this
@@ -375,44 +408,59 @@ class CoordSet:
         key = ("expand", ksize, ts_out)
         if key in self._derived:
             return _ready(self.expand(ksize, ts_out, want_csr))
-        if not self._expand_by_grid(ksize, ts_out):
-            return None
-        dev = self.device
-        lib = L.load()
-        ob, cells, h, words = self._expand_lattice(ksize, ts_out)
+        ob = self.bounds.expanded(ksize, ts_out)
+        lat = Lattice.of(ob, ts_out)
         m = self.n * ksize ** 3
+        if not (USE_CSR and USE_GRID and EXPAND_BY_GRID and self.n > 0 and ksize in (2, 3, 5) and lat.fits() and m < (1 << 31)
+                and self.grid()):
+            return None
         # mark the output bitmap, read the set back out, then build the pair lists by probing this set's grid
-        bits = torch.empty(words, dtype=torch.int64, device=dev)
-        rank = torch.empty(words, dtype=torch.int32, device=dev)
-        out = torch.empty(min(m, cells), dtype=torch.int64, device=dev)
+        bits, rank, ws = lat.alloc(self.device)
+        out = torch.empty(min(m, lat.cells), dtype=torch.int64, device=self.device)
         cnt = L.counter()
-        ws = L.workspace(lib.pcc_grid_ws_bytes(words), dev)
-        L.call("pcc_coords_expand_grid", L.ptr(self.keys), self.n, ksize, h, L.ptr(bits), L.ptr(rank), L.ptr(out),
+        L.call("pcc_coords_expand_grid", L.ptr(self.keys), self.n, ksize, lat.h, L.ptr(bits), L.ptr(rank), L.ptr(out),
                L.cptr(cnt), L.ptr(ws), ws.numel(), L.stream())
         # batched sets: the per-batch row ranges of the new set (top-k runs per batch) come back with its size
-        entries = ob.bmax + 2 if 0 < ob.bmax <= 10 else 0
-        if entries:
-            seg_a, seg_b, seg_c = L.counter(4), L.counter(4), L.counter(4)
-            L.call("pcc_batch_bounds", L.ptr(out), L.cptr(cnt), 0, entries, L.cptr(seg_a), L.cptr(seg_b), L.cptr(seg_c), L.stream())
+        segs, seg_decode = batch_bounds_begin(out, cnt, 0, ob.bmax + 2) if 0 < ob.bmax <= 10 else (None, None)
 
         def finish(v):
-            segs = None
-            if v and isinstance(v[0], (list, tuple)):            # [[n], ranges 0-3, ranges 4-7, ranges 8-11]
-                segs = (list(v[1]) + list(v[2]) + list(v[3]))[:entries]
-                v = v[0]
-            n = int(v[0])
-            cs = CoordSet(out[:n].clone() if n < out.numel() // 2 else out, n, ts_out, ob)
-            cs._grid = (bits, rank, h)
-            cs._on_lattice = self._on_lattice
-            if segs is not None:
-                cs._derived["segments"] = [int(x) for x in segs]
+            ranges = isinstance(v[0], (list, tuple))             # read with the ranges: [[n], ranges 0-3, ranges 4-7, ranges 8-11]
+            n = int(v[0][0] if ranges else v[0])
+            cs = CoordSet(out[:n].clone() if n < out.numel() // 2 else out, n, ts_out, ob, grid=GridIndex(bits, rank, lat.h),
+                          on_lattice=self._on_lattice)
+            if ranges:
+                cs._derived["segments"] = seg_decode(v[1:])
             self._derived[key] = cs
             if want_csr:
                 self._derived[("csr", ksize, ts_out)] = self.csr_for(cs.keys, n, ksize, ts_out)
             return cs
         if ksize == 2 and self.ts == 2 * ts_out and self._on_lattice:
             return _ready(finish([8 * self.n]))
-        return Pending([cnt, seg_a, seg_b, seg_c] if entries else cnt, finish)
+        return Pending([cnt] + segs if segs else cnt, finish)
+
+    def _expand_sort32(self, ksize, ts_out, ob, lat):
+        """Expansion by a radix sort of 32-bit cell numbers with the pair ids as payload: the set and its CSR pair lists."""
+        m = self.n * ksize ** 3
+        out = torch.empty(m, dtype=torch.int64, device=self.device)
+        pair_ids = torch.empty(m, dtype=torch.int32, device=self.device)
+        first = torch.empty(m + 1, dtype=torch.int32, device=self.device)
+        cnt = L.counter()
+        ws = L.workspace(L.load().pcc_expand_csr_ws_bytes(self.n, ksize), self.device)
+        L.call("pcc_coords_expand_csr", L.ptr(self.keys), self.n, ksize, ts_out, lat.h, L.ptr(out), L.cptr(cnt),
+               L.ptr(pair_ids), L.ptr(first), L.ptr(ws), ws.numel(), L.stream())
+        n = int(L.read(cnt)[0])
+        self._derived[("csr", ksize, ts_out)] = (first[:n + 1].clone(), pair_ids)
+        return CoordSet(out[:n].clone(), n, ts_out, ob)
+
+    def _expand_sort64(self, ksize, ts_out, ob):
+        """Expansion by a radix sort of the 64-bit keys + unique: the set alone."""
+        out = torch.empty(max(self.n * ksize ** 3, 1), dtype=torch.int64, device=self.device)
+        cnt = L.counter()
+        ws = L.workspace(L.load().pcc_expand_ws_bytes(self.n, ksize), self.device)
+        L.call("pcc_coords_expand", L.ptr(self.keys), self.n, ksize, ts_out, ob.bit_mask(), L.ptr(out),
+               L.cptr(cnt), L.ptr(ws), ws.numel(), L.stream())
+        n = int(L.read(cnt)[0])
+        return CoordSet(out[:n].clone(), n, ts_out, ob)
 
     def expand(self, ksize, ts_out, want_csr=True):
         """Output set of a generative transposed conv (a3-i): unique{c + off_k*ts_out}, plus (want_csr) the transposed
@@ -426,32 +474,12 @@ class CoordSet:
             pend = self.expand_begin(ksize, ts_out, want_csr)
             if pend is not None:
                 return resolve(pend)[0]
-            dev = self.device
-            K = ksize ** 3
-            ob, cells, h, words = self._expand_lattice(ksize, ts_out)
-            if USE_CSR and self.n > 0 and cells <= 0xFFFFFFFF and self.n * K < (1 << 31):
-                m = self.n * K
-                out = torch.empty(m, dtype=torch.int64, device=dev)
-                pair_ids = torch.empty(m, dtype=torch.int32, device=dev)
-                first = torch.empty(m + 1, dtype=torch.int32, device=dev)
-                cnt = L.counter()
-                ws = L.workspace(L.load().pcc_expand_csr_ws_bytes(self.n, ksize), dev)
-                L.call("pcc_coords_expand_csr", L.ptr(self.keys), self.n, ksize, ts_out, h, L.ptr(out), L.cptr(cnt),
-                       L.ptr(pair_ids), L.ptr(first), L.ptr(ws), ws.numel(), L.stream())
-                n = int(L.read(cnt)[0])
-                cs = CoordSet(out[:n].clone(), n, ts_out, ob)
-                self._derived[key] = cs
-                self._derived[("csr", ksize, ts_out)] = (first[:n + 1].clone(), pair_ids)
-                return cs
-            cap = max(self.n * K, 1)
-            out = torch.empty(cap, dtype=torch.int64, device=dev)
-            cnt = L.counter()
-            nb = L.load().pcc_expand_ws_bytes(self.n, ksize)
-            ws = L.workspace(nb, dev)
-            L.call("pcc_coords_expand", L.ptr(self.keys), self.n, ksize, ts_out, ob.bit_mask(), L.ptr(out),
-                   L.cptr(cnt), L.ptr(ws), ws.numel(), L.stream())
-            n = int(L.read(cnt)[0])
-            self._derived[key] = CoordSet(out[:n].clone(), n, ts_out, ob)
+            ob = self.bounds.expanded(ksize, ts_out)
+            lat = Lattice.of(ob, ts_out)
+            if USE_CSR and self.n > 0 and lat.cells <= 0xFFFFFFFF and self.n * ksize ** 3 < (1 << 31):
+                self._derived[key] = self._expand_sort32(ksize, ts_out, ob, lat)
+            else:
+                self._derived[key] = self._expand_sort64(ksize, ts_out, ob)
         return self._derived[key]
 
     def csr_map(self, ksize, ts_out):
@@ -472,33 +500,22 @@ class CoordSet:
             return m
         dev = self.device
         lib = L.load()
-        K = ksize ** 3
-        m = KernelMap()
-        m.n_in, m.n_out, m.K, m.ksize, m.transposed = self.n, out_set.n, K, ksize, bool(transposed)
-        m._pairs = None
-        m.hdr = torch.empty(L.MAP_HDR_INTS, dtype=torch.int32, device=dev)
         nelem = lib.pcc_map_nbr_elems(out_set.n, ksize, up_stride, 1 if transposed else 0)
-        m.nbr = torch.empty(max(nelem, 1), dtype=torch.int32, device=dev)
-        m.rows = torch.empty(max(out_set.n, 1), dtype=torch.int32, device=dev) if (transposed or morton) else None
-        m.d_pairs = torch.zeros(1, dtype=torch.int64, device=dev) if COUNT_PAIRS else None
+        m = KernelMap(self.n, out_set.n, ksize, transposed,
+                      hdr=torch.empty(L.MAP_HDR_INTS, dtype=torch.int32, device=dev),
+                      nbr=torch.empty(max(nelem, 1), dtype=torch.int32, device=dev),
+                      rows=torch.empty(max(out_set.n, 1), dtype=torch.int32, device=dev) if (transposed or morton) else None,
+                      d_pairs=torch.zeros(1, dtype=torch.int64, device=dev) if COUNT_PAIRS else None)
         if step is None:
             step = out_set.ts if transposed else self.ts
-        g = self.grid() if USE_GRID else None
         ws = L.workspace(lib.pcc_map_ws_bytes(out_set.n), dev)
         L.call("pcc_kernel_map_build", L.ptr(self.keys), self.n, L.ptr(out_set.keys), out_set.n, ksize, step,
                up_stride, 1 if transposed else 0, L.ptr(m.hdr), L.ptr(m.nbr), L.ptr(m.rows), L.ptr(m.d_pairs),
-               L.ptr(g[0]) if g else None, L.ptr(g[1]) if g else None, g[2] if g else None,
-               L.ptr(ws), ws.numel(), L.stream())
+               *grid_args(self.grid() if USE_GRID else None), L.ptr(ws), ws.numel(), L.stream())
         self._maps[key] = m
         # (the cache key is the output set's serial number, not id(): nothing has to keep the output set alive, and a
         #  reference from here would close cycles such as y -> stride -> z -> expand -> children -> map onto y)
         return m
-
-
-def _canon_check(keys, n):
-    flag = L.counter(1, torch.int32)
-    L.call("pcc_keys_is_canonical", L.ptr(keys), n, L.cptr(flag), L.stream())
-    return bool(L.read(flag)[0])
 
 
 def pack_keys(coords):
@@ -597,19 +614,15 @@ def coordset_from_coords(coords, tensor_stride, stride_chain=None):
         return cs, None, None
     dev = coords.device
     lib = L.load()
-    dims = [(b.hi[i] - b.lo[i]) // tensor_stride + 1 for i in range(3)]
-    h = (C.c_int32 * 8)(b.lo[0], b.lo[1], b.lo[2], dims[0], dims[1], dims[2], tensor_stride, b.bmax + 1)
-    words = lib.pcc_grid_words(h)
+    lat = Lattice.of(b, tensor_stride)
     on_lattice = all(v % tensor_stride == 0 for v in b.lo)      # rows of a stride-ts tensor sit on multiples of ts
-    if USE_GRID and CANON_BY_GRID and on_lattice and words < (1 << 31) and words * 12 <= GRID_MAX_BYTES:
+    if USE_GRID and CANON_BY_GRID and on_lattice and lat.fits():
         # through the occupancy bitmap: canonical keys, first-wins row per coordinate and the grid index, no sort
-        bits = torch.empty(words, dtype=torch.int64, device=dev)
-        rank = torch.empty(words, dtype=torch.int32, device=dev)
+        bits, rank, ws = lat.alloc(dev)
         ukeys = torch.empty(n, dtype=torch.int64, device=dev)
         first_user = torch.empty(n, dtype=torch.int32, device=dev)
         cnt = L.counter(2)
-        ws = L.workspace(lib.pcc_grid_ws_bytes(words), dev)
-        L.call("pcc_keys_canonicalize_grid", L.ptr(keys), n, h, L.ptr(bits), L.ptr(rank), L.ptr(ukeys), L.ptr(first_user),
+        L.call("pcc_keys_canonicalize_grid", L.ptr(keys), n, lat.h, L.ptr(bits), L.ptr(rank), L.ptr(ukeys), L.ptr(first_user),
                L.cptr(cnt), L.ptr(ws), ws.numel(), L.stream())
         cs = CoordSet(ukeys, n, tensor_stride, b)          # (row count filled in below)
         # the strided sets of the chain do not need the canonical rows: marking coarse cells from the user rows is the same
@@ -617,15 +630,9 @@ def coordset_from_coords(coords, tensor_stride, stride_chain=None):
         (nu, off_lattice), _ = resolve(Pending(cnt, lambda v: (int(v[0]), int(v[1]))), chain)
         if not off_lattice:
             cs.n = nu
-            cs._grid = (bits, rank, h)
+            cs._grid = GridIndex(bits, rank, lat.h)
             cs._on_lattice = True
-            first_user = first_user[:nu].long()
-            if nu == n:
-                return cs, first_user, None
-            keep, inv = torch.sort(first_user)            # surviving user rows, original order
-            rank_u = torch.empty_like(inv)
-            rank_u[inv] = torch.arange(nu, device=dev)
-            return cs, rank_u, keep
+            return _first_wins(cs, first_user[:nu].long(), n)
     skeys = torch.empty(n, dtype=torch.int64, device=dev)
     perm = torch.empty(n, dtype=torch.int32, device=dev)
     ws = L.workspace(lib.pcc_sort_ws_bytes(n), dev)
@@ -639,12 +646,17 @@ def coordset_from_coords(coords, tensor_stride, stride_chain=None):
     nu = int(L.read(cnt)[0])
     # stable sort => first[] points at the smallest user row of each run
     first_user = perm.long()[first[:nu].long()]
-    cs = CoordSet(ukeys[:nu].clone() if nu < n else ukeys, nu, tensor_stride, b)
-    if nu == n:
+    return _first_wins(CoordSet(ukeys[:nu].clone() if nu < n else ukeys, nu, tensor_stride, b), first_user, n)
+
+
+def _first_wins(cs, first_user, n):
+    """(cs, perm, keep) of `coordset_from_coords` from first_user (int64 [cs.n]: canonical position -> first of the n user
+    rows with that coordinate)."""
+    if cs.n == n:
         return cs, first_user, None
     keep, inv = torch.sort(first_user)            # surviving user rows, original order
     rank = torch.empty_like(inv)
-    rank[inv] = torch.arange(nu, device=dev)
+    rank[inv] = torch.arange(cs.n, device=cs.device)
     return cs, rank, keep
 
 
@@ -704,6 +716,15 @@ class PackedConv:
         return self.packed
 
 
+def _flat_bias(bias):
+    return bias.detach().reshape(-1).contiguous() if bias is not None else None
+
+
+def _map_ptrs(kmap):
+    """(d_hdr, d_nbr, d_rows) of an optional kernel map (None: the K = 1 identity)."""
+    return (L.ptr(kmap.hdr), L.ptr(kmap.nbr), L.ptr(kmap.rows)) if kmap is not None else (None, None, None)
+
+
 def wants_pairs(K, cin, cout):
     """Does conv_forward try the pair-list form for this shape?  (The coordinate pre-passes of g_a / g_s queue the pair
     plans of such layers ahead of the features, so that their sizes are read together.)"""
@@ -716,7 +737,7 @@ def conv_forward(feats, packed_w, bias, K, cin, cout, kmap, n_out, act=L.ACT_NON
     out = torch.empty((n_out, cout), dtype=torch.float32, device=feats.device)
     if n_out == 0:
         return out
-    b = bias.detach().reshape(-1).contiguous() if bias is not None else None
+    b = _flat_bias(bias)
     if kmap is not None and wants_pairs(K, cin, cout):
         plan = kmap.pair_plan()
         if plan is not None:           # sparse map: gathered GEMM over the compacted pairs, then ordered reduce
@@ -728,9 +749,7 @@ def conv_forward(feats, packed_w, bias, K, cin, cout, kmap, n_out, act=L.ACT_NON
             return out
     ws = L.workspace(L.load().pcc_conv_ws_bytes(feats.shape[0], K, cin, cout), feats.device)
     L.call("pcc_conv_fwd", L.ptr(feats), feats.shape[0], cin, L.ptr(packed_w), L.ptr(b), K, cout,
-           L.ptr(kmap.hdr) if kmap is not None else None, L.ptr(kmap.nbr) if kmap is not None else None,
-           L.ptr(kmap.rows) if kmap is not None else None, n_out, L.ptr(out), act, float(slope), L.ptr(ws),
-           ws.numel(), *L.arith_args(feats.device), L.stream())
+           *_map_ptrs(kmap), n_out, L.ptr(out), act, float(slope), L.ptr(ws), ws.numel(), *L.arith_args(feats.device), L.stream())
     return out
 
 
@@ -744,8 +763,7 @@ def conv_head_forward(feats, packed_w0, bias0, cmid, w2, bias2, cset, kmap):
         return out
     bands = cset.band_tiles()
     ws = L.workspace(L.load().pcc_conv_head_ws_bytes(n), feats.device)
-    b0 = bias0.detach().reshape(-1).contiguous() if bias0 is not None else None
-    b2 = bias2.detach().reshape(-1).contiguous() if bias2 is not None else None
+    b0, b2 = _flat_bias(bias0), _flat_bias(bias2)
     L.call("pcc_conv_head_fwd", L.ptr(feats), n, cin, L.ptr(packed_w0), L.ptr(b0), cmid, L.ptr(w2), L.ptr(b2),
            L.ptr(kmap.hdr), L.ptr(kmap.nbr), L.ptr(bands[0]) if bands else None, L.ptr(bands[1]) if bands else None,
            L.ptr(out), L.ptr(ws), ws.numel(), L.stream())
@@ -760,7 +778,7 @@ def convt_forward(feats, packed_w, bias, K, cin, cout, kmap, n_out, act=L.ACT_NO
     if n_out == 0 or n_in == 0:
         return out
     T = torch.empty(n_in * K * cout, dtype=torch.float32, device=feats.device)
-    b = bias.detach().reshape(-1).contiguous() if bias is not None else None
+    b = _flat_bias(bias)
     L.call("pcc_convt_fwd", L.ptr(feats), n_in, cin, L.ptr(packed_w), L.ptr(b), K, cout, L.ptr(kmap.hdr),
            L.ptr(kmap.nbr), L.ptr(kmap.rows), n_out, L.ptr(T), L.ptr(out), act, float(slope), *L.arith_args(feats.device),
            L.stream())
@@ -779,7 +797,7 @@ def convt_forward_csr(feats, packed_w, bias, K, cin, cout, csr, n_out, act=L.ACT
         return out
     first, pair_ids = csr
     T = torch.empty(n_in * K * cout, dtype=torch.float32, device=feats.device)
-    b = bias.detach().reshape(-1).contiguous() if bias is not None else None
+    b = _flat_bias(bias)
     eb = ex_bias.detach().to(torch.float32).contiguous() if ex_map is not None else None
     L.call("pcc_convt_fwd_csr", L.ptr(feats), n_in, cin, L.ptr(packed_w), L.ptr(b), K, cout, L.ptr(first),
            L.ptr(pair_ids), n_out, L.ptr(T), L.ptr(out), act, float(slope),
@@ -808,11 +826,10 @@ def convt_forward_csr_grid(feats, packed_w, bias, K, cin, cout, csr, out_set, ac
         return out
     first, pair_ids = csr[0], csr[1]
     wg_end = csr[2] if len(csr) > 2 else None                  # slotted lists (`csr_for(slots=True)`)
-    g = out_set.grid()
     T = torch.empty(n_in * K * cout, dtype=torch.float32, device=feats.device)
-    b = bias.detach().reshape(-1).contiguous() if bias is not None else None
+    b = _flat_bias(bias)
     L.call("pcc_convt_fwd_csr_grid", L.ptr(feats), n_in, cin, L.ptr(packed_w), L.ptr(b), K, cout, L.ptr(first), L.ptr(pair_ids),
-           n_out, L.ptr(T), L.ptr(out), act, float(slope), L.ptr(out_set.keys), L.ptr(g[0]), L.ptr(g[1]), g[2],
+           n_out, L.ptr(T), L.ptr(out), act, float(slope), L.ptr(out_set.keys), *out_set.grid().args,
            L.ptr(ex_bias.detach().to(torch.float32).contiguous()), L.ptr(wg_end), *L.arith_args(feats.device), L.stream())
     return out
 
@@ -824,11 +841,10 @@ def conv_thin_grid_forward(feats, packed_w, bias, cin, cout, cset):
     out = torch.empty((n, cout), dtype=torch.float32, device=feats.device)
     if n == 0:
         return out
-    g = cset.grid()
     ws = L.workspace(L.load().pcc_thin_grid_ws_bytes(n, cout), feats.device)
-    b = bias.detach().reshape(-1).contiguous() if bias is not None else None
-    L.call("pcc_conv_thin_grid_fwd", L.ptr(feats), n, cin, L.ptr(packed_w), L.ptr(b), cout, L.ptr(cset.keys), L.ptr(g[0]), L.ptr(g[1]),
-           g[2], L.ptr(out), L.ptr(ws), ws.numel(), L.stream())
+    b = _flat_bias(bias)
+    L.call("pcc_conv_thin_grid_fwd", L.ptr(feats), n, cin, L.ptr(packed_w), L.ptr(b), cout, L.ptr(cset.keys), *cset.grid().args,
+           L.ptr(out), L.ptr(ws), ws.numel(), L.stream())
     return out
 
 
@@ -845,7 +861,7 @@ def convt_forward_rows(feats, packed_w, bias, K, cin, cout, csr, n_out, act=L.AC
     pairs = int(first[n_out].item()) if pairs_bound is None else pairs_bound
     T = torch.empty(max(lib.pcc_convt_rows_t_elems(pairs, K, cout), 1), dtype=torch.float32, device=feats.device)
     ws = L.workspace(lib.pcc_convt_rows_int_ws_bytes(pairs, K), feats.device)
-    b = bias.detach().reshape(-1).contiguous() if bias is not None else None
+    b = _flat_bias(bias)
     L.call("pcc_convt_fwd_rows", L.ptr(feats), feats.shape[0], cin, L.ptr(packed_w), L.ptr(b), K, cout, L.ptr(first),
            L.ptr(pair_ids), n_out, pairs, L.ptr(T), L.ptr(out), act, float(slope), L.ptr(ws), ws.numel(),
            *L.arith_args(feats.device), L.stream())
@@ -857,12 +873,8 @@ def map_from_csr(csr, n_in, n_out, ksize):
     CSR pair lists: conv_forward then evaluates it (pair-list form when sparse) without the dense per-pair buffer."""
     first, pair_ids = csr
     dev = first.device
-    K = ksize ** 3
-    m = KernelMap()
-    m.n_in, m.n_out, m.K, m.ksize, m.transposed = n_in, n_out, K, ksize, False
-    m._pairs, m.d_pairs, m.rows = None, None, None
-    m.hdr = torch.empty(L.MAP_HDR_INTS, dtype=torch.int32, device=dev)
-    m.nbr = torch.empty(max(K * n_out, 1), dtype=torch.int32, device=dev)
+    m = KernelMap(n_in, n_out, ksize, False, hdr=torch.empty(L.MAP_HDR_INTS, dtype=torch.int32, device=dev),
+                  nbr=torch.empty(max(ksize ** 3 * n_out, 1), dtype=torch.int32, device=dev))
     if n_out:
         L.call("pcc_map_from_csr", L.ptr(first), L.ptr(pair_ids), n_out, ksize, L.ptr(m.hdr), L.ptr(m.nbr), L.stream())
     return m
@@ -874,8 +886,7 @@ def conv_wgrad(feats_in, grad_out, K, cin, cout, kmap):
     dW = torch.empty((K, cin, cout), dtype=torch.float32, device=feats_in.device)
     ws = L.workspace(L.load().pcc_conv_wgrad_ws_bytes(grad_out.shape[0], K, cin, cout), feats_in.device)
     L.call("pcc_conv_wgrad", L.ptr(feats_in), feats_in.shape[0], cin, L.ptr(grad_out), grad_out.shape[0], cout, K,
-           L.ptr(kmap.hdr) if kmap is not None else None, L.ptr(kmap.nbr) if kmap is not None else None,
-           L.ptr(kmap.rows) if kmap is not None else None, L.ptr(dW), L.ptr(ws), ws.numel(), L.stream())
+           *_map_ptrs(kmap), L.ptr(dW), L.ptr(ws), ws.numel(), L.stream())
     return dW
 
 
@@ -901,38 +912,14 @@ def convt_scatter_rows(grad_out, csr, n_pairs, cout):
     return dT
 
 
-def topk_mask(logits, seg_begin, ks):
-    """Per-batch top-k mask over rows in canonical order (a4)."""
-    n = logits.shape[0]
-    mask = torch.empty(max(n, 1), dtype=torch.uint8, device=logits.device)
-    if n == 0:
-        return mask[:0].bool()
+def _topk_args(what, logits, seg_begin, ks):
+    """What `pcc_topk_mask` / `pcc_topk_prune_keys` share: (logits, their row stride, seg_begin int64[nb + 1], k int64[nb],
+    workspace).  logits: [n], or column 0 of an [n, c] tensor (`prediction.F[:, 0]`, model/transforms.py:246), read in place
+    when its rows are strided."""
     nb = len(ks)
     sb = (C.c_int64 * (nb + 1))(*seg_begin)
     kk = (C.c_int64 * nb)(*[int(k) for k in ks])
-    ws = L.workspace(L.load().pcc_topk_ws_bytes(n), logits.device)
-    if logits.dim() == 2:     # column 0 of an [n,c] logit tensor (`prediction.F[:, 0]`, model/transforms.py:246)
-        if logits.stride(1) != 1 and logits.shape[1] != 1:
-            logits = logits.contiguous()
-        stride = logits.stride(0)
-    else:
-        logits, stride = logits.contiguous(), 1
-    if not logits.is_cuda:
-        raise L.PccError("topk_mask: GPU tensor required")
-    L.call("pcc_topk_mask", logits.data_ptr(), stride, sb, kk, nb, L.ptr(mask), L.ptr(ws), ws.numel(), L.stream())
-    return mask[:n].view(torch.bool)
-
-
-def topk_prune_keys(logits, seg_begin, ks, keys):
-    """`topk_mask` and the compaction of the kept rows' keys in one pass over the logits (a4, coordinates only: what the
-    decoder's composite levels need).  Returns (mask bool [n], kept keys int64 [n_keep], n_keep)."""
-    n = logits.shape[0]
-    nb = len(ks)
-    n_keep = sum(min(max(int(k), 0), seg_begin[i + 1] - seg_begin[i]) for i, k in enumerate(ks))
-    mask = torch.empty(max(n, 1), dtype=torch.uint8, device=logits.device)
-    keys_out = torch.empty(max(n_keep, 1), dtype=torch.int64, device=logits.device)
-    if n == 0:
-        return mask[:0].bool(), keys_out[:0], 0
+    ws = L.workspace(L.load().pcc_topk_ws_bytes(logits.shape[0]), logits.device)
     if logits.dim() == 2:
         if logits.stride(1) != 1 and logits.shape[1] != 1:
             logits = logits.contiguous()
@@ -940,11 +927,32 @@ def topk_prune_keys(logits, seg_begin, ks, keys):
     else:
         logits, stride = logits.contiguous(), 1
     if not logits.is_cuda:
-        raise L.PccError("topk_prune_keys: GPU tensor required")
-    sb = (C.c_int64 * (nb + 1))(*seg_begin)
-    kk = (C.c_int64 * nb)(*[int(k) for k in ks])
-    ws = L.workspace(L.load().pcc_topk_ws_bytes(n), logits.device)
-    L.call("pcc_topk_prune_keys", logits.data_ptr(), stride, sb, kk, nb, L.ptr(keys), L.ptr(mask), L.ptr(keys_out), L.ptr(ws),
+        raise L.PccError(f"{what}: GPU tensor required")
+    return logits, stride, sb, kk, ws
+
+
+def topk_mask(logits, seg_begin, ks):
+    """Per-batch top-k mask over rows in canonical order (a4)."""
+    n = logits.shape[0]
+    mask = torch.empty(max(n, 1), dtype=torch.uint8, device=logits.device)
+    if n == 0:
+        return mask[:0].bool()
+    logits, stride, sb, kk, ws = _topk_args("topk_mask", logits, seg_begin, ks)
+    L.call("pcc_topk_mask", logits.data_ptr(), stride, sb, kk, len(ks), L.ptr(mask), L.ptr(ws), ws.numel(), L.stream())
+    return mask[:n].view(torch.bool)
+
+
+def topk_prune_keys(logits, seg_begin, ks, keys):
+    """`topk_mask` and the compaction of the kept rows' keys in one pass over the logits (a4, coordinates only: what the
+    decoder's composite levels need).  Returns (mask bool [n], kept keys int64 [n_keep], n_keep)."""
+    n = logits.shape[0]
+    n_keep = sum(min(max(int(k), 0), seg_begin[i + 1] - seg_begin[i]) for i, k in enumerate(ks))
+    mask = torch.empty(max(n, 1), dtype=torch.uint8, device=logits.device)
+    keys_out = torch.empty(max(n_keep, 1), dtype=torch.int64, device=logits.device)
+    if n == 0:
+        return mask[:0].bool(), keys_out[:0], 0
+    logits, stride, sb, kk, ws = _topk_args("topk_prune_keys", logits, seg_begin, ks)
+    L.call("pcc_topk_prune_keys", logits.data_ptr(), stride, sb, kk, len(ks), L.ptr(keys), L.ptr(mask), L.ptr(keys_out), L.ptr(ws),
            ws.numel(), L.stream())
     return mask[:n].view(torch.bool), keys_out[:n_keep], n_keep
 
@@ -1039,9 +1047,8 @@ def channelwise_full_taps(kernel_size):
 
 def _chconv_common(cset, feats, taps):
     cols, widx = taps.on(feats.device)
-    g = cset.grid() if USE_GRID else None
-    return (L.ptr(cset.keys), cset.n, L.ptr(feats), feats.shape[1], L.ptr(g[0]) if g else None, L.ptr(g[1]) if g else None,
-            g[2] if g else None, cset.ts, L.ptr(cols), taps.ncol, L.ptr(widx), taps.ntaps, taps.kernel_size)
+    return (L.ptr(cset.keys), cset.n, L.ptr(feats), feats.shape[1], *grid_args(cset.grid() if USE_GRID else None), cset.ts,
+            L.ptr(cols), taps.ncol, L.ptr(widx), taps.ntaps, taps.kernel_size)
 
 
 def channelwise_gather(cset, feats, taps, weights, query_keys, nq):
