@@ -634,6 +634,53 @@ int pcc_geom_tables(const uint64_t* state, const uint32_t* h_pop, int32_t* cdf, 
 int pcc_geom_state_update(uint64_t* state, const uint32_t* hist, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 8f-3c RAHT colour coder over the level sets of 8f-3b: the anchor the reference compares against is
+ *       `tmc3 --transformType=0` (`utils.py:505-529`); this is the same transform family in our own stream, no G-PCC syntax.
+ *       A level is given as its canonical node keys at `pitch` plus the canonical child set at pitch / 2 with that set's grid
+ *       index (child_bits / child_rank / h_child, pcc_grid_build layout; three NULLs: binary search over child_keys).  Child j of
+ *       a node is (dx, dy, dz), j = dx<<2 | dy<<1 | dz.  Values are Q8 int32 [rows, channels], 1 <= channels <= 8; weights int32.
+ *       Coefficient rows: a node with m children emits m - 1 rows (stage 3, stage 2 slots 0 and 4, stage 1 slots 0 2 4 6) from row
+ *       row_base + off[i] - i of one [rows_total, channels] matrix shared by all levels (row_base = nodes(level) - 1, off from
+ *       pcc_geom_child_offsets over the masks); rows at or past rows_total are never touched.  n, n_child < 2^26.
+ * pcc_raht_isqrt / pcc_raht_butterfly  HOST: the kernels' own arithmetic for the CPU tests.  isqrt: exact floor square root
+ *                      (x < 2^62, else 0).  butterfly: h_out[6] = a, b (Q30 factors of weights w1, w2), L, H, and the inverse's x1, x2.
+ * pcc_raht_prepare     uint8 attrs [n, channels] (row perm[i] of the caller's order, perm NULL: row i) -> Q8 values; colour != 0
+ *                      (channels == 3): the integer BT.709 transform of DESIGN.md 7f instead of v << 8.
+ * pcc_raht_mask        mask[i] = child-occupancy byte of node i.
+ * pcc_raht_weights     w[i] = sum of the children's weights (child_w NULL: the children are voxels of weight 1).
+ * pcc_raht_forward     w[i], v[i, :] (the node's DC) and the node's quantised coefficients, q = sign(H) * ((|H| + step / 2) / step)
+ *                      with h_steps[channels] (HOST, Q8).
+ * pcc_raht_inverse     child_v of every child from v, the rows' q * step (clamped to +-2^30 like every butterfly output; a clamp
+ *                      sets bit 0 of *d_flag, device int32 zeroed by the caller).
+ * pcc_raht_index       idx[row, c] of a level's rows from its masks: side NULL: the group level * 6 + (c ? 3 : 0) + stage - 1;
+ *                      else side[group] & 63 (device int32 [levels * 6]), the table member of that group.
+ * pcc_raht_hist        hist[groups * 128] (uint32, zeroed here; groups <= 90): hist[grp * 128 + value + 63], values outside
+ *                      -63 .. 63 in slot 127.  Integer atomics, reduced in LDS per workgroup first.
+ * pcc_raht_finish      Q8 values -> uint8: (v + 128) >> 8 clamped, or the inverse colour transform (colour != 0, channels == 3).
+ * ---------------------------------------------------------------------------------------- */
+uint64_t pcc_raht_isqrt(uint64_t x);
+int pcc_raht_butterfly(uint32_t w1, uint32_t w2, int64_t x1, int64_t x2, int64_t* h_out /*[6]*/);
+int pcc_raht_prepare(const uint8_t* attrs, const int64_t* perm /*nullable*/, int64_t n, int32_t channels, int32_t colour,
+                     int32_t* values, void* stream);
+int pcc_raht_mask(const int64_t* keys, int64_t n, int32_t pitch, const int64_t* child_keys, int64_t n_child,
+                  const uint64_t* child_bits, const int32_t* child_rank, const int32_t* h_child, int32_t* mask, void* stream);
+int pcc_raht_weights(const int64_t* keys, int64_t n, int32_t pitch, const int64_t* child_keys, int64_t n_child,
+                     const uint64_t* child_bits, const int32_t* child_rank, const int32_t* h_child,
+                     const int32_t* child_w /*nullable*/, int32_t* w, void* stream);
+int pcc_raht_forward(const int64_t* keys, int64_t n, int32_t pitch, const int64_t* child_keys, int64_t n_child,
+                     const uint64_t* child_bits, const int32_t* child_rank, const int32_t* h_child, const int32_t* off,
+                     const int32_t* child_w /*nullable*/, const int32_t* child_v, int32_t channels, const int32_t* h_steps,
+                     int32_t* w, int32_t* v, int32_t* coef, int64_t row_base, int64_t rows_total, void* stream);
+int pcc_raht_inverse(const int64_t* keys, int64_t n, int32_t pitch, const int64_t* child_keys, int64_t n_child,
+                     const uint64_t* child_bits, const int32_t* child_rank, const int32_t* h_child, const int32_t* off,
+                     const int32_t* child_w /*nullable*/, const int32_t* v, int32_t channels, const int32_t* h_steps,
+                     const int32_t* coef, int64_t row_base, int64_t rows_total, int32_t* child_v, int32_t* d_flag, void* stream);
+int pcc_raht_index(const int32_t* mask, const int32_t* off, int64_t n, int32_t level, int32_t channels,
+                   const int32_t* side /*nullable*/, int32_t* idx, int64_t row_base, int64_t rows_total, void* stream);
+int pcc_raht_hist(const int32_t* sym, const int32_t* grp, int64_t n_sym, int32_t groups, uint32_t* hist, void* stream);
+int pcc_raht_finish(const int32_t* values, int64_t n, int32_t channels, int32_t colour, uint8_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * 8f-4  nearest-neighbour association of the distortion report (replaces the two Open3D KD-trees and the per-point
  *       Python loop of PointCloudMetric.__init__, metrics/metric.py:36-43).  Exact, integer coordinates.
  *       a_xyz [n_a,3] int32 queries (any order; canonical order is fastest); b_xyz [n_b,3] int32 SORTED BY x ascending

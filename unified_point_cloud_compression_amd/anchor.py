@@ -1,0 +1,84 @@
+"""The octree + RAHT anchor codec: `compress_anchor` / `decompress_anchor`, this project's counterpart of the reference's
+`utils.compress_related("G-PCC", data, q_a, q_g, ...)` (`utils.py:505-529`: `tmc3 --transformType=0` with
+`--positionQuantizationScale=q_g --qp=q_a --qpChromaOffset=-2 --mergeDuplicatedPoints=1`), so that rate / PSNR points of the
+learned codec have something to stand against.  Not `tmc3` syntax, no bit-compatibility claim.
+
+Three device parts: positions scaled by `position_scale` and rounded to the nearest cell, the points of a cell merged with
+their mean colour (`voxelize.voxel_grid`); the lossless octree (`geometry.encode_geometry`); RAHT colour
+(`attributes.encode_attributes`).
+
+    container = u8 0xC1 | f64 position_scale | u32 len_geometry | geometry stream | attribute stream
+"""
+import math
+import struct
+
+import torch
+
+from . import lib as L
+from . import sparse as S
+from .attributes import decode_attributes, encode_attributes
+from .geometry import decode_geometry, encode_geometry
+from .voxelize import voxel_grid
+
+MAGIC = 0xC1
+HEADER = struct.Struct("<BdI")
+
+
+def container_size(len_geometry, len_attributes):
+    return HEADER.size + int(len_geometry) + int(len_attributes)
+
+
+def parse_container(data):
+    """(position_scale, geometry stream, attribute stream); PccError on a bad magic byte, scale or length."""
+    if len(data) < HEADER.size:
+        raise L.PccError("anchor stream truncated inside the header")
+    magic, scale, len_g = HEADER.unpack_from(data, 0)
+    if magic != MAGIC:
+        raise L.PccError(f"anchor stream: magic byte {magic:#x}, this build reads {MAGIC:#x}")
+    if not (math.isfinite(scale) and 0.0 < scale <= 1.0):
+        raise L.PccError(f"anchor stream: position scale {scale} outside (0, 1]")
+    if HEADER.size + len_g > len(data):
+        raise L.PccError("anchor stream truncated inside the geometry stream")
+    return scale, bytes(data[HEADER.size:HEADER.size + len_g]), bytes(data[HEADER.size + len_g:])
+
+
+def scaled_voxels(cloud, position_scale):
+    """The anchor's voxelisation: `voxel_grid` of xyz * position_scale (fp32) with unit cells centred on the integers, i.e.
+    positions rounded half up and the colours of a cell averaged."""
+    pts = cloud[:, :3].to(torch.float32)
+    if position_scale != 1.0:
+        pts = pts * float(position_scale)
+    return voxel_grid(pts.contiguous(), cloud[:, 3:6], 1.0, origin=(-0.5, -0.5, -0.5))
+
+
+@torch.no_grad()
+def compress_anchor(cloud, qp, position_scale=1.0, chroma_qp_offset=-2):
+    """[N, 6] GPU cloud (xyz, rgb in [0, 1]) -> bytes.  position_scale in (0, 1]: below 1 the points are scaled first; points
+    that then share a cell are merged with their mean colour.  qp, chroma_qp_offset: `attributes.encode_attributes`."""
+    what = "compress_anchor"
+    if not torch.is_tensor(cloud) or cloud.dim() != 2 or cloud.shape[1] != 6 or cloud.shape[0] == 0:
+        raise L.PccError(f"{what}: a non-empty [N, 6] cloud (xyz, rgb in [0, 1]) is required")
+    if not cloud.is_cuda:
+        raise L.PccError(f"{what} operates on GPU tensors only (no CPU fallback)")
+    scale = float(position_scale)
+    if not (math.isfinite(scale) and 0.0 < scale <= 1.0):
+        raise L.PccError(f"{what}: position_scale {position_scale} outside (0, 1]")
+    g = scaled_voxels(cloud, scale)
+    c4 = torch.cat([torch.zeros((g.index.shape[0], 1), dtype=torch.int32, device=cloud.device), g.index], dim=1).contiguous()
+    cs = S.coordset_from_coords(c4, 1)[0]                    # the grid's rows are ascending: canonical as they are
+    levels = torch.round(g.attrs.to(torch.float64) * 255.0).clamp_(0, 255).to(torch.uint8)
+    geometry = encode_geometry(cs)
+    attributes = encode_attributes(cs, qp, chroma_qp_offset, attrs=levels)
+    return HEADER.pack(MAGIC, scale, len(geometry)) + geometry + attributes
+
+
+@torch.no_grad()
+def decompress_anchor(data, device):
+    """bytes -> [n, 6] float32 on `device`: positions divided by the scale, colours / 255, in canonical order."""
+    scale, geometry, attributes = parse_container(data)
+    cs = decode_geometry(geometry, device, as_set=True)
+    levels = decode_attributes(attributes, cs)
+    dev = cs.device
+    xyz = cs.coords()[:cs.n, 1:].to(torch.float64) / torch.tensor(scale, dtype=torch.float64, device=dev)
+    rgb = levels.to(torch.float64) / torch.tensor(255.0, dtype=torch.float64, device=dev)
+    return torch.cat([xyz, rgb], dim=1).to(torch.float32)

@@ -169,37 +169,44 @@ def _key_of(x, y, z):
     return ((x + S.BIAS) << 32) | ((y + S.BIAS) << 16) | (z + S.BIAS)
 
 
-def _input_set(x):
-    """Canonical, de-duplicated pitch-1 single-batch CoordSet of the input, with exact bounds."""
+def canonical_rows(x, what="encode_geometry"):
+    """(set, perm, keep): the canonical, de-duplicated pitch-1 single-batch CoordSet of the input with exact bounds, and for
+    tensor rows the permutation / surviving rows of `sparse.coordset_from_coords` (None, None for a set, whose rows already
+    are canonical).  `what` names the caller in the refusals."""
     if isinstance(x, S.CoordSet):
         if x.ts != 1:
-            raise L.PccError(f"encode_geometry: a pitch-1 coordinate set is required, got pitch {x.ts}")
+            raise L.PccError(f"{what}: a pitch-1 coordinate set is required, got pitch {x.ts}")
         if x.bounds.bmax > 0:
-            raise L.PccError("encode_geometry codes one block: batched input is not supported")
+            raise L.PccError(f"{what} codes one block: batched input is not supported")
         if x.n == 0:
-            return x
+            return x, None, None
         b = S.bounds_of(x.coords())               # a set's own bounds may be conservative; the header needs the minimum
         if b.bmax > 0:
-            raise L.PccError("encode_geometry codes one block: batched input is not supported")
+            raise L.PccError(f"{what} codes one block: batched input is not supported")
         cs = S.CoordSet(x.keys, x.n, 1, b, on_lattice=True)        # a set of our own: the caller's object is not touched
         if b.lo == x.bounds.lo and b.hi == x.bounds.hi:
             cs.share_grid(x)
-        return cs
+        return cs, None, None
     if not torch.is_tensor(x) or x.dim() != 2 or x.shape[1] < 3:
-        raise L.PccError("encode_geometry: an [N, >= 3] tensor or a CoordSet is required")
+        raise L.PccError(f"{what}: an [N, >= 3] tensor or a CoordSet is required")
     if not x.is_cuda:
-        raise L.PccError("encode_geometry operates on GPU tensors only (no CPU fallback)")
+        raise L.PccError(f"{what} operates on GPU tensors only (no CPU fallback)")
     xyz = x[:, :3]
     xyz = torch.floor(xyz).to(torch.int32) if xyz.dtype.is_floating_point else xyz.to(torch.int32)
     c4 = torch.cat([torch.zeros((x.shape[0], 1), dtype=torch.int32, device=x.device), xyz], dim=1).contiguous()
-    cs = S.coordset_from_coords(c4, 1)[0]
+    cs, perm, keep = S.coordset_from_coords(c4, 1)
     if cs.bounds.bmax > 0:
-        raise L.PccError("encode_geometry codes one block: batched input is not supported")
-    return cs
+        raise L.PccError(f"{what} codes one block: batched input is not supported")
+    return cs, perm, keep
 
 
-def _level_sets(cs, origin, depth):
-    """[level 0 (root), ..., level depth (the voxels)] as CoordSets of origin-relative cells."""
+def _input_set(x):
+    """Canonical, de-duplicated pitch-1 single-batch CoordSet of the input, with exact bounds."""
+    return canonical_rows(x)[0]
+
+
+def level_sets(cs, origin, depth):
+    """[level 0 (root), ..., level depth (the voxels)] as CoordSets of origin-relative cells (shared with attributes.py)."""
     dev = cs.device
     ext = [cs.bounds.hi[i] - origin[i] for i in range(3)]
     if all(v == 0 for v in origin):
@@ -255,7 +262,7 @@ def encode_geometry(x, segment_nodes=SEGMENT_NODES, timings=None):
     dev = cs.device
     lib = L.load()
     with torch.cuda.device(dev):
-        sets = _level_sets(cs, origin, depth)
+        sets = level_sets(cs, origin, depth)
         hw = lib.pcc_geom_hist_words()
         nodes = [s.n for s in sets[:depth]]
         at = np.concatenate([[0], np.cumsum(nodes)]).tolist()

@@ -155,6 +155,16 @@ SIGNATURES = {
     "pcc_geom_dec_table_bytes": (_i64, []),
     "pcc_geom_tables": (C.c_int, [_p, C.POINTER(C.c_uint32), _p, _p, _p]),
     "pcc_geom_state_update": (C.c_int, [_p, _p, _p]),
+    "pcc_raht_isqrt": (_u64, [_u64]),
+    "pcc_raht_butterfly": (C.c_int, [C.c_uint32, C.c_uint32, _i64, _i64, C.POINTER(_i64)]),
+    "pcc_raht_prepare": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p]),
+    "pcc_raht_mask": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p]),
+    "pcc_raht_weights": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _p]),
+    "pcc_raht_forward": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _p, _i32, C.POINTER(_i32), _p, _p, _p, _i64, _i64, _p]),
+    "pcc_raht_inverse": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _p, _i32, C.POINTER(_i32), _p, _i64, _i64, _p, _p, _p]),
+    "pcc_raht_index": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p, _i64, _i64, _p]),
+    "pcc_raht_hist": (C.c_int, [_p, _p, _i64, _i32, _p, _p]),
+    "pcc_raht_finish": (C.c_int, [_p, _i64, _i32, _i32, _p, _p]),
     "pcc_conv_pairs_supported": (C.c_int, [_i32, _i32, _i32]),
     "pcc_pair_plan_ws_bytes": (_sz, [_i64, _i32]),
     "pcc_pair_plan_rank": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _sz, _p]),
