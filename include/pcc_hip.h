@@ -706,6 +706,28 @@ int pcc_normals_grid(const int64_t* keys, int64_t n, const uint64_t* grid_bits /
                      float* normals /*[n,3]*/, int32_t* counts /*nullable*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 8f-6  the two radius kernels of the PCQM quality metric (Meynet, Nehme, Digne, Lavoue, QoMEX 2020; the reference
+ *       reads it from an external binary, utils.py:270-322; restated on the voxel lattice, see metrics.py `pcqm`).
+ *       keys / grid_bits / grid_rank / h_grid: a canonical set at pitch 1 and its pcc_grid_build index, or NULL bits:
+ *       binary search over the keys, same bits out.  Neighbourhoods as in pcc_normals_grid: |d|^2 <= lim, the point itself
+ *       included; 0 <= lim <= 288 (radius <= 17), else an error.  No atomics, every sum in an order fixed by the set.
+ *       pcc_curvature_grid: out[n] fp64 = the absolute mean curvature, at the point's foot, of the quadric
+ *       z = a x^2 + b xy + c y^2 + d x + e y + f fitted (unweighted least squares, 6 x 6 normal equations in fp64 summed in
+ *       the order dx, dy, dz ascending, Cholesky) to the neighbourhood in the frame (u, v, n): n the normal of
+ *       pcc_normals_grid kept in fp64, u = normalise(e x n) with e the axis of the smallest |n| (first on a tie), v = n x u.
+ *       Fewer than 6 members, or a pivot <= 1e-12 x the largest diagonal entry: 0.  (Offsets only: the rank array is not read.)
+ *       pcc_pcqm_features: table [n,10] fp64 holds per point (curvature, lightness, a, b, chroma), each as the pair (own
+ *       value, value of the paired point).  out [n,8] fp64 = the features f1 .. f8 from the Gaussian-weighted
+ *       (w = exp(-|d|^2 inv_two_sigma2)) means, deviations and covariance over the neighbourhood, every attribute shifted
+ *       by the centre's own value before it is summed.  One wave per point, rows gathered through the rank array.
+ * ---------------------------------------------------------------------------------------- */
+int pcc_curvature_grid(const int64_t* keys, int64_t n, const uint64_t* grid_bits /*nullable*/, const int32_t* grid_rank,
+                       const int32_t* h_grid, int32_t lim, double* out /*[n]*/, void* stream);
+int pcc_pcqm_features(const int64_t* keys, int64_t n, const uint64_t* grid_bits /*nullable*/, const int32_t* grid_rank,
+                      const int32_t* h_grid, int32_t lim, double inv_two_sigma2, const double* table /*[n,10]*/,
+                      double* out /*[n,8]*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * 9    training batches: cube slicing and the per-step augmented batch (reference data/dataloader.py:168-208
  *      StaticDataset.slice_into_cubes; data/transform.py:32-54 ColorJitter, :57-123 RandomRotate; train.py:199-208
  *      sparse_collate + sparse_quantize).

@@ -5,7 +5,9 @@ ALL items, so a vox11 frame's >= 8 blocks spread over the node), each rank codes
 them from plain coordinates, measures bits and the block-local D1 numerators on its GPU, and one all_gather of fixed-size
 records ends the sweep; per-frame totals are summed from the block records (`evaluate.py:102-195` without the external tools).
 --d2 adds the block-local point-to-plane (D2, `pc_error`'s d2_psnr) numerators, normals estimated per block with radius 5
-(`evaluate.py:153`), gathered in a second record exchange.  --ply PATH [PATH ...] loads real frames (`evaluate.py:30-37`,
+(`evaluate.py:153`), gathered in a second record exchange.  --pcqm adds the PCQM figure (`evaluate.py:168-171`;
+`metrics.pcqm_features`, the published metric restated, r = 0.004 x the frame's resolution, h = 2 r), block-local like D2: the
+per-point features of every block are pooled over the frame's points, gathered in a record exchange of its own.  --ply PATH [PATH ...] loads real frames (`evaluate.py:30-37`,
 `ply.read_ply`) instead of synthetic ones; --bits then gives their resolution for the PSNR (one value for all, or one per file).
 Single process: python tools/eval_frames.py [--bits 9 9 10] [--d2]
 N GPUs:  python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/eval_frames.py"""
@@ -27,6 +29,7 @@ ap.add_argument("--bits", type=int, nargs="+", default=None, help="grid bits of 
 ap.add_argument("--ply", nargs="+", default=None, metavar="PATH", help="PLY frames to evaluate instead of synthetic ones")
 ap.add_argument("--block-size", type=int, default=None, help="default: 1024 for <= 10 bits, 512 above (evaluate.py:39-46)")
 ap.add_argument("--d2", action="store_true", help="also the block-local point-to-plane (D2) numerators and PSNR")
+ap.add_argument("--pcqm", action="store_true", help="also the block-local PCQM figure (restated metric, see metrics.pcqm_features)")
 args = ap.parse_args()
 if args.ply:
     args.bits = args.bits or [10]
@@ -95,6 +98,7 @@ def blocks(i):
 
 
 d2_local = {}                                          # (frame, block) -> D2 numerators (--d2)
+pcqm_local = {}                                        # (frame, block) -> points, then f3, f4, f6 summed over them (--pcqm)
 
 
 def process(f, b):
@@ -108,6 +112,9 @@ def process(f, b):
     rep = metrics.pointcloud_metrics(x, rec, resolution=(1 << args.bits[f]) - 1, point_to_plane=args.d2)
     if args.d2:
         d2_local[(f, b)] = (rep["AB_d2_mse"] * x.shape[0], x.shape[0], rep["BA_d2_mse"] * rec.shape[0], rec.shape[0])
+    if args.pcqm:
+        pq = metrics.pcqm_features(x, rec, radius=metrics.PCQM_RADIUS_FRACTION * ((1 << args.bits[f]) - 1))
+        pcqm_local[(f, b)] = (pq["n"],) + tuple(pq[k] * pq["n"] for k in metrics.PCQM_WEIGHTS)
     return (f, b, x.shape[0], t1 - t0, t2 - t1, metrics.count_bits([strings]), rec.shape[0],
             rep["AB_mse"] * x.shape[0], x.shape[0], rep["BA_mse"] * rec.shape[0], rec.shape[0])
 
@@ -127,6 +134,13 @@ if args.d2:                                            # D2 numerators: one more
         t = totals[int(r[0])]
         for k, v in zip(("se2_ab", "n2_ab", "se2_ba", "n2_ba"), r[2:]):
             t[k] = t.get(k, 0.0) + float(v)
+if args.pcqm:                                          # pooled features: one more exchange of fixed-size records
+    for r in frames.gather_records([(f, b) + v for (f, b), v in sorted(pcqm_local.items())], coll, n_fields=6):
+        t = totals[int(r[0])]
+        for k, v in zip(("pcqm_n",) + tuple("pcqm_" + k for k in metrics.PCQM_WEIGHTS), r[2:]):
+            t[k] = t.get(k, 0.0) + float(v)
+    for t in totals.values():
+        t["pcqm"] = sum(w * t["pcqm_" + k] for k, w in metrics.PCQM_WEIGHTS.items()) / max(t["pcqm_n"], 1.0)
 torch.cuda.synchronize()
 wall = torch.tensor([time.time() - t_wall0], dtype=torch.float64, device=coll)
 if world > 1:
@@ -134,7 +148,7 @@ if world > 1:
 wall = float(wall.item())
 if rank == 0:
     print(f"{'frame':>5s} {'blocks':>6s} {'points':>9s} {'enc ms':>8s} {'dec ms':>8s} {'bpp':>7s} {'decoded':>9s} {'D1 dB':>7s}"
-          + (f" {'D2 dB':>7s}" if args.d2 else ""))
+          + (f" {'D2 dB':>7s}" if args.d2 else "") + (f" {'PCQM':>9s}" if args.pcqm else ""))
     import math
     for f, t in sorted(totals.items()):
         res = (1 << args.bits[f]) - 1
@@ -145,6 +159,8 @@ if rank == 0:
         if args.d2:                                    # `pc_error`: 3 res^2 over the worse direction's mse
             mse2 = max(t["se2_ab"] / max(t["n2_ab"], 1.0), t["se2_ba"] / max(t["n2_ba"], 1.0))
             line += f" {10 * math.log10(3 * res * res / mse2) if mse2 > 0 else float('inf'):7.2f}"
+        if args.pcqm:
+            line += f" {t['pcqm']:9.6f}"
         print(line)
     tot = sum(t["n_points"] for t in totals.values())
     busy = sum(t["t_encode"] + t["t_decode"] for t in totals.values())

@@ -14,18 +14,11 @@
 // the smallest eigenvalue is normalised, rounded to fp32 and flipped so that its largest-magnitude component is positive
 // (first axis on a tie).  Fewer than 3 neighbours: (0, 0, 1), as Open3D's EstimateNormals.  Every step is integer or
 // order-fixed, so the grid and search paths give the same bits, call after call.
-#include "pcc_common.h"
+#include "pcc_normals.h"
 
 static constexpr int NRM_MAX_LIM = 63;          // r <= 8: column half-height <= 7, a z field <= 15 bits
 static constexpr int NRM_MAX_R = 7;             // floor(sqrt(NRM_MAX_LIM))
 static constexpr int NRM_SIDE = 2 * NRM_MAX_R + 1;
-static constexpr int NRM_JACOBI_SWEEPS = 8;
-
-struct NrmArgs {
-  const long long* keys; int n;
-  PccGrid g;                                     // g.bits == nullptr: binary search
-  int lim, R;                                    // R = floor(sqrt(lim))
-};
 
 struct NrmMoments {
   int n, sx, sy, sz, sxx, syy, szz, sxy, sxz, syz;
@@ -84,40 +77,6 @@ __device__ inline void nrm_column(const NrmArgs& a, NrmMoments& m, long long b, 
   if (f) nrm_add_column(m, f, zlo - Z, dx, dy);
 }
 
-// eigenvector of the smallest eigenvalue of the symmetric A (fp64, overwritten) by cyclic Jacobi with a fixed sweep count
-__device__ inline void nrm_smallest_eigvec(double A[3][3], double v[3]) {
-  double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-  for (int sweep = 0; sweep < NRM_JACOBI_SWEEPS; ++sweep) {
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      const int p = r == 2 ? 1 : 0, q = r == 0 ? 1 : 2, o = 3 - p - q;
-      const double apq = A[p][q];
-      if (apq == 0.0) continue;
-      const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-      const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-      const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-      A[p][p] -= t * apq;
-      A[q][q] += t * apq;
-      A[p][q] = A[q][p] = 0.0;
-      const double aop = A[o][p], aoq = A[o][q];
-      A[o][p] = A[p][o] = c * aop - s * aoq;
-      A[o][q] = A[q][o] = s * aop + c * aoq;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const double vp = V[k][p], vq = V[k][q];
-        V[k][p] = c * vp - s * vq;
-        V[k][q] = s * vp + c * vq;
-      }
-    }
-  }
-  int j = 0;                                     // (selects, not an indexed read: keeps A and V in registers)
-  double lo = A[0][0];
-  if (A[1][1] < lo) { lo = A[1][1]; j = 1; }
-  if (A[2][2] < lo) j = 2;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) v[k] = j == 0 ? V[k][0] : (j == 1 ? V[k][1] : V[k][2]);
-}
-
 __global__ void __launch_bounds__(256) k_normals(NrmArgs a, float* __restrict__ normals, int* __restrict__ counts) {
   __shared__ signed char s_zr[NRM_SIDE * NRM_SIDE];            // half-height of column (dx, dy), -1: outside the radius
   for (int i = threadIdx.x; i < NRM_SIDE * NRM_SIDE; i += blockDim.x) {
@@ -168,18 +127,8 @@ extern "C" int pcc_normals_grid(const int64_t* keys, int64_t n, const uint64_t* 
   PCC_REQUIRE(n >= 0 && n < (1ll << 31), "pcc_normals_grid: too many rows");
   if (n == 0) return PCC_OK;
   PCC_REQUIRE(keys && normals, "pcc_normals_grid: NULL array");
-  NrmArgs a = NrmArgs();
-  if (grid_bits) {
-    PCC_REQUIRE(h_grid, "pcc_normals_grid: grid needs its 8 host parameters");
-    PCC_REQUIRE(h_grid[6] == 1, "pcc_normals_grid: grid pitch %d, the set must be at pitch 1", h_grid[6]);
-    a.g.bits = (const unsigned long long*)grid_bits;
-    for (int i = 0; i < 3; ++i) { a.g.lo[i] = h_grid[i]; a.g.dims[i] = h_grid[3 + i]; }
-    a.g.ts_log2 = 0;
-    a.g.nbatch = h_grid[7];
-  }
-  a.keys = (const long long*)keys; a.n = (int)n; a.lim = lim;
-  a.R = 0;
-  while ((a.R + 1) * (a.R + 1) <= lim) ++a.R;
+  NrmArgs a;
+  PCC_TRY(nrm_fill_args(a, "pcc_normals_grid", keys, n, grid_bits, nullptr, h_grid, lim));
   k_normals<<<(unsigned)pcc_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(a, normals, counts);
   PCC_LAUNCH_CHECK();
   return PCC_OK;

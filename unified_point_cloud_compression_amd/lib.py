@@ -173,6 +173,8 @@ SIGNATURES = {
                                      C.c_float, _i32, _p, _p]),
     "pcc_nn_sorted_x": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _p]),
     "pcc_normals_grid": (C.c_int, [_p, _i64, _p, C.POINTER(_i32), _i32, _p, _p, _p]),
+    "pcc_curvature_grid": (C.c_int, [_p, _i64, _p, _p, C.POINTER(_i32), _i32, _p, _p]),
+    "pcc_pcqm_features": (C.c_int, [_p, _i64, _p, _p, C.POINTER(_i32), _i32, C.c_double, _p, _p, _p]),
     "pcc_cube_keys": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p]),
     "pcc_cube_regroup": (C.c_int, [_p, _p, _p, _i64, _p, _p, _p]),
     "pcc_aug_gray_sums": (C.c_int, [_p, _i64, _p, _p, _i32, _p, _p, _i32, _p, _p, _p]),

@@ -5,7 +5,10 @@ The nearest-neighbour association -- two Open3D KD-trees and a Python loop per p
 GPU (`pcc_nn_sorted_x`); the per-point arithmetic after it is a handful of float64 tensor ops on the device.
 
 The point-to-plane (D2) figures the reference reads back from MPEG `pc_error` (`utils.py:189-267`) use normals estimated
-with a radius search (`evaluate.py:153`); `estimate_normals` computes them on the GPU (`pcc_normals_grid`)."""
+with a radius search (`evaluate.py:153`); `estimate_normals` computes them on the GPU (`pcc_normals_grid`).
+
+PCQM, which the reference reads back from another external binary (`utils.py:270-322`), is restated on the voxel lattice:
+`pcqm` / `pcqm_features` (`pcc_curvature_grid`, `pcc_pcqm_features`)."""
 import math
 
 import torch
@@ -215,6 +218,139 @@ def d2_psnr(a_xyz, b_xyz, resolution=1023, radius=5.0):
     ab = _d2_psnr(_d2_mse(a, b, nb, nearest(a, b)[1]), resolution)
     ba = _d2_psnr(_d2_mse(b, a, na, nearest(b, a)[1]), resolution)
     return ab, ba, min(ab, ba)
+
+
+# ---- PCQM -----------------------------------------------------------------------------------------------------------------
+# Constants of the published metric (Meynet, Nehme, Digne, Lavoue, "PCQM: a full-reference quality metric for colored 3D
+# point clouds", QoMEX 2020), restated from the paper.  The binary the reference shells out to (`utils.py:270-322`) and its
+# source are not available here, so none of them is read from it: they are unpinned.
+PCQM_MAX_RADIUS = 17.0                                   # of h; a z field of the feature kernel is then <= 33 bits
+PCQM_RADIUS_FRACTION = 0.004                             # the reference's `-r 0.004`
+PCQM_RADIUS_FACTOR = 2.0                                 # the reference's `-rx 2.0`
+PCQM_K, PCQM_C1, PCQM_C2, PCQM_C3, PCQM_C4, PCQM_C5 = 1.0, 0.002, 0.1, 0.1, 0.002, 0.008    # (pcc_pcqm.hip holds the same)
+PCQM_WEIGHTS = {"f3": 0.0057, "f4": 0.9771, "f6": 0.0172}
+_SRGB_TO_XYZ = ((0.4124564, 0.3575761, 0.1804375), (0.2126729, 0.7151522, 0.0721750), (0.0193339, 0.1191920, 0.9503041))
+_D65_WHITE = (0.95047, 1.0, 1.08883)
+
+
+def rgb_to_lab(rgb):
+    """8-bit levels round(rgb * 255) (clamped) -> CIE Lab, float64 [n, 3]: sRGB -> linear (0.04045 / 12.92 / 2.4 form) ->
+    XYZ (D65) -> Lab with white (0.95047, 1, 1.08883)."""
+    c = torch.round(rgb.to(torch.float64) * 255.0).clamp(0, 255) / 255.0
+    lin = torch.where(c <= 0.04045, c / 12.92, ((c + 0.055) / 1.055) ** 2.4)
+    xyz = lin @ torch.tensor(_SRGB_TO_XYZ, dtype=torch.float64, device=rgb.device).t()
+    t = xyz / torch.tensor(_D65_WHITE, dtype=torch.float64, device=rgb.device)
+    f = torch.where(t > (6.0 / 29.0) ** 3, t.clamp_min(0).pow(1.0 / 3.0), t / (3.0 * (6.0 / 29.0) ** 2) + 4.0 / 29.0)
+    return torch.stack([116.0 * f[:, 1] - 16.0, 500.0 * (f[:, 0] - f[:, 1]), 200.0 * (f[:, 1] - f[:, 2])], dim=1)
+
+
+def _pcqm_radii(radius, radius_fraction, radius_factor, extent=None):
+    """(r, h) of a PCQM call, checked: 0 < r <= h <= 17.  radius None: r = radius_fraction x extent."""
+    r = float(radius) if radius is not None else float(radius_fraction) * float(extent)
+    h = float(radius_factor) * r
+    if not (0.0 < r <= h <= PCQM_MAX_RADIUS):                      # (also refuses NaN)
+        raise L.PccError(f"pcqm: radii r = {r:g}, h = {h:g} unsupported (0 < r <= h <= {PCQM_MAX_RADIUS:g})")
+    return r, h
+
+
+def _pcqm_lim(radius):
+    """The integer neighbourhood rule of `estimate_normals`: |d|^2 <= ceil(radius^2) - 1."""
+    return math.ceil(radius * radius) - 1
+
+
+def _set_curvature(cs, radius):
+    """float64 [n]: the curvature field of a canonical pitch-1 set at `radius`, in canonical order (`pcc_curvature_grid`)."""
+    out = torch.empty(cs.n, dtype=torch.float64, device=cs.device)
+    if cs.n:
+        L.call("pcc_curvature_grid", L.ptr(cs.keys), cs.n, *S.grid_args(cs.grid() if S.USE_GRID else None),
+               _pcqm_lim(radius), L.ptr(out), L.stream())
+    return out
+
+
+def curvature(xyz, radius):
+    """The curvature field PCQM compares (step 1 of `pcqm_features`): float64 [N] in the caller's row order, a duplicate
+    row taking the value of its cell.  xyz: GPU [N, >= 3] voxel coordinates; 0 < radius <= 17."""
+    _pcqm_radii(radius, None, 1.0)
+    cs, _, _, coords = _canonical_set(torch.as_tensor(xyz)[:, :3])
+    rho = _set_curvature(cs, float(radius))
+    if coords is not None:
+        rho = rho[torch.searchsorted(cs.keys[:cs.n], S.pack_keys(coords)[:coords.shape[0]])]
+    return rho
+
+
+def pcqm_features(source, reconstruction, radius=None, radius_fraction=PCQM_RADIUS_FRACTION, radius_factor=PCQM_RADIUS_FACTOR,
+                  per_point=False):
+    """PCQM (Meynet, Nehme, Digne, Lavoue, QoMEX 2020) of a reconstruction D against its source R, the figure the
+    reference's evaluation prints first (`evaluate.py:168-171`), with its eight features.  source / reconstruction: GPU
+    [N, 6] tensors, voxel xyz then rgb in [0, 1]; duplicates are dropped, the first row of a cell wins.
+
+    This is the published metric RESTATED on a voxel lattice, not the binary the reference calls (`utils.py:270-322`), which
+    is not available here: the constants and weights below are taken from the paper, not read from that binary, and so are
+    unpinned; a figure of this function is not comparable digit for digit with one the reference printed.
+
+    r = `radius` in voxels when given, else radius_fraction x the largest extent of R's bounding box (the reference's
+    `-r 0.004`); h = radius_factor x r (`-rx 2.0`); 0 < r <= h <= 17, else PccError.  All neighbourhoods follow the integer
+    rule of `estimate_normals`: the offsets d with |d|^2 <= ceil(rho^2) - 1, the centre included.
+      1. Curvature field of each cloud over N(q, r): the normal of `estimate_normals` kept in fp64; in-plane axes u =
+         normalise(e x n), e the axis where |n| is smallest (first on a tie), v = n x u; an unweighted least-squares fit of
+         z = a x^2 + b xy + c y^2 + d x + e y + f to the offsets in that frame (6 x 6 normal equations in fp64, summed in
+         the order dx, dy, dz ascending, Cholesky); the value is |((1 + e^2) a - d e b + (1 + d^2) c) / (1 + d^2 + e^2)^1.5|,
+         the absolute mean curvature of the fitted surface at q's foot, and 0 with fewer than 6 neighbours or a pivot
+         <= 1e-12 x the largest diagonal entry.
+      2. Correspondence: nn(q) = the nearest point of D to q (`nearest`, ties to the smallest canonical row).  A DEPARTURE
+         from the published method, which projects q onto a quadric fitted to D: on a lattice the distorted samples are
+         lattice points, so the nearest one stands for the projection.
+      3. Colour: `rgb_to_lab` of the 8-bit levels.
+      4. Per point q of R the pairs (R's value at q, D's value at nn(q)) of curvature, L, a, b and C = hypot(a, b).
+      5. At every point p of R, over N_R(p, h) with weights exp(-|d|^2 / (2 sigma^2)), sigma = h / 2: means, standard
+         deviations (variance clamped at 0) and covariance of the curvature and L pairs, means of the a, b, C pairs (every
+         attribute shifted by p's own value before it is summed; `pcc_pcqm_features`).
+      6. f1 = |mu_R - mu_D| / (max(mu_R, mu_D) + k), f2 the same of sigma, f3 = |sigma_R sigma_D - sigma_RD| /
+         (sigma_R sigma_D + k) on curvature; f4 = 1 - 1 / (c1 (muL_R - muL_D)^2 + 1), f5 = 1 - (2 sL_R sL_D + c2) /
+         (sL_R^2 + sL_D^2 + c2), f6 = 1 - (sL_RD + c3) / (sL_R sL_D + c3) on lightness; f7 = 1 - 1 / (c4 dC^2 + 1),
+         f8 = 1 - 1 / (c5 dH^2 + 1), dH^2 = max(0, da^2 + db^2 - dC^2) on the chroma means.
+      7. Each feature is averaged over R's points; PCQM = 0.0057 f3 + 0.9771 f4 + 0.0172 f6.
+    Not covered: a symmetric variant, float positions.
+
+    Returns {"pcqm", "f1" .. "f8", "r", "h", "n"}; with per_point also "features", float64 [N, 8] in the caller's row order
+    of R (a duplicate row takes the values of its cell)."""
+    if radius is not None:
+        _pcqm_radii(radius, radius_fraction, radius_factor)          # (raises before any work)
+    sa, sb = torch.as_tensor(source), torch.as_tensor(reconstruction)
+    if sa.dim() != 2 or sb.dim() != 2 or sa.shape[1] < 6 or sb.shape[1] < 6:
+        raise L.PccError("pcqm: both clouds need colour ([N, 6]: voxel xyz, then rgb in [0, 1])")
+    if sa.shape[0] == 0 or sb.shape[0] == 0:
+        raise L.PccError("pcqm: empty cloud")
+    if not (sa.is_cuda and sb.is_cuda):
+        raise L.PccError("pcqm: GPU tensors required (no CPU fallback)")
+    ca, a_pts, (a_rgb,), a_coords = _canonical_set(sa[:, :3], sa[:, 3:6])
+    cb, b_pts, (b_rgb,), _ = _canonical_set(sb[:, :3], sb[:, 3:6])
+    extent = None
+    if radius is None:
+        extent = int((a_pts.max(dim=0).values - a_pts.min(dim=0).values).max())
+    r, h = _pcqm_radii(radius, radius_fraction, radius_factor, extent)
+    nn = nearest(a_pts, b_pts)[1].long()
+    lab_a, lab_b = rgb_to_lab(a_rgb), rgb_to_lab(b_rgb)[nn]
+    table = torch.stack([_set_curvature(ca, r), _set_curvature(cb, r)[nn], lab_a[:, 0], lab_b[:, 0], lab_a[:, 1], lab_b[:, 1],
+                         lab_a[:, 2], lab_b[:, 2], torch.hypot(lab_a[:, 1], lab_a[:, 2]), torch.hypot(lab_b[:, 1], lab_b[:, 2])],
+                        dim=1).contiguous()
+    feats = torch.empty((ca.n, 8), dtype=torch.float64, device=table.device)
+    L.call("pcc_pcqm_features", L.ptr(ca.keys), ca.n, *S.grid_args(ca.grid() if S.USE_GRID else None), _pcqm_lim(h),
+           2.0 / (h * h), L.ptr(table), L.ptr(feats), L.stream())
+    means = feats.mean(dim=0).tolist()
+    out = {"f%d" % (k + 1): means[k] for k in range(8)}
+    out["pcqm"] = sum(w * out[f] for f, w in PCQM_WEIGHTS.items())
+    out.update(r=r, h=h, n=ca.n)
+    if per_point:
+        if a_coords is not None:
+            feats = feats[torch.searchsorted(ca.keys[:ca.n], S.pack_keys(a_coords)[:a_coords.shape[0]])]
+        out["features"] = feats
+    return out
+
+
+def pcqm(source, reconstruction, radius=None, radius_fraction=PCQM_RADIUS_FRACTION, radius_factor=PCQM_RADIUS_FACTOR):
+    """The PCQM score of `pcqm_features` (0 = identical; larger = worse)."""
+    return pcqm_features(source, reconstruction, radius, radius_fraction, radius_factor)["pcqm"]
 
 
 def count_bits(strings):
