@@ -26,16 +26,12 @@ def _factorised(channels):
 
 def _decode(em, data, rows, c, idx, form):
     """(symbols, status) of `data` through pcc_rans_decode_streams_form."""
-    from unified_point_cloud_compression_amd import lib as L
+    from unified_point_cloud_compression_amd import rans as R
     d = dev()
-    cdf, sizes, offs = (x.to(d).contiguous() for x in (em._quantized_cdf, em._cdf_length, em._offset))
     buf = em.upload_string(data, d).device_buf
-    tab = em._dec_table(d)
     sym = torch.full((rows, c), -(1 << 30), dtype=torch.int32, device=d)
     status = torch.zeros(1, dtype=torch.int32, device=d)
-    L.call("pcc_rans_decode_streams_form", L.ptr(buf), len(data), L.ptr(idx) if idx is not None else None, rows, c,
-           *em._segments_of(data, rows, c), L.ptr(cdf), cdf.shape[1], L.ptr(sizes), L.ptr(offs), L.ptr(tab), tab.numel(),
-           L.ptr(sym), L.ptr(status), L.stream(), form)
+    R.decode(em.tables(d), buf, len(data), idx, rows, c, *em._segments_of(data, rows, c), sym, status, form)
     torch.cuda.synchronize()
     return sym, int(status.item())
 

@@ -9,16 +9,15 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from unified_point_cloud_compression_amd import lib as L
+from unified_point_cloud_compression_amd import rans as R
 from unified_point_cloud_compression_amd.compressai.entropy_models import GaussianConditional, get_scale_table
 
 SYMBOLS = 1400
 REPEATS = 7
 dev = torch.device("cuda:0")
-lib = L.load()
 gc = GaussianConditional(None).to(dev)
 gc.update_scale_table(get_scale_table(), force=True)
-cdf, sizes, offs = (x.to(dev).contiguous() for x in (gc._quantized_cdf, gc._cdf_length, gc._offset))
-tab, enc = gc._dec_table(dev), gc._enc_table(dev)
+tabs = gc.tables(dev)
 print(f"# {L.device_info()}  symbols per stream {SYMBOLS}, table rows idx 0..47 uniform, best of {REPEATS} launches (HIP events)")
 print(f"{'streams':>8s} {'bits/sym':>9s} {'lane us':>10s} {'wave us':>10s} {'lane ns/sym':>12s} {'wave ns/sym':>12s} {'wave/lane':>10s}")
 for ns in [int(a) for a in sys.argv[1:]] or [96, 1408, 4096, 16384, 65536]:
@@ -29,16 +28,13 @@ for ns in [int(a) for a in sys.argv[1:]] or [96, 1408, 4096, 16384, 65536]:
     g = torch.Generator(device=dev).manual_seed(ns)
     idx = torch.randint(0, 48, (rows, c), generator=g, device=dev, dtype=torch.int32)
     sym = torch.round(torch.randn((rows, c), generator=g, device=dev) * gc.scale_table.to(dev)[idx.long()]).to(torch.int32)
-    per = lib.pcc_rans_stream_symbols(rows, c, c, segs)
-    assert per == SYMBOLS
-    out = torch.zeros(lib.pcc_rans_container_max_bytes(per, ns) + 8, dtype=torch.uint8, device=dev)
+    plan = R.Plan(rows, c, c, segs)
+    assert plan.per_stream == SYMBOLS
+    out = torch.empty(plan.capacity, dtype=torch.uint8, device=dev)
     nb = L.counter()
-    ws = L.workspace(lib.pcc_rans_streams_ws_bytes(per, ns), dev)
-    L.call("pcc_rans_encode_streams", L.ptr(sym), L.ptr(idx), rows, c, c, segs, L.ptr(cdf), cdf.shape[1], L.ptr(sizes),
-           L.ptr(offs), L.ptr(enc), L.ptr(out), L.cptr(nb), L.ptr(ws), ws.numel(), L.stream())
-    torch.cuda.synchronize()
+    R.encode(tabs, plan, sym, idx, out, nb)
     nbytes = int(L.read(nb)[0])
-    out[nbytes:nbytes + 8].zero_()                        # the decoder looks up to two words ahead
+    out = R.upload_string(out[:nbytes].cpu().numpy().tobytes(), dev).device_buf        # padded as the decoder wants it
     res, best = {}, {}
     for form in (1, 2):
         dec = torch.zeros_like(sym)
@@ -47,8 +43,7 @@ for ns in [int(a) for a in sys.argv[1:]] or [96, 1408, 4096, 16384, 65536]:
         for _ in range(REPEATS + 1):                      # the first launch is the warm-up
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
-            L.call("pcc_rans_decode_streams_form", L.ptr(out), nbytes, L.ptr(idx), rows, c, c, segs, L.ptr(cdf), cdf.shape[1],
-                   L.ptr(sizes), L.ptr(offs), L.ptr(tab), tab.numel(), L.ptr(dec), L.ptr(status), L.stream(), form)
+            R.decode(tabs, out, nbytes, idx, rows, c, c, segs, dec, status, form)
             b.record()
             torch.cuda.synchronize()
             times.append(a.elapsed_time(b) * 1e3)

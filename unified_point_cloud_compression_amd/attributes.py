@@ -29,6 +29,7 @@ import torch
 
 from . import geometry as G
 from . import lib as L
+from . import rans as R
 from . import sparse as S
 
 MAGIC = 0xB3               # format version 1
@@ -125,7 +126,7 @@ def choose_members(hist):
 
 def segments_for(symbols, segment_symbols=SEGMENT_SYMBOLS):
     """rANS streams of the symbol vector."""
-    return max(1, min(-(-int(symbols) // max(1, int(segment_symbols))), MAX_STREAMS))
+    return R.segments_for(symbols, segment_symbols, MAX_STREAMS)
 
 
 def _zigzag(v):
@@ -207,31 +208,9 @@ def parse_header(data):
 # ------------------------------------------------------------------------------------------------------------------------
 # device side
 # ------------------------------------------------------------------------------------------------------------------------
-def _np_ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-_CONST = {}
-
-
-def _constants(dev):
-    """(cdf, sizes, offsets, encoder table, decoder table) of the family on the device: one upload per device."""
-    const = _CONST.get(str(dev))
-    if const is None:
-        lib = L.load()
-        cdf = table_family()[0]
-        enc = np.zeros(cdf.size * 2, dtype=np.uint64)
-        L.check(lib.pcc_rans_build_enc_table(_np_ptr(cdf), N_TABLES, cdf.shape[1], _np_ptr(TABLE_SIZES), _np_ptr(enc)),
-                "pcc_rans_build_enc_table")
-        dec = np.zeros(lib.pcc_rans_dec_table_bytes(N_TABLES, _np_ptr(TABLE_SIZES)), dtype=np.uint8)
-        L.check(lib.pcc_rans_build_dec_table(_np_ptr(cdf), N_TABLES, cdf.shape[1], _np_ptr(TABLE_SIZES), _np_ptr(dec)),
-                "pcc_rans_build_dec_table")
-        const = _CONST[str(dev)] = tuple(torch.from_numpy(a).to(dev) for a in (cdf, TABLE_SIZES, TABLE_OFFSETS, enc.view(np.int64), dec))
-    return const
-
-
-def _align8(v):
-    return (int(v) + 7) // 8 * 8
+def _tables(dev):
+    """The family on the device, with its encoder entries and decoder blob: one upload per device."""
+    return R.fixed_tables("raht", dev, table_family()[0], TABLE_SIZES, TABLE_OFFSETS, enc=True, dec=True)
 
 
 def _depth_of(cs):
@@ -318,7 +297,6 @@ def encode_attributes(cloud, qp, chroma_qp_offset=-2, colour=True, attrs=None, s
     dev = cs.device
     if levels.device != dev:
         raise L.PccError(f"{what}: points and attrs are on different devices")
-    lib = L.load()
     steps = steps_for(qp, cqo, ch)
     h_steps = (C.c_int32 * ch)(*steps)
     origin, depth = tuple(cs.bounds.lo), _depth_of(cs)
@@ -360,15 +338,11 @@ def encode_attributes(cloud, qp, chroma_qp_offset=-2, colour=True, attrs=None, s
         if rows:
             d_side = torch.tensor(side, dtype=torch.int32, device=dev)
             _fill_index(masks, offs, sets, depth, ch, d_side, idx, rows)
-            d_cdf, d_sizes, d_offs, d_enc, _ = _constants(dev)
-            symbols = rows * ch
-            segs = segments_for(symbols, segment_symbols)
-            per = lib.pcc_rans_stream_symbols(symbols, 1, 1, segs)
-            cap = _align8(lib.pcc_rans_container_max_bytes(per, segs))
+            tabs = _tables(dev)
+            plan = R.Plan(rows * ch, 1, 1, segments_for(rows * ch, segment_symbols))
+            cap = R.align8(plan.capacity)
             blob = torch.zeros(8 + cap, dtype=torch.uint8, device=dev)
-            ws = L.workspace(lib.pcc_rans_streams_ws_bytes(per, segs), dev)
-            L.call("pcc_rans_encode_streams", L.ptr(coef), L.ptr(idx), symbols, 1, 1, segs, L.ptr(d_cdf), N_SLOTS + 1, L.ptr(d_sizes),
-                   L.ptr(d_offs), L.ptr(d_enc), blob.data_ptr() + 8, blob.data_ptr(), L.ptr(ws), ws.numel(), L.stream())
+            R.encode(tabs, plan, coef, idx, blob.data_ptr() + 8, blob.data_ptr())
             if ev:
                 ev[4].record()
             host = blob.cpu().numpy()                                      # one read: size + container
@@ -422,15 +396,11 @@ def decode_attributes(data, geometry, device=None):
         coef = torch.zeros(max(rows, 1) * ch, dtype=torch.int32, device=dev)
         if rows:
             b0, b1 = hdr["payload"]
-            h_buf = np.zeros(_align8(b1 - b0 + 8), dtype=np.uint8)          # the decoder reads whole words and looks one ahead
-            h_buf[:b1 - b0] = np.frombuffer(data, np.uint8, b1 - b0, b0)
-            d_buf = torch.from_numpy(h_buf).to(dev)
+            d_buf = torch.from_numpy(R.stage(data, [(b0, b1)])[0]).to(dev)
             d_side = torch.tensor(hdr["side"], dtype=torch.int32, device=dev)
             idx = torch.empty(rows * ch, dtype=torch.int32, device=dev)
             _fill_index(masks, offs, sets, depth, ch, d_side, idx, rows)
-            d_cdf, d_sizes, d_offs, _, d_dec = _constants(dev)
-            L.call("pcc_rans_decode_streams", L.ptr(d_buf), b1 - b0, L.ptr(idx), rows * ch, 1, 1, hdr["streams"], L.ptr(d_cdf), N_SLOTS + 1,
-                   L.ptr(d_sizes), L.ptr(d_offs), L.ptr(d_dec), d_dec.numel(), L.ptr(coef), status.data_ptr(), L.stream())
+            R.decode(_tables(dev), d_buf, b1 - b0, idx, rows * ch, 1, 1, hdr["streams"], coef, status.data_ptr())
         v = torch.tensor([[q * s for q, s in zip(hdr["dc"], steps)]], dtype=torch.int32, device=dev)
         for l in range(depth):
             cv = torch.zeros((sets[l + 1].n, ch), dtype=torch.int32, device=dev)

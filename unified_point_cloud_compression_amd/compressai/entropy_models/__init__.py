@@ -10,16 +10,15 @@ Tensor layout at this surface is CompressAI's [B, C, N]; the HIP kernels work on
 (the layout the sparse convolutions produce), so the [N, C] entry points `*_rows` are what the
 build's own model uses and the [B, C, N] methods transpose around them.
 """
-import ctypes as C
 import math
-
-import warnings
 
 import numpy as np
 import torch
 import torch.nn as nn
 
 from ... import lib as L
+from ... import rans as R
+from ...rans import UploadedString                      # (part of this module's surface)
 from ..ops import LowerBound
 
 SCALES_MIN, SCALES_MAX, SCALES_LEVELS = 0.11, 256, 64
@@ -38,18 +37,6 @@ def _rows(x):
     def back(r):
         return r.reshape(B, n, Cc).permute(0, 2, 1).reshape(x.shape)
     return perm.reshape(B * n, Cc), back
-
-
-def _np_ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def pmf_to_quantized_cdf(pmf, precision=16):
-    """CompressAI `pmf_to_quantized_cdf` (C++ op) -> libpcc_hip host function."""
-    pmf = np.ascontiguousarray(np.asarray(pmf, dtype=np.float32))
-    out = np.zeros(len(pmf) + 1, dtype=np.int32)
-    L.check(L.load().pcc_pmf_to_quantized_cdf(_np_ptr(pmf), len(pmf), precision, _np_ptr(out)), "pcc_pmf_to_quantized_cdf")
-    return out
 
 
 class EntropyModel(nn.Module):
@@ -99,7 +86,7 @@ class EntropyModel(nn.Module):
         length = pmf_length.detach().cpu().numpy()
         cdf = np.zeros((len(length), int(max_length) + 2), dtype=np.int32)
         for i in range(len(length)):
-            c = pmf_to_quantized_cdf(np.concatenate([pmf[i, :length[i]], tail[i, :1]]), self.entropy_coder_precision)
+            c = R.pmf_to_quantized_cdf(np.concatenate([pmf[i, :length[i]], tail[i, :1]]), self.entropy_coder_precision)
             cdf[i, :len(c)] = c
         return torch.from_numpy(cdf)
 
@@ -129,34 +116,23 @@ class EntropyModel(nn.Module):
     # ---- coding of [N, C] int32 symbol rows (the layout the kernels produce) -------------------------------
     def compress_rows(self, sym, idx=None):
         """sym [N,C] int32 (device) with table rows idx [N,C] (None: row = channel) -> bytes."""
-        self._check_tables()
-        sym = sym.contiguous()
-        n, c = sym.shape
-        dev = sym.device
-        cdf, sizes, offs = (t.to(dev).contiguous() for t in (self._quantized_cdf, self._cdf_length, self._offset))
         if self.entropy_coder == "ans":
+            tabs = self.tables(sym.device)
+            n, c = sym.shape
             s = sym.t().contiguous().cpu().numpy().reshape(-1)                      # channel-major, as [1,C,N].reshape(-1)
             i = (idx.t().contiguous().cpu().numpy().reshape(-1) if idx is not None
                  else np.repeat(np.arange(c, dtype=np.int32), n))
-            return self._host_encode(s, np.ascontiguousarray(i, np.int32))
-        lib = L.load()
-        ng, segs = self.n_streams(n, c)
-        if self.FRAMING_TARGET > 0 and n * c >= self.ADAPTIVE_MIN_SYMBOLS:
+            return R.host_encode(tabs.host(), s, np.ascontiguousarray(i, np.int32))
+        job = StreamsJob(self, sym, idx)
+        est = None
+        if job.adaptive:
             est = L.counter()
-            L.call("pcc_rans_estimate_bits", L.ptr(sym), L.ptr(idx.contiguous()) if idx is not None else None, n, c, L.ptr(cdf),
-                   cdf.shape[1], L.ptr(sizes), L.ptr(offs), L.cptr(est), L.stream())
-            segs = self._adaptive_segments(n, c, ng, segs, int(L.read(est)[0]) / 2048.0)
-        ns = ng * segs
-        per = lib.pcc_rans_stream_symbols(n, c, ng, segs)
-        cap = lib.pcc_rans_container_max_bytes(per, ns)
-        out = torch.empty(cap, dtype=torch.uint8, device=dev)
+            job.launch_estimate(L.cptr(est))
+            est = L.read(est)[0]
         nb = L.counter()
-        ws = L.workspace(lib.pcc_rans_streams_ws_bytes(per, ns), dev)
-        L.call("pcc_rans_encode_streams", L.ptr(sym), L.ptr(idx.contiguous()) if idx is not None else None, n, c, ng, segs,
-               L.ptr(cdf), cdf.shape[1], L.ptr(sizes), L.ptr(offs), L.ptr(self._enc_table(dev)), L.ptr(out), L.cptr(nb),
-               L.ptr(ws), ws.numel(), L.stream())
+        job.launch_encode(est, count=nb)
         from ...container import StreamBytes
-        return StreamBytes(out[:int(L.read(nb)[0])].cpu().numpy().tobytes(), ng)
+        return StreamBytes(job.blob[:int(L.read(nb)[0])].cpu().numpy().tobytes(), job.ng)
 
     # ---- the same coding, split so that a caller with several matrices to code shares the host reads --------------------
     HDR = 64                 # bytes in front of a container in its device blob: int64 nbytes | int64 guest word | padding
@@ -202,21 +178,18 @@ class EntropyModel(nn.Module):
         (keeps the decode path free of host synchronisation).  `status`: the counter() word to use (a caller that runs this
         under another stream allocates it beforehand: counter blocks are zeroed on the stream that is current when they are
         cut)."""
-        self._check_tables()
         dev = torch.device(device) if device is not None else (idx.device if idx is not None else self._quantized_cdf.device)
-        cdf, sizes, offs = (t.to(dev).contiguous() for t in (self._quantized_cdf, self._cdf_length, self._offset))
+        tabs = self.tables(dev)
         if self.entropy_coder == "ans":
             i = (idx.t().contiguous().cpu().numpy().reshape(-1) if idx is not None
                  else np.repeat(np.arange(c, dtype=np.int32), n))
-            s = self._host_decode(data, np.ascontiguousarray(i, np.int32))
+            s = R.host_decode(tabs.host(), data, np.ascontiguousarray(i, np.int32))
             return torch.from_numpy(s.reshape(c, n).T.copy()).to(dev)
-        buf = data.device_buf if isinstance(data, UploadedString) else self.upload_string(data, dev).device_buf
+        buf = R.upload_string(data, dev).device_buf
         sym = torch.empty((n, c), dtype=torch.int32, device=dev)
         if status is None:
             status = L.counter(1, torch.int32)
-        L.call("pcc_rans_decode_streams", L.ptr(buf), len(data), L.ptr(idx.contiguous()) if idx is not None else None,
-               n, c, *self._segments_of(data, n, c), L.ptr(cdf), cdf.shape[1], L.ptr(sizes), L.ptr(offs),
-               L.ptr(self._dec_table(dev)), self._dec_table(dev).numel(), L.ptr(sym), L.ptr(status), L.stream())
+        R.decode(tabs, buf, len(data), idx.contiguous() if idx is not None else None, n, c, *self._segments_of(data, n, c), sym, status)
         if check is None:                       # synchronous check (one device->host read)
             st = int(status.item())
             if st != 0:
@@ -225,70 +198,17 @@ class EntropyModel(nn.Module):
             check.append(status)
         return sym
 
-    @staticmethod
-    def upload_string(data, dev):
-        """The container's bytes on the device (padded: the decoder looks one word ahead), as an `UploadedString` that
-        `decompress_rows` takes in place of the bytes -- so that a caller can start the copy early, on another stream."""
-        if isinstance(data, UploadedString):
-            return data
-        nb = len(data)
-        buf = torch.empty(nb + 8, dtype=torch.uint8, device=dev)
-        if nb:
-            with warnings.catch_warnings():          # (a read-only view of the bytes: no host-side copy before the upload)
-                warnings.simplefilter("ignore")
-                src = torch.frombuffer(data, dtype=torch.uint8)
-            buf[:nb].copy_(src)
-        buf[nb:].zero_()
-        return UploadedString(data, buf)
+    upload_string = staticmethod(R.upload_string)
 
-    def _dec_table(self, dev):
-        """Compact decoder table of the current CDFs (rebuilt when the tables change)."""
+    def tables(self, dev):
+        """The table set of the current CDFs on `dev` (`rans.Tables`; its encoder entries and decoder blob are built at first
+        use and dropped when the tables change).  Raises while the model has no tables."""
+        self._check_tables()
         tag = (self._tables_gen, self._quantized_cdf._version, str(dev))
-        if getattr(self, "_dec_tag", None) != tag:
-            cdf, sizes, _ = self._host_tables()
-            lib = L.load()
-            nb = lib.pcc_rans_dec_table_bytes(cdf.shape[0], _np_ptr(sizes))
-            blob = np.zeros(nb, dtype=np.uint8)
-            L.check(lib.pcc_rans_build_dec_table(_np_ptr(cdf), cdf.shape[0], cdf.shape[1], _np_ptr(sizes), _np_ptr(blob)),
-                    "pcc_rans_build_dec_table")
-            self._dec_dev = torch.from_numpy(blob).to(dev)
-            self._dec_tag = tag
-        return self._dec_dev
-
-    def _enc_table(self, dev):
-        """Division-free encoder entries of the current CDFs (rebuilt when the tables change)."""
-        tag = (self._tables_gen, self._quantized_cdf._version, str(dev))
-        if getattr(self, "_enc_tag", None) != tag:
-            cdf, sizes, _ = self._host_tables()
-            tab = np.zeros(cdf.shape[0] * cdf.shape[1] * 2, dtype=np.uint64)
-            L.check(L.load().pcc_rans_build_enc_table(_np_ptr(cdf), cdf.shape[0], cdf.shape[1], _np_ptr(sizes),
-                                                      _np_ptr(tab)), "pcc_rans_build_enc_table")
-            self._enc_dev = torch.from_numpy(tab.view(np.int64)).to(dev)
-            self._enc_tag = tag
-        return self._enc_dev
-
-    def _host_tables(self):
-        return tuple(np.ascontiguousarray(t.detach().cpu().numpy().astype(np.int32))
-                     for t in (self._quantized_cdf, self._cdf_length, self._offset))
-
-    def _host_encode(self, sym, idx):
-        cdf, sizes, offs = self._host_tables()
-        lib = L.load()
-        sym = np.ascontiguousarray(sym, np.int32)
-        cap = lib.pcc_rans_max_bytes(len(sym))
-        out = np.zeros(cap, np.uint8)
-        nb = C.c_int64(0)
-        L.check(lib.pcc_rans_encode_host(_np_ptr(sym), _np_ptr(idx), len(sym), _np_ptr(cdf), cdf.shape[1], _np_ptr(sizes),
-                                         _np_ptr(offs), _np_ptr(out), cap, C.byref(nb)), "pcc_rans_encode_host")
-        return out[:nb.value].tobytes()
-
-    def _host_decode(self, data, idx):
-        cdf, sizes, offs = self._host_tables()
-        buf = np.frombuffer(data, np.uint8).copy()
-        out = np.zeros(len(idx), np.int32)
-        L.check(L.load().pcc_rans_decode_host(_np_ptr(buf), len(buf), _np_ptr(idx), len(idx), _np_ptr(cdf), cdf.shape[1],
-                                              _np_ptr(sizes), _np_ptr(offs), _np_ptr(out)), "pcc_rans_decode_host")
-        return out
+        if getattr(self, "_tables_tag", None) != tag:
+            self._tables_dev = R.Tables(*(t.to(dev).contiguous() for t in (self._quantized_cdf, self._cdf_length, self._offset)))
+            self._tables_tag = tag
+        return self._tables_dev
 
     # ---- CompressAI surface: [B, C, N] tensors, one string per batch element ----------------------------------
     def compress(self, inputs, indexes, means=None):
@@ -313,20 +233,6 @@ class EntropyModel(nn.Module):
         return out + means if means is not None else out
 
 
-class UploadedString:
-    """A coded string together with its (padded) copy in device memory; behaves like the bytes for the host-side parsing."""
-
-    def __init__(self, data, device_buf):
-        self.data, self.device_buf = data, device_buf
-        self.groups = getattr(data, "groups", 0)
-
-    def __len__(self):
-        return len(self.data)
-
-    def __getitem__(self, i):
-        return self.data[i]
-
-
 class StreamsJob:
     """GPU rANS coding of one [N, C] symbol matrix (`EntropyModel.compress_rows`, entropy_coder "pcc_streams") in steps.
 
@@ -339,41 +245,33 @@ class StreamsJob:
     """
 
     def __init__(self, em, sym, idx):
-        em._check_tables()
         self.em, self.sym = em, sym.contiguous()
         self.idx = idx.contiguous() if idx is not None else None
         self.n, self.c = self.sym.shape
-        dev = self.sym.device
-        self.tabs = tuple(t.to(dev).contiguous() for t in (em._quantized_cdf, em._cdf_length, em._offset))
+        self.tabs = em.tables(self.sym.device)
         self.ng, self.segs = em.n_streams(self.n, self.c)
         self.adaptive = em.FRAMING_TARGET > 0 and self.n * self.c >= em.ADAPTIVE_MIN_SYMBOLS
         self.blob, self.guess, self.host = None, None, None
 
     def launch_estimate(self, d_ptr):
-        cdf, sizes, offs = self.tabs
-        L.call("pcc_rans_estimate_bits", L.ptr(self.sym), L.ptr(self.idx), self.n, self.c, L.ptr(cdf), cdf.shape[1], L.ptr(sizes),
-               L.ptr(offs), d_ptr, L.stream())
+        R.estimate(self.tabs, self.sym, self.idx, d_ptr)
 
-    def launch_encode(self, est_bits256=None):
-        em, dev = self.em, self.sym.device
-        lib = L.load()
-        cdf, sizes, offs = self.tabs
+    def launch_encode(self, est_bits256=None, count=None):
+        """count: a counter() that receives the byte count; the blob then is the bare container, no header (`compress_rows`)."""
+        em = self.em
         if self.adaptive:
             if est_bits256 is None:
                 raise L.PccError("StreamsJob: an adaptive container needs its payload estimate first")
             payload = int(est_bits256) / 2048.0
             self.segs = em._adaptive_segments(self.n, self.c, self.ng, self.segs, payload)
-        ns = self.ng * self.segs
-        per = lib.pcc_rans_stream_symbols(self.n, self.c, self.ng, self.segs)
-        cap = lib.pcc_rans_container_max_bytes(per, ns)
-        self.blob = torch.empty(em.HDR + cap, dtype=torch.uint8, device=dev)
-        self.blob[:em.HDR].zero_()
-        if self.adaptive and cap > em.FULL_COPY_BYTES:       # payload estimate + framing + slack: what the first copy fetches
-            self.guess = min(cap, int(payload * 1.02) + 12 * ns + 4096)
-        ws = L.workspace(lib.pcc_rans_streams_ws_bytes(per, ns), dev)
-        L.call("pcc_rans_encode_streams", L.ptr(self.sym), L.ptr(self.idx), self.n, self.c, self.ng, self.segs, L.ptr(cdf),
-               cdf.shape[1], L.ptr(sizes), L.ptr(offs), L.ptr(em._enc_table(dev)), self.blob.data_ptr() + em.HDR,
-               self.blob.data_ptr(), L.ptr(ws), ws.numel(), L.stream())
+        plan = R.Plan(self.n, self.c, self.ng, self.segs)
+        head = em.HDR if count is None else 0
+        self.blob = torch.empty(head + plan.capacity, dtype=torch.uint8, device=self.sym.device)
+        if head:
+            self.blob[:head].zero_()
+        if self.adaptive and plan.capacity > em.FULL_COPY_BYTES:       # payload estimate + framing + slack: what the first copy fetches
+            self.guess = min(plan.capacity, int(payload * 1.02) + 12 * plan.streams + 4096)
+        R.encode(self.tabs, plan, self.sym, self.idx, self.blob.data_ptr() + head, count if count is not None else self.blob.data_ptr())
         return self
 
     def guest_ptr(self):

@@ -38,10 +38,6 @@ class StreamBytes(bytes):
         return b
 
 
-def _np_ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
 def encode_points(coords, pitch=8):
     """coords: [n,4] (b,x,y,z) or [n,3] integer tensor/array of lattice points (multiples of `pitch`) -> bytes."""
     c = coords.detach().cpu().numpy() if torch.is_tensor(coords) else np.asarray(coords)
@@ -59,7 +55,7 @@ def encode_points(coords, pitch=8):
     cap = lib.pcc_octree_max_bytes(n, depth)
     out = np.zeros(cap, np.uint8)
     nb = C.c_int64(0)
-    L.check(lib.pcc_octree_encode_host(_np_ptr(cells), n, depth, _np_ptr(out), cap, C.byref(nb)), "pcc_octree_encode_host")
+    L.check(lib.pcc_octree_encode_host(L.nptr(cells), n, depth, L.nptr(out), cap, C.byref(nb)), "pcc_octree_encode_host")
     return struct.pack("<iiiiB", int(origin[0]), int(origin[1]), int(origin[2]), pitch, depth) + out[:nb.value].tobytes()
 
 
@@ -73,14 +69,14 @@ def decode_points(data):
     body = np.frombuffer(data, np.uint8, offset=17).copy()
     lib = L.load()
     n, depth = C.c_int64(0), C.c_int32(0)
-    L.check(lib.pcc_octree_decode_host(_np_ptr(body), len(body), None, 0, C.byref(n), C.byref(depth)), "pcc_octree_decode_host")
+    L.check(lib.pcc_octree_decode_host(L.nptr(body), len(body), None, 0, C.byref(n), C.byref(depth)), "pcc_octree_decode_host")
     # the point count comes from the stream header: bound it before allocating for it.  The adaptive range coder's cost per
     # occupancy decision saturates near 0.02 bit, so a fully dense block codes at well over 100 points per payload byte: the
     # bound is what the lattice can hold (8^depth cells) and a loose 4096 points per byte, not a rate assumption
     if n.value < 0 or n.value > min(8 ** min(int(depth.value), 20), 4096 * max(len(body), 1) + 4096):
         raise L.PccError(f"latent-coordinate stream: header claims {n.value} points for {len(body)} payload bytes at depth {depth.value}")
     cells = np.zeros((max(n.value, 1), 3), np.int32)
-    L.check(lib.pcc_octree_decode_host(_np_ptr(body), len(body), _np_ptr(cells), n.value, C.byref(n), C.byref(depth)),
+    L.check(lib.pcc_octree_decode_host(L.nptr(body), len(body), L.nptr(cells), n.value, C.byref(n), C.byref(depth)),
             "pcc_octree_decode_host")
     xyz = cells[:n.value].astype(np.int64) * pitch + np.array([ox, oy, oz])
     order = np.lexsort((xyz[:, 2], xyz[:, 1], xyz[:, 0]))

@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import lib as L
+from . import rans as R
 from . import sparse as S
 
 MAGIC = 0xA7              # format version 1
@@ -46,7 +47,7 @@ POPCOUNT = np.array([bin(v).count("1") for v in range(256)], dtype=np.int64)
 
 def segments_for(nodes, segment_nodes=SEGMENT_NODES):
     """Row segments (= rANS streams) of a coded level."""
-    return max(1, min(-(-int(nodes) // max(1, int(segment_nodes))), 65536))
+    return R.segments_for(nodes, segment_nodes, 65536)
 
 
 class TableState:
@@ -161,10 +162,6 @@ def parse_header(data):
 # ------------------------------------------------------------------------------------------------------------------------
 # device side
 # ------------------------------------------------------------------------------------------------------------------------
-def _np_ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
 def _key_of(x, y, z):
     return ((x + S.BIAS) << 32) | ((y + S.BIAS) << 16) | (z + S.BIAS)
 
@@ -228,26 +225,6 @@ def level_sets(cs, origin, depth):
     return sets[::-1]
 
 
-_CONST = {}
-
-
-def _constants(dev):
-    """(sizes, offsets) of the 64 table rows on the device: the same for every level, one upload per device."""
-    const = _CONST.get(str(dev))
-    if const is None:
-        const = _CONST[str(dev)] = (torch.from_numpy(TABLE_SIZES).to(dev), torch.from_numpy(TABLE_OFFSETS).to(dev))
-    return const
-
-
-def _upload_enc_tables(cdf, dev):
-    """(cdf, sizes, offsets, division-free encoder entries) on the device for one level of the encoder."""
-    tab = np.zeros(cdf.shape[0] * cdf.shape[1] * 2, dtype=np.uint64)
-    L.check(L.load().pcc_rans_build_enc_table(_np_ptr(cdf), cdf.shape[0], cdf.shape[1], _np_ptr(TABLE_SIZES), _np_ptr(tab)),
-            "pcc_rans_build_enc_table")
-    const = _constants(dev)
-    return torch.from_numpy(cdf).to(dev), const[0], const[1], torch.from_numpy(tab.view(np.int64)).to(dev)
-
-
 @torch.no_grad()
 def encode_geometry(x, segment_nodes=SEGMENT_NODES, timings=None):
     """[N, >= 3] GPU tensor (any row order, duplicates allowed, floats floored) or pitch-1 CoordSet -> bytes.
@@ -297,25 +274,21 @@ def encode_geometry(x, segment_nodes=SEGMENT_NODES, timings=None):
         # coded levels: tables from the levels before, one rANS launch each into a shared blob [sizes | containers]
         state = TableState()
         coded = [l for l in range(depth) if nodes[l] >= RAW_NODES]
-        segs = {l: segments_for(nodes[l], segment_nodes) for l in coded}
-        per = {l: lib.pcc_rans_stream_symbols(nodes[l], 1, 1, segs[l]) for l in coded}
-        caps = {l: int(_align8(lib.pcc_rans_container_max_bytes(per[l], segs[l]))) for l in coded}
+        plans = {l: R.Plan(nodes[l], 1, 1, segments_for(nodes[l], segment_nodes)) for l in coded}
+        caps = {l: R.align8(plans[l].capacity) for l in coded}
         head = 8 * max(len(coded), 1)
         blob = torch.zeros(head + sum(caps.values()), dtype=torch.uint8, device=dev)
         begin, keep, where = head, [], {}
         t_code = []
         for l in range(depth):
-            if l in segs:
-                cdf = derive_tables(state.counts, h_hist[l, N_CTX * 256:])
-                d_cdf, d_sizes, d_offs, d_tab = _upload_enc_tables(cdf, dev)
-                keep.append((d_cdf, d_sizes, d_offs, d_tab))
-                ws = L.workspace(lib.pcc_rans_streams_ws_bytes(per[l], segs[l]), dev)
+            if l in plans:
+                tabs = R.fresh_cdf_tables("geometry", dev, derive_tables(state.counts, h_hist[l, N_CTX * 256:]), TABLE_SIZES, TABLE_OFFSETS)
+                keep.append(tabs)
                 if timings is not None:
                     t_code.append((l, torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
                     t_code[-1][1].record()
-                L.call("pcc_rans_encode_streams", sym.data_ptr() + 4 * at[l], ctx.data_ptr() + 4 * at[l], nodes[l], 1, 1, segs[l],
-                       L.ptr(d_cdf), cdf.shape[1], L.ptr(d_sizes), L.ptr(d_offs), L.ptr(d_tab), blob.data_ptr() + begin,
-                       blob.data_ptr() + 8 * coded.index(l), L.ptr(ws), ws.numel(), L.stream())
+                R.encode(tabs, plans[l], sym.data_ptr() + 4 * at[l], ctx.data_ptr() + 4 * at[l], blob.data_ptr() + begin,
+                         blob.data_ptr() + 8 * coded.index(l))
                 if timings is not None:
                     t_code[-1][2].record()
                 where[l] = (begin, caps[l])
@@ -346,10 +319,6 @@ def encode_geometry(x, segment_nodes=SEGMENT_NODES, timings=None):
     return bytes(out)
 
 
-def _align8(v):
-    return (int(v) + 7) // 8 * 8
-
-
 def _canonical_children(keys, n, pitch, depth_level, dev, counts_ptr):
     """Canonical order of a level's child keys (inside the level's 2^l cube by construction): through the occupancy bitmap of
     that cube while it is small enough, else by radix sort (the level then has no grid index and the context kernel searches).
@@ -374,23 +343,17 @@ def _canonical_children(keys, n, pitch, depth_level, dev, counts_ptr):
     return out, None
 
 
-def _aligned_payloads(data, levels):
-    """Host buffers for ONE upload each: the coded levels' rANS containers at 8-aligned offsets with 8 zero bytes behind each
-    (the decoder reads whole words and looks one ahead), and the raw levels' bytes as int32 symbols."""
-    at, where, raw_at, raw = 0, {}, {}, []
+def _payloads(data, levels):
+    """Host buffers for ONE upload each: the coded levels' rANS containers (`rans.stage`) and the raw levels' bytes as int32
+    symbols."""
+    coded = [l for l, lv in enumerate(levels) if not lv["raw"]]
+    buf, offsets = R.stage(data, [levels[l]["payload"] for l in coded])
+    raw_at, raw = {}, []
     for l, lv in enumerate(levels):
-        b0, b1 = lv["payload"]
         if lv["raw"]:
             raw_at[l] = len(raw)
-            raw.extend(data[b0:b1])
-        else:
-            where[l] = at
-            at += (b1 - b0 + 8 + 7) // 8 * 8
-    buf = np.zeros(max(at, 8), dtype=np.uint8)
-    for l, o in where.items():
-        b0, b1 = levels[l]["payload"]
-        buf[o:o + b1 - b0] = np.frombuffer(data, np.uint8, b1 - b0, b0)
-    return buf, where, np.asarray(raw if raw else [1], dtype=np.int32), raw_at
+            raw.extend(data[lv["payload"][0]:lv["payload"][1]])
+    return buf, dict(zip(coded, offsets)), np.asarray(raw if raw else [1], dtype=np.int32), raw_at
 
 
 @torch.no_grad()
@@ -416,14 +379,15 @@ def decode_geometry(data, device, as_set=False, timings=None):
     hw = lib.pcc_geom_hist_words()
     levels = hdr["levels"]
     with torch.cuda.device(dev):
-        h_buf, where, h_raw, raw_at = _aligned_payloads(data, levels)
+        h_buf, where, h_raw, raw_at = _payloads(data, levels)
         d_buf, d_raw = torch.from_numpy(h_buf).to(dev), torch.from_numpy(h_raw).to(dev)
-        const = _constants(dev)
+        const = R.fixed_tables("geometry", dev, None, TABLE_SIZES, TABLE_OFFSETS)
         state = torch.zeros(N_CTX * 256, dtype=torch.int64, device=dev)
         hist = torch.zeros((depth, hw), dtype=torch.int32, device=dev)
         flags = torch.zeros((depth, 8), dtype=torch.int32, device=dev)     # status | bad byte | child total (i64) | distinct, off-lattice (i64 x 2)
-        d_cdf = torch.empty((N_CTX, N_SYM + 2), dtype=torch.int32, device=dev)
-        d_tab = torch.zeros(lib.pcc_geom_dec_table_bytes(), dtype=torch.uint8, device=dev)
+        # the level's cdf and decoder blob are derived on the device (`pcc_geom_tables`), in place, before each coded level
+        tabs = R.Tables(torch.empty((N_CTX, N_SYM + 2), dtype=torch.int32, device=dev), const.sizes, const.offsets,
+                        dec=torch.zeros(lib.pcc_geom_dec_table_bytes(), dtype=torch.uint8, device=dev))
         keys = torch.tensor([_key_of(0, 0, 0)], dtype=torch.int64, device=dev)
         grid, by_grid, tl = None, [], []
         for l, lv in enumerate(levels):
@@ -440,10 +404,9 @@ def decode_geometry(data, device, as_set=False, timings=None):
                 sym = d_raw[raw_at[l]:raw_at[l] + m]
             else:
                 nb = lv["payload"][1] - lv["payload"][0]
-                L.call("pcc_geom_tables", L.ptr(state), (C.c_uint32 * 8)(*lv["pop"]), L.ptr(d_cdf), L.ptr(d_tab), L.stream())
+                L.call("pcc_geom_tables", L.ptr(state), (C.c_uint32 * 8)(*lv["pop"]), L.ptr(tabs.cdf), L.ptr(tabs.dec), L.stream())
                 sym = torch.empty(m, dtype=torch.int32, device=dev)
-                L.call("pcc_rans_decode_streams", d_buf.data_ptr() + where[l], nb, L.ptr(ctx), m, 1, 1, lv["streams"], L.ptr(d_cdf),
-                       N_SYM + 2, L.ptr(const[0]), L.ptr(const[1]), L.ptr(d_tab), d_tab.numel(), L.ptr(sym), fp, L.stream())
+                R.decode(tabs, d_buf.data_ptr() + where[l], nb, ctx, m, 1, 1, lv["streams"], sym, fp)
             if evs:
                 evs[2].record()
             L.call("pcc_geom_hist", L.ptr(sym), L.ptr(ctx), m, hist[l].data_ptr(), fp + 4, L.stream())

@@ -239,6 +239,11 @@ def ptr(t):
     return t.data_ptr()
 
 
+def nptr(a):
+    """Host pointer of a numpy array (the host entry points: table builders, single-stream coders, the octree coder)."""
+    return a.ctypes.data_as(C.c_void_p)
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
