@@ -413,6 +413,15 @@ int pcc_gauss_encode(const float* y, const float* params, const int64_t* keys, c
 int pcc_gauss_decode(const int32_t* sym, const float* params, const int64_t* keys, const float* gain,
                      int64_t n, int32_t c, const float* table, int32_t n_table, float* y_hat,
                      int32_t* idx, void* stream);
+/* Rate sweep: the rANS payload estimate (pcc_rans_estimate_bits below, 1/256 bit) of y under each of K candidate gain rows,
+ * gains [K, c], every row applied to all n rows of y (one batch).  d_bits256[k] is exactly the integer that
+ * pcc_gauss_encode with gain row k (keys of batch 0) followed by pcc_rans_estimate_bits on its sym / idx gives: the same
+ * element rules (csrc/pcc_entropy_rule.h), integer sums.  y and params are read once per element, neither sym nor idx is
+ * written; one launch, no workspace.  table: the scale table of a7; cdf / sizes / offsets: its rANS tables (n_table rows).
+ * Limits: 1 <= K <= 256, c >= 1, 2 <= n_table <= 256, n * c < 2^31; n == 0 zeroes d_bits256 [K] and launches nothing. */
+int pcc_gauss_rate_sweep(const float* y, const float* params, int64_t n, int32_t c, const float* gains /*[K,c]*/, int32_t K,
+                         const float* table, int32_t n_table, const int32_t* cdf, int32_t cdf_stride, const int32_t* sizes,
+                         const int32_t* offsets, int64_t* d_bits256 /*[K], device*/, void* stream);
 
 /* Differentiable Gaussian likelihood of the TRAINING forward (GaussianConditional._likelihood + lower bound 1e-9;
  * model/entropy_models.py:312-316,327-331; rate term loss.py:77-79) on n elements:

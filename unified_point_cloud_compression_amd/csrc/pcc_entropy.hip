@@ -1,19 +1,12 @@
 // Hyperprior likelihood path: fused Gaussian-conditional kernel (scale bound, table index search,
 // quantisation, likelihood) and the factorised prior on the hyper latent.  Element-wise, HBM-bound.
 #include "pcc_common.h"
+#include "pcc_entropy_rule.h"
 
-static constexpr float SCALE_BOUND = 0.11f;
 static constexpr float LIK_BOUND = 1e-9f;
 
 __device__ inline float std_cum(float x) {           // 0.5 * erfc(-x / sqrt(2))
   return 0.5f * erfcf(-0.70710678118654752440f * x);
-}
-
-__device__ inline int table_index(float s, const float* __restrict__ tab, int nt) {
-  // idx = (nt-1) - #{t < nt-1 : s <= tab[t]}   (GaussianConditional.build_indexes)
-  int idx = nt - 1;
-  for (int t = 0; t < nt - 1; ++t) idx -= (s <= tab[t]) ? 1 : 0;
-  return idx;
 }
 
 template <bool ENCODE>
@@ -34,11 +27,11 @@ __global__ void __launch_bounds__(256) k_gauss(const float* __restrict__ y, cons
   const float mean = params[r * 2 * c + c + ch];
   float g = 1.f;
   if (gain) g = gain[(keys[r] >> 48) * c + ch];
-  const float s = fmaxf(scale * g, SCALE_BOUND);
+  const float s = gauss_bound_scale(scale, g);
   if (idx) idx[t] = table_index(s, tab, nt);
   if (ENCODE) {
     if (!sym && !lik) return;                       // index-only call (decoder side, before the symbols exist)
-    const float q = rintf(y[t] * g - mean * g);
+    const float q = gauss_quantise(y[t], mean, g);
     if (sym) sym[t] = (int)q;
     if (lik) {
       const float a = fabsf(q);

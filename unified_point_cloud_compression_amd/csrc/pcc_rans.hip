@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "pcc_common.h"
+#include "pcc_entropy_rule.h"
 
 #define RANS_HD __host__ __device__ inline
 
@@ -20,8 +21,6 @@ static constexpr int R_PREC = 16;
 static constexpr int R_BYP = 4;
 static constexpr int R_MAXB = (1 << R_BYP) - 1;
 static constexpr unsigned long long R_L = 1ull << 31;
-
-struct RansTab { const int* cdf; int stride; const int* sizes; const int* offsets; };
 
 // Per (table row, value) division-free encoder entry (ryg_rans `Rans64EncSymbol`): x -> x + bias + q*cmpl_freq with
 // q = mulhi(x, rcp_freq) >> rcp_shift equals ((x / freq) << 16) + (x % freq) + start exactly.
@@ -846,18 +845,10 @@ __global__ void __launch_bounds__(256) k_rans_estimate(const int* __restrict__ s
   // element-per-thread form cost ~75 of the kernel's 92 us; the sum is an integer, so its order does not matter)
   unsigned long long acc = 0;
   for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-    unsigned b = 0;
     const int ci = idx ? idx[e] : (int)(e % channels);
     const int max_value = t.sizes[ci] - 2;
-    int v = sym[e] - t.offsets[ci];
-    unsigned raw = 0;
-    if (v < 0) { raw = (unsigned)(-2 * v - 1); v = max_value; }
-    else if (v >= max_value) { raw = (unsigned)(2 * (v - max_value)); v = max_value; }
-    const int* row = t.cdf + (size_t)ci * t.stride;
-    const int freq = max(row[v + 1] - row[v], 1);
-    b = (unsigned)__float2int_rn(256.f * (16.f - __log2f((float)freq)));
-    if (v == max_value) b += 256u * 4u * (unsigned)((32 - __clz((int)(raw | 1u)) + 3) / 4 + 1);   // bypass digits, 4 bits each
-    acc += b;
+    const int v = sym[e] - t.offsets[ci];
+    acc += rans_value_bits256(v, max_value, t.cdf + (size_t)ci * t.stride);
   }
   unsigned long long w = acc;
 #pragma unroll

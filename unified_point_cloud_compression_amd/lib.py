@@ -125,6 +125,7 @@ SIGNATURES = {
     "pcc_lookup_rows": (C.c_int, [_p, _i64, _p, _i64, _p, _p]),
     "pcc_gauss_encode": (C.c_int, [_p, _p, _p, _p, _i64, _i32, _p, _i32, _p, _p, _p, _p]),
     "pcc_gauss_decode": (C.c_int, [_p, _p, _p, _p, _i64, _i32, _p, _i32, _p, _p, _p]),
+    "pcc_gauss_rate_sweep": (C.c_int, [_p, _p, _i64, _i32, _p, _i32, _p, _i32, _p, _i32, _p, _p, _p, _p]),
     "pcc_eb_encode": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _p, _p]),
     "pcc_eb_lik_fwd": (C.c_int, [_p, _i64, _i32, _p, _p, _p]),
     "pcc_eb_lik_bwd": (C.c_int, [_p, _p, _i64, _i32, _p, _p, _p, _p]),

@@ -50,6 +50,17 @@ def _mlp(sizes, last=None):
     return nn.Sequential(*layers)
 
 
+class LatentAnalysis:
+    """The part of `MeanScaleHyperprior.compress` that does not depend on q (`analyse`): the hyper-latent's coded string
+    (`z_code`: [z_string], or its symbols with entropy_coder "symbols"), `shape` = [Nz], the (scales | means) rows `params`
+    of y, and y's canonical rows `y_rows` on the set `y_cset`.  `points` = [y.C, z.C] as `compress` returns them."""
+
+    def __init__(self, y, z, z_code, params):
+        self.y_rows, self.y_cset = y._canonical_features(), y._cset
+        self.points = [y.C, z.C]
+        self.z_code, self.shape, self.params = z_code, [z._cset.n], params
+
+
 class MeanScaleHyperprior(CompressionModel):
     def __init__(self, config):
         super().__init__()
@@ -269,6 +280,65 @@ class MeanScaleHyperprior(CompressionModel):
             guard.zero_()
             raise L.RangeGuardTripped()
         return z_string, yj.fetch()
+
+    # ---- the same coding in two halves: what does not see q, and y's string per q -----------------
+    def analyse(self, y):
+        """Everything `compress(y, q)` computes before q enters: the hyper-latent and its coded string, the (scales | means)
+        rows of y, y's canonical rows and keys -> `LatentAnalysis`.  Every guarded matrix product of the block (g_a's and
+        h_a's) is queued by the time the range guard is read, once, here: with the stream coder it travels in the header of
+        the hyper-latent's container as in `_code_streams`, otherwise it is read as `compress` reads it.  A trip raises
+        `RangeGuardTripped` before anything of y is coded."""
+        z = self.hyper_analysis(y)
+        z_sym, z_hat_f, _ = self.entropy_bottleneck.encode_rows(z._canonical_features(), want_likelihood=False)
+        zj = self._start_z_streams(z_sym)
+        z_hat = SparseTensor._from_canonical(z._cset, z_hat_f)
+        params = self._gaussian_params(z_hat, y._cset)
+        guard = L.h_guard(z_sym.device)
+        if self.entropy_coder == "pcc_streams":
+            if zj.adaptive:                               # large frames: the stream count needs the payload estimate first
+                est = L.counter()
+                zj.launch_estimate(est.data_ptr())
+                zj.launch_encode(L.read(est)[0])
+            else:                                         # (started on the side stream by `_start_z_streams`)
+                torch.cuda.current_stream(z_sym.device).wait_event(zj.ready)
+            zj.attach(guard)
+            z_code = [zj.fetch()]
+            tripped = bool(zj.guest2)
+        else:
+            tripped = L.arith() == L.ARITH_H3 and bool(guard.item())
+            z_code = z_sym if self.entropy_coder == "symbols" else [self.entropy_bottleneck.compress_rows(z_sym)]
+        if tripped and L.arith() == L.ARITH_H3:
+            guard.zero_()
+            raise L.RangeGuardTripped()
+        return LatentAnalysis(y, z, z_code, params)
+
+    def code_latents(self, analysis, q):
+        """y's string for one q ([1, 2]) on top of `analyse`: [y_string], or y's int32 symbols with entropy_coder "symbols" --
+        what `compress(y, q)` returns in strings[0].  One element-wise pass over y and one rANS encode; no matrix product."""
+        a = analysis
+        scale, _ = self._gains(q, a.y_cset, a.y_rows.shape[1])
+        y_sym, idx, _ = self.gaussian_conditional.encode_rows(a.y_rows, a.params, a.y_cset.keys, scale, want_likelihood=False)
+        if self.entropy_coder == "symbols":
+            return y_sym
+        if self.entropy_coder != "pcc_streams":
+            return [self.gaussian_conditional.compress_rows(y_sym, idx)]
+        yj = self.gaussian_conditional.streams_job(y_sym, idx)
+        if yj.adaptive:
+            est = L.counter()
+            yj.launch_estimate(est.data_ptr())
+            yj.launch_encode(L.read(est)[0])
+        else:
+            yj.launch_encode()
+        return [yj.fetch()]
+
+    def sweep_gains(self, qs, c):
+        """[K, c] float32 gain rows of the quality pairs qs [K, 2] (row i = the row `_gains(qs[i:i+1])` gives); ones without
+        adaptive_BN, where q does not reach the latents."""
+        if not self.adaptive_BN:
+            return torch.ones((qs.shape[0], c), dtype=torch.float32, device=qs.device)
+        # one row at a time: a batched product may sum in another order than the one-row call `compress` makes, and the
+        # sweep promises the integers of exactly those gain rows
+        return torch.cat([self._gains(qs[i:i + 1], None, c)[0] for i in range(qs.shape[0])], dim=0)
 
     def likelihoods(self, y, q):
         """Eval-mode likelihoods of y and z (what `forward` feeds the rate loss, `loss.py:63-81`)."""

@@ -182,6 +182,143 @@ class UnifiedModel(CompressionModel):
             return None
         return bitstreams, block_shapes, block_k, block_coordinates, block_q_vals
 
+    # ---- many quality points, or a byte budget, from one analysis pass (DESIGN.md section 7h) --------------------------------
+    def _frame_blocks(self, pointcloud, block_size):
+        """[(rows of the block, coordinate hint)] exactly as the block loop of `compress` hands them to `compress_block`."""
+        if not pointcloud.is_cuda:
+            raise L.PccError("compress expects the point cloud on the GPU (`utils.py:436-441` moves it there)")
+        single = None
+        n_pts = pointcloud.shape[0]
+        if n_pts > 1 and pointcloud.dtype == torch.float32 and pointcloud.dim() == 2 and pointcloud.shape[1] == 6 \
+                and pointcloud.is_contiguous() and pointcloud.data_ptr() % 8 == 0:
+            keys, feats, b, canonical = S.frame_intake(pointcloud)
+            if max(b.hi[i] - b.lo[i] for i in range(3)) < block_size:
+                single = (S.FrameRows(n_pts, pointcloud.device, (keys, b, canonical)), feats)
+        elif n_pts > 1:
+            c4 = torch.cat([torch.zeros((n_pts, 1), device=pointcloud.device, dtype=pointcloud.dtype), pointcloud[:, :3]], dim=1)
+            keys = S.pack_keys(c4)
+            b, canonical = S.bounds_of(c4, canon_keys=keys)
+            if max(b.hi[i] - b.lo[i] for i in range(3)) < block_size:
+                c4._pcc_hint = (keys, b, canonical)
+                single = c4
+        order, counts = (None, [n_pts]) if single is not None else self.partition(pointcloud, block_size)
+        xs = pointcloud if order is None else pointcloud[order]
+        out, start = [], 0
+        for count in counts:
+            out.append((xs[start:start + count], single))
+            start += count
+        return out
+
+    def _analyse_block(self, x_block, coords=None):
+        """(LatentAnalysis, k) of one block: g_a and the q-independent half of the entropy model, under the range guard as in
+        `compress_block` -- a trip runs this shared part again in the six-term form, before any latent is coded."""
+        def run():
+            if isinstance(coords, tuple):
+                coords[0]._pcc_chain = self.stride_chain()
+                x = SparseTensor._from_frame(x_block, coords[0], coords[1])
+            else:
+                x = self.block_input(x_block, coords=coords)
+            y, k = self.g_a(x)
+            return self.entropy_model.analyse(y), k
+        try:
+            return run()
+        except L.RangeGuardTripped:
+            with L.arith_scope(L.ARITH_BF6):
+                return run()
+
+    def _code_candidate(self, analyses, q):
+        """The `compress` 5-tuple of one q ([1, 2]) from the blocks' shared parts."""
+        em = self.entropy_model
+        bitstreams, block_shapes, block_coordinates, block_q_vals, block_k = [], [], [], [], []
+        for a, k in analyses:
+            y_code = em.code_latents(a, q)
+            bitstreams.append([y_code, a.z_code])
+            block_shapes.append(a.shape)
+            block_k.append(k)
+            block_coordinates.append(a.points[0])
+            block_q_vals.append(q)
+        return bitstreams, block_shapes, block_k, block_coordinates, block_q_vals
+
+    def _rate_map(self, analyses, qs):
+        from .. import rate
+        em = self.entropy_model
+        gc = em.gaussian_conditional
+        K = qs.shape[0]
+        if not 1 <= K <= rate.MAX_CANDIDATES:
+            raise L.PccError(f"rate_map: {K} quality points (1 to {rate.MAX_CANDIDATES})")
+        gains = em.sweep_gains(qs, em.gaussian_conditional_channels())
+        per_block = torch.stack([rate.sweep_bits(gc, a.y_rows, a.params, gains, a.y_cset) for a, _ in analyses]).tolist()   # the one read
+        if em.entropy_coder == "symbols":
+            fixed = 0
+        else:
+            fixed = sum(len(s) for a, _ in analyses for s in a.z_code)
+        predicted = [fixed] * K
+        for (a, _), bits in zip(analyses, per_block):
+            n, c = a.y_rows.shape
+            predicted = [p + rate.predicted_bytes(gc, n, c, b) for p, b in zip(predicted, bits)]
+        y_bits = torch.tensor([sum(col) for col in zip(*per_block)], dtype=torch.int64)
+        return {"y_bits256": y_bits, "fixed_bytes": fixed, "predicted_bytes": predicted}
+
+    @staticmethod
+    def _check_qs(qs):
+        if qs.dim() != 2 or qs.shape[1] != 2 or qs.shape[0] < 1:
+            raise L.PccError(f"qs must be [K, 2] quality pairs with K >= 1, got {tuple(qs.shape)}")
+
+    @torch.no_grad()
+    def compress_multirate(self, pointcloud, qs, block_size=1024):
+        """K quality points of one frame: a list whose entry i is what `compress(pointcloud, qs[i:i+1], block_size=block_size)`
+        returns, byte for byte.  g_a and the hyper path run once per block; each q then costs one element-wise pass over y
+        and one rANS encode per block (`MeanScaleHyperprior.analyse / code_latents`)."""
+        self._check_qs(qs)
+        analyses = [self._analyse_block(x, coords) for x, coords in self._frame_blocks(pointcloud, block_size)]
+        return [self._code_candidate(analyses, qs[i:i + 1]) for i in range(qs.shape[0])]
+
+    @torch.no_grad()
+    def rate_map(self, pointcloud, qs, block_size=1024):
+        """Rate of every quality pair of qs [K, 2] (K <= 256) without coding a latent: {"y_bits256": int64 [K], the payload
+        estimate of y summed over the blocks (for each q the integer `pcc_rans_estimate_bits` gives on the symbols `compress`
+        codes); "fixed_bytes": the hyper-latents' strings, the same for every q; "predicted_bytes": K ints, fixed_bytes + per
+        block ceil(y_bits256 / 2048) + the framing of the stream plan that estimate implies (`rate.predicted_bytes`)}.
+        Beyond the shared part (one read per block, the hyper-latent's string) one host read serves the whole grid."""
+        self._check_qs(qs)
+        analyses = [self._analyse_block(x, coords) for x, coords in self._frame_blocks(pointcloud, block_size)]
+        return self._rate_map(analyses, qs)
+
+    @torch.no_grad()
+    def compress_to_size(self, pointcloud, max_bytes, qs=None, block_size=1024):
+        """The frame in at most max_bytes, measured as `metrics.count_bits(strings) / 8` over all blocks (the figure the bpp is
+        computed from; latent coordinates and headers are not in it): -> (result, info).  The shared part runs once,
+        `rate_map` predicts every candidate of qs (default `rate.q_grid()`), `rate.choose` picks the largest prediction within
+        the budget, its latents are coded, and a candidate whose real size exceeds the budget is excluded and the choice
+        repeated -- until one fits or none is left (a prediction is not a bound: once no prediction is within the budget the
+        remaining candidates are tried from the smallest prediction up).  result: the `compress` 5-tuple of the chosen q, the
+        same q for every block.  info: index, q ([1, 2]), predicted_bytes, bytes, met, tries; when no candidate fits (met
+        false, tries = K) the one with the smallest prediction is returned."""
+        from .. import rate
+        from ..metrics import count_bits
+        if self.entropy_model.entropy_coder == "symbols":
+            raise L.PccError("compress_to_size needs byte strings to count: build the model with entropy_coder 'pcc_streams' or 'ans'")
+        if qs is None:
+            qs = torch.from_numpy(rate.q_grid()).to(pointcloud.device)
+        self._check_qs(qs)
+        analyses = [self._analyse_block(x, coords) for x, coords in self._frame_blocks(pointcloud, block_size)]
+        predicted = self._rate_map(analyses, qs)["predicted_bytes"]
+        smallest = rate.choose(predicted, -1)[0]
+        tried, kept, met = [], None, False
+        while not met:
+            index, _ = rate.choose(predicted, max_bytes, exclude=tried)
+            if index is None:
+                break
+            result = self._code_candidate(analyses, qs[index:index + 1])
+            nbytes = count_bits(result[0]) // 8
+            tried.append(index)
+            met = nbytes <= max_bytes
+            if met or index == smallest:
+                kept = (index, result, nbytes)
+        index, result, nbytes = kept
+        return result, {"index": index, "q": qs[index:index + 1], "predicted_bytes": predicted[index], "bytes": nbytes,
+                        "met": met, "tries": len(tried)}
+
     @torch.no_grad()
     def decompress(self, path=None, coordinates=None, strings=None, shape=None, k=None, q_vals=None, trace=None,
                    probe=None):
