@@ -21,7 +21,7 @@ import pytest
 import torch
 
 from oracle import codec, coords as co
-from tests.util import dev, t, n, coord_set, flat_keys, ratios, shape_rows, surface_keys
+from tests.util import dev, t, n, bits as _bits, conv_sums64, coord_set, flat_keys, ratios, shape_rows, surface_keys
 
 pytestmark = pytest.mark.gpu
 
@@ -159,25 +159,8 @@ def _act64(v, act):
 def _ref64(x, W, b, act, pairs, n_out):
     """(ref, S2) [n_out, cout] float64 on the GPU: ref = act(bias + sum_k index_add(x[i_k] @ W[k])),
     S2 = sqrt(bias^2 + sum_k index_add(x[i_k]^2 @ W[k]^2)) over the oracle's pairs (pairs None: the identity, K = 1)."""
-    x64, W64 = t(x).double(), t(W).double()
-    cout = W.shape[2]
-    ref = torch.zeros((n_out, cout), dtype=torch.float64, device=dev())
-    s2 = torch.zeros_like(ref)
-    if b is not None:
-        b64 = t(b).double()
-        ref += b64
-        s2 += b64 * b64
-    if pairs is None:
-        ref += x64 @ W64[0]
-        s2 += (x64 * x64) @ (W64[0] * W64[0])
-    else:
-        for k, (i, o) in enumerate(pairs):
-            if len(i) == 0:
-                continue
-            xi, oo = x64[torch.from_numpy(i.astype(np.int64)).to(dev())], torch.from_numpy(o.astype(np.int64)).to(dev())
-            ref.index_add_(0, oo, xi @ W64[k])
-            s2.index_add_(0, oo, (xi * xi) @ (W64[k] * W64[k]))
-    return _act64(ref, act), s2.sqrt()
+    ref, sq = conv_sums64(t(x).double(), t(W).double(), t(b).double() if b is not None else None, pairs, n_out)
+    return _act64(ref, act), sq.sqrt()
 
 
 def _run(name, xt, Wt, bt, act, form):
@@ -202,10 +185,6 @@ def _run(name, xt, Wt, bt, act, form):
         L.call("pcc_prof_enable", 0)
     assert cnt == 1, (name, rec)                # one event-timed launch per pcc_conv_fwd
     return out, rec[0]
-
-
-def _bits(a):
-    return n(a.contiguous().view(torch.int32))
 
 
 def _expected_form(kind, form):

@@ -6,7 +6,7 @@ import pytest
 import torch
 
 from oracle import coords as co, ops
-from tests.util import dev, t, n, cloud_keys, assert_close
+from tests.util import dev, t, n, cloud_keys, assert_close, two_batch_keys as _two_batch_keys
 
 pytestmark = pytest.mark.gpu
 
@@ -98,16 +98,6 @@ def test_fused_head_matches_oracle(cin, cmid, bands, small_bands):
         finally:
             S.BAND_TILES = old[0]
     assert torch.equal(again.F, got.F)
-
-
-def _two_batch_keys(seed, ts, shift):
-    C = []
-    for b, (size, p) in enumerate(((21, 0.3), (17, 0.2))):
-        c = co.unpack_keys(cloud_keys(seed + b, size, p, ts))
-        c[:, 0] = b
-        c[:, 1:] += shift * ts
-        C.append(c)
-    return np.unique(co.pack_keys(np.concatenate(C)))
 
 
 @pytest.mark.parametrize("ts,shift,cin,cout", [(1, 0, 16, 1), (2, -5, 16, 1), (2, -5, 8, 3), (1, -3, 32, 4), (1, 0, 64, 1), (2, -5, 32, 1)])

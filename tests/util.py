@@ -36,6 +36,18 @@ def cloud_keys(seed, size, p, ts=1, margin=0, batch=1):
     return keys
 
 
+def two_batch_keys(seed, ts, shift, sizes=((21, 0.3), (17, 0.2))):
+    """Two batch entries of `cloud_keys` (seed, seed + 1) at the given per-batch (size, p), every coordinate moved by
+    shift * ts (negative coordinates for shift < 0)."""
+    C = []
+    for b, (size, p) in enumerate(sizes):
+        c = co.unpack_keys(cloud_keys(seed + b, size, p, ts))
+        c[:, 0] = b
+        c[:, 1:] += shift * ts
+        C.append(c)
+    return np.unique(co.pack_keys(np.concatenate(C)))
+
+
 @functools.lru_cache(maxsize=None)
 def surface_keys(scale):
     """Voxelised sphere + torus surface (batch 0): ~205 k rows at scale 0.515, ~1.07 M at 1.17 -- the sizes of the training
@@ -70,6 +82,35 @@ def shape_rows(x, dist, rng):
     if dist == "spread":
         return x * np.exp(rng.uniform(-6, 6, (x.shape[0], 1))).astype(np.float32)
     raise ValueError(dist)
+
+
+def conv_sums64(x64, W64, b64, pairs, n_out):
+    """The float64 reference of a sparse convolution over the ORACLE's pairs, on the device of x64 (torch float64):
+    (sum, sum of squares) [n_out, cout] of the terms of every entry -- b (None: no bias) and x[i][ci] * W[k][ci][co] for every pair
+    (i, o) of every offset k.  pairs: [(in_rows, out_rows)] per offset (numpy), or None for the identity (K = 1)."""
+    device = x64.device
+    ref = torch.zeros((n_out, W64.shape[2]), dtype=torch.float64, device=device)
+    sq = torch.zeros_like(ref)
+    if b64 is not None:
+        ref += b64.reshape(1, -1)
+        sq += b64.reshape(1, -1) ** 2
+    if pairs is None:
+        ref += x64 @ W64[0]
+        sq += (x64 * x64) @ (W64[0] * W64[0])
+        return ref, sq
+    for k, (i, o) in enumerate(pairs):
+        if len(i) == 0:
+            continue
+        xi = x64[torch.from_numpy(i.astype(np.int64)).to(device)]
+        oo = torch.from_numpy(o.astype(np.int64)).to(device)
+        ref.index_add_(0, oo, xi @ W64[k])
+        sq.index_add_(0, oo, (xi * xi) @ (W64[k] * W64[k]))
+    return ref, sq
+
+
+def bits(a):
+    """The bit patterns of a float32 device tensor (numpy int32): equality of results bit for bit, NaNs included."""
+    return n(a.contiguous().view(torch.int32))
 
 
 def ratios(got, ref, s2):
