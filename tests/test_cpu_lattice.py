@@ -88,6 +88,66 @@ def test_fits_flips_exactly_at_twelve_bytes_per_word(monkeypatch):
     assert below.words == (1 << 31) - (1 << 20) and below.fits(1 << 60)
 
 
+# ---- the one header decoder of the native side (pcc_lattice_from_host / pcc_grid_from_host in csrc/pcc_common.h) ------------
+# Every entry point that takes the 8-int header refuses a bad one with PCC_EINVAL and an error that names the entry point and the
+# lattice -- on the host, before any HIP call (this suite has no device: a HIP call would return PCC_EHIP).  Dummy pointers stand
+# for the device arrays, as in tests/test_cpu_abi.py; nothing reads them.
+GOOD_H = [-8, -16, 8, 3, 5, 7, 4, 2]
+BAD_HEADERS = {
+    "pitch 3": [-8, -16, 8, 3, 5, 7, 3, 2],
+    "pitch 0": [-8, -16, 8, 3, 5, 7, 0, 2],
+    "zero dim": [-8, -16, 8, 3, 0, 7, 4, 2],
+    "zero batches": [-8, -16, 8, 3, 5, 7, 4, 0],
+    "NULL header": None,
+}
+
+
+def _header_calls(L, p, h):
+    """entry point -> call with header h (None: NULL), dummy pointer p for every array, sizes that pass the other checks"""
+    big = 1 << 40
+    return {
+        "pcc_grid_build": lambda: L.pcc_grid_build(p, 10, h, p, p, p, big, None),
+        "pcc_coords_stride_grid": lambda: L.pcc_coords_stride_grid(p, 10, None, h, p, p, p, p, p, big, None),
+        "pcc_keys_canonicalize_grid": lambda: L.pcc_keys_canonicalize_grid(p, 10, h, p, p, p, p, p, p, big, None),
+        "pcc_coords_expand_grid": lambda: L.pcc_coords_expand_grid(p, 10, 3, h, p, p, p, p, p, big, None),
+        "pcc_coords_expand_grid_csr": lambda: L.pcc_coords_expand_grid_csr(p, 10, 3, 2, p, p, h, 10, p, p, p, p, big, None),
+        "pcc_coords_expand_grid_csr_zk": lambda: L.pcc_coords_expand_grid_csr_zk(p, 10, 3, 2, p, p, h, 10, p, p, p, p, big, None),
+        "pcc_coords_expand_grid_csr_slots": lambda: L.pcc_coords_expand_grid_csr_slots(p, 10, 5, 2, p, p, h, 10, p, p, p, p, 0, None),
+        "pcc_coords_expand_csr": lambda: L.pcc_coords_expand_csr(p, 10, 3, 4, h, p, p, p, p, p, big, None),
+        "pcc_kernel_map_build": lambda: L.pcc_kernel_map_build(p, 10, p, 10, 3, 4, 1, 0, p, p, None, None, p, p, h, p, big, None),
+        "pcc_convt_fwd_csr_grid": lambda: L.pcc_convt_fwd_csr_grid(p, 10, 32, p, p, 8, 32, p, p, 10, p, p, 0, 0.0, p, p, p, h, p, None,
+                                                                    0, None, None),
+        "pcc_conv_thin_grid_fwd": lambda: L.pcc_conv_thin_grid_fwd(p, 10, 16, p, p, 1, p, p, p, h, p, p, big, None),
+        "pcc_chconv_fwd": lambda: L.pcc_chconv_fwd(p, 10, p, 4, p, p, h, 4, p, 9, p, 27, 3, p, 4, p, 10, p, None),
+        "pcc_chconv_wgrad": lambda: L.pcc_chconv_wgrad(p, 10, p, 4, p, p, h, 4, p, 9, p, 27, 3, p, 10, p, p, 4, p, big, None),
+        "pcc_geom_occ_ctx": lambda: L.pcc_geom_occ_ctx(p, 10, 4, p, p, h, None, 0, None, None, None, None, p, None),
+        "pcc_normals_grid": lambda: L.pcc_normals_grid(p, 10, p, h, 4, p, p, None),
+        "pcc_curvature_grid": lambda: L.pcc_curvature_grid(p, 10, p, p, h, 4, p, None),
+        "pcc_pcqm_features": lambda: L.pcc_pcqm_features(p, 10, p, p, h, 4, 0.5, p, p, None),
+    }
+
+
+@pytest.mark.parametrize("what", sorted(BAD_HEADERS))
+def test_every_entry_point_refuses_a_bad_header_on_the_host(what):
+    import ctypes
+    from unified_point_cloud_compression_amd import lib
+    L = lib.load()
+    buf = (ctypes.c_int64 * 8)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    values = BAD_HEADERS[what]
+    h = (ctypes.c_int32 * 8)(*values) if values is not None else None
+    calls = _header_calls(L, p, h)
+    assert len(calls) == 17
+    for name, call in sorted(calls.items()):
+        rc = call()
+        err = L.pcc_last_error().decode()
+        assert rc == -1, (name, what, rc, err)                                  # PCC_EINVAL
+        assert err.startswith(name + ":") and "lattice" in err, (name, what, err)
+    # the size query has no status to return: a refused header has no words
+    assert L.pcc_grid_words(h) == 0 and L.pcc_last_error().decode().startswith("pcc_grid_words:")
+    assert L.pcc_grid_words((ctypes.c_int32 * 8)(*GOOD_H)) == 4                  # 2 * 105 cells = 210 bits -> 4 words
+
+
 def test_grid_index_is_a_three_tuple_and_grid_args_of_none():
     S, _ = _S()
     lat = S.Lattice((0, 0, 0), (4, 4, 4), 1, 1)

@@ -256,3 +256,97 @@ def test_stride_chain_equals_stride_link_by_link():
             assert torch.equal(bits, fresh[0]) and torch.equal(rank, fresh[1]) and list(h) == list(fresh[2])
         assert cur is last
         assert root.stride(2) is root._derived[("stride", 2)]          # stride() finds the chain's sets: nothing is rebuilt
+
+
+# ---- the kernels that take a PccLattice by value, at the smallest lattice where a swapped field shows ------------------------
+def _np_keys(C):
+    """b << 48 | (x + 2^15) << 32 | (y + 2^15) << 16 | (z + 2^15), from the definition"""
+    C = np.asarray(C, dtype=np.int64)
+    return (C[:, 0] << 48) | ((C[:, 1] + 32768) << 32) | ((C[:, 2] + 32768) << 16) | (C[:, 3] + 32768)
+
+
+def _np_grid(C, lo, dims, pitch, batches):
+    """bits (uint64, an even number of words) and rank (exclusive prefix popcount per word) of the coordinates C in the lattice"""
+    cell = ((C[:, 0] * dims[0] + (C[:, 1] - lo[0]) // pitch) * dims[1] + (C[:, 2] - lo[1]) // pitch) * dims[2] + (C[:, 3] - lo[2]) // pitch
+    words = ((batches * dims[0] * dims[1] * dims[2] + 63) // 64 + 1) // 2 * 2
+    occ = np.zeros(words * 64, dtype=np.uint64)
+    occ[cell] = 1
+    per_word = occ.reshape(words, 64)
+    bits = (per_word << np.arange(64, dtype=np.uint64)).sum(axis=1, dtype=np.uint64)
+    count = per_word.sum(axis=1).astype(np.int64)
+    return bits, (np.cumsum(count) - count).astype(np.int32)
+
+
+def _np_expand(C, ks, ts_out):
+    """sorted unique output coordinates of the generative expansion and, per output, its ascending pair ids i * K + k
+    (i: canonical input row, k = ix + ks * iy + ks^2 * iz, offsets centred for odd ks and 0 .. ks - 1 for even ks)"""
+    o0 = -(ks - 1) // 2 if ks % 2 else 0
+    lists = {}
+    for i, (b, x, y, z) in enumerate(C.tolist()):
+        for k in range(ks ** 3):
+            off = (k % ks + o0, k // ks % ks + o0, k // (ks * ks) + o0)
+            lists.setdefault((b, x + off[0] * ts_out, y + off[1] * ts_out, z + off[2] * ts_out), []).append(i * ks ** 3 + k)
+    out = sorted(lists)
+    return np.array(out, dtype=np.int64), [sorted(lists[c]) for c in out]
+
+
+def test_small_lattice_with_distinct_dims_through_every_lattice_kernel(monkeypatch):
+    """lo = (-8, -16, 8), dims (3, 5, 7), pitch 4, two batches: 105 cells per batch, so bitmap word 1 straddles the batch
+    boundary and the read-out carries z into y, x and the batch.  About 60 occupied cells as shuffled user rows with duplicates
+    go through canonicalisation on the bitmap (keys, first-wins perm and keep), the grid index, stride(8), and expand(3, 4) /
+    expand(2, 2) on the bitmap and the 32-bit sort, CSR lists included.  Everything is compared exactly with numpy computed
+    here from the definitions; pairwise distinct dims make any mix-up of the lattice fields change a result."""
+    S, L = _S()
+    monkeypatch.setattr(S, "USE_GRID", True)
+    monkeypatch.setattr(S, "CANON_BY_GRID", True)
+    monkeypatch.setattr(S, "STRIDE_BY_GRID", True)
+    monkeypatch.setattr(S, "USE_CSR", True)
+    lo, dims, pitch, batches = np.array([-8, -16, 8]), (3, 5, 7), 4, 2
+    rng = np.random.default_rng(17)
+    pinned = np.array([0, 63, 64, 100, 104, 105, 106, 127, 128, 209])       # both corners of both batches, around word ends
+    cells = np.unique(np.concatenate([pinned, rng.choice(210, 52, replace=False)]))
+    assert 55 <= len(cells) <= 62
+    cz, cy, cx, cb = cells % 7, cells // 7 % 5, cells // 35 % 3, cells // 105
+    Cu = np.stack([cb, lo[0] + pitch * cx, lo[1] + pitch * cy, lo[2] + pitch * cz], axis=1).astype(np.int64)    # canonical order
+    rows = rng.permutation(np.concatenate([np.arange(len(Cu)), rng.integers(0, len(Cu), 25)]))
+    user = Cu[rows]
+    assert np.array_equal(np.sort(_np_keys(Cu)), _np_keys(Cu))                  # ascending cell == ascending key
+    # canonicalisation through the bitmap
+    cs, perm, keep = S.coordset_from_coords(t(user.astype(np.int32)), pitch)
+    assert cs._on_lattice and cs.n == len(Cu)
+    assert np.array_equal(n(cs.keys)[:cs.n], _np_keys(Cu))
+    first_user = np.array([np.nonzero(rows == c)[0].min() for c in range(len(Cu))])
+    want_keep = np.sort(first_user)
+    assert np.array_equal(n(keep), want_keep) and np.array_equal(n(perm), np.searchsorted(want_keep, first_user))
+    # the grid index that came with it, and one built from the canonical keys (pcc_grid_build)
+    want_bits, want_rank = _np_grid(Cu, lo, dims, pitch, batches)
+    assert len(want_bits) == 4
+    for g in (cs.grid(), S.CoordSet(cs.keys[:cs.n].clone(), cs.n, pitch, cs.bounds).grid()):
+        assert list(g.h) == [-8, -16, 8, 3, 5, 7, 4, 2]
+        assert np.array_equal(n(g.bits).view(np.uint64), want_bits) and np.array_equal(n(g.rank), want_rank)
+    # stride(8): floor to multiples of 8 -> lo (-8, -16, 8), dims (2, 3, 4)
+    C8 = Cu.copy()
+    C8[:, 1:] = C8[:, 1:] // 8 * 8
+    C8 = np.unique(C8, axis=0)
+    s8 = cs.stride(8)
+    assert s8.n == len(C8) and np.array_equal(n(s8.keys)[:s8.n], _np_keys(C8))
+    g8 = s8.grid()
+    b8, r8 = _np_grid(C8, lo, (2, 3, 4), 8, batches)
+    assert list(g8.h) == [-8, -16, 8, 2, 3, 4, 8, 2]
+    assert np.array_equal(n(g8.bits).view(np.uint64), b8) and np.array_equal(n(g8.rank), r8)
+    # generative expansions, bitmap marking + grid probing and the 32-bit cell sort
+    for ks, ts_out, want_h in ((3, 4, [-12, -20, 4, 5, 7, 9, 4, 2]), (2, 2, [-8, -16, 8, 6, 10, 14, 2, 2])):
+        Co, lists = _np_expand(Cu, ks, ts_out)
+        for mode in ("bitmap", "sort32"):
+            monkeypatch.setattr(S, "EXPAND_BY_GRID", mode == "bitmap")
+            src = S.CoordSet(cs.keys[:cs.n].clone(), cs.n, pitch, cs.bounds)
+            got = src.expand(ks, ts_out)
+            assert got.n == len(Co) and np.array_equal(n(got.keys)[:got.n], _np_keys(Co)), (ks, mode)
+            first, pair_ids = (n(x) for x in src.csr_map(ks, ts_out))
+            assert len(first) == len(Co) + 1 and first[0] == 0 and first[-1] == len(Cu) * ks ** 3, (ks, mode)
+            assert np.array_equal(first, np.cumsum([0] + [len(v) for v in lists])), (ks, mode)
+            assert np.array_equal(pair_ids[:first[-1]], np.concatenate(lists)), (ks, mode)
+            go = got.grid()
+            bo, ro = _np_grid(Co, want_h[0:3], want_h[3:6], ts_out, batches)
+            assert list(go.h) == want_h, (ks, mode)
+            assert np.array_equal(n(go.bits).view(np.uint64), bo) and np.array_equal(n(go.rank), ro), (ks, mode)

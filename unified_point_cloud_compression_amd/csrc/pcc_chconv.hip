@@ -42,15 +42,16 @@ struct ChQuery {
 
 __device__ inline ChQuery ch_query(const ChArgs& a, long long key) {
   ChQuery d;
-  d.b = key >> 48;
-  d.X = (int)((key >> 32) & 0xFFFF); d.Y = (int)((key >> 16) & 0xFFFF); d.Z = (int)(key & 0xFFFF);
+  d.b = key >> PCC_KEY_B_SHIFT;
+  d.X = (int)((key >> PCC_KEY_X_SHIFT) & PCC_KEY_FIELD); d.Y = (int)((key >> PCC_KEY_Y_SHIFT) & PCC_KEY_FIELD); d.Z = (int)(key & PCC_KEY_FIELD);
   d.cx = d.cy = d.cz = 0; d.zlo = 0; d.nz = 0; d.s = 0;
   d.any = true;
   if (a.g.bits) {
-    const int x = d.X - (int)PCC_BIAS - a.g.lo[0], y = d.Y - (int)PCC_BIAS - a.g.lo[1], z = d.Z - (int)PCC_BIAS - a.g.lo[2];
-    if (d.b >= a.g.nbatch || ((x | y | z) & ((1 << a.g.ts_log2) - 1))) { d.any = false; return d; }
-    d.cx = x >> a.g.ts_log2; d.cy = y >> a.g.ts_log2; d.cz = z >> a.g.ts_log2;
-    const int zlo = max(d.cz - a.radius, 0), zhi = min(d.cz + a.radius, a.g.dims[2] - 1);
+    const PccLattice& L = a.g.lat;
+    const int x = d.X - (int)PCC_BIAS - L.lo[0], y = d.Y - (int)PCC_BIAS - L.lo[1], z = d.Z - (int)PCC_BIAS - L.lo[2];
+    if (d.b >= L.nbatch || ((x | y | z) & ((1 << L.ts_log2) - 1))) { d.any = false; return d; }
+    d.cx = x >> L.ts_log2; d.cy = y >> L.ts_log2; d.cz = z >> L.ts_log2;
+    const int zlo = max(d.cz - a.radius, 0), zhi = min(d.cz + a.radius, L.dims[2] - 1);
     if (zlo > zhi) { d.any = false; return d; }
     d.zlo = zlo; d.nz = zhi - zlo + 1; d.s = zlo - (d.cz - a.radius);
   }
@@ -62,10 +63,11 @@ template <typename F>
 __device__ inline void ch_column(const ChArgs& a, const ChQuery& d, int dx, int dy, unsigned zm, F&& visit) {
   if (a.g.bits) {
     const int nx = d.cx + dx, ny = d.cy + dy;
-    if (nx < 0 || ny < 0 || nx >= a.g.dims[0] || ny >= a.g.dims[1]) return;
+    if (nx < 0 || ny < 0 || nx >= a.g.lat.dims[0] || ny >= a.g.lat.dims[1]) return;
     const unsigned tm = (zm >> d.s) & ((1u << d.nz) - 1u);      // taps inside the lattice, in field bits
     if (!tm) return;
-    const long long cell = ((d.b * a.g.dims[0] + nx) * a.g.dims[1] + ny) * (long long)a.g.dims[2] + d.zlo;
+    // (spelled out: through pcc_lat_cell these kernels come out with other instructions, tools/kernel_identity.py)
+    const long long cell = ((d.b * a.g.lat.dims[0] + nx) * a.g.lat.dims[1] + ny) * (long long)a.g.lat.dims[2] + d.zlo;
     const long long wi = cell >> 6;
     const int sh = (int)(cell & 63);
     const unsigned long long w0 = a.g.bits[wi];
@@ -83,14 +85,15 @@ __device__ inline void ch_column(const ChArgs& a, const ChQuery& d, int dx, int 
     return;
   }
   const int tx = d.X + dx * a.step, ty = d.Y + dy * a.step;
-  if (tx < 0 || ty < 0 || tx > 0xFFFF || ty > 0xFFFF) return;
+  if (tx < 0 || ty < 0 || tx > PCC_KEY_FIELD || ty > PCC_KEY_FIELD) return;
   unsigned m = zm;
   while (m) {
     const int k = __ffs((int)m) - 1;
     m &= m - 1;
     const int tz = d.Z + (k - a.radius) * a.step;
-    if (tz < 0 || tz > 0xFFFF) continue;
-    const long long key = (d.b << 48) | ((long long)tx << 32) | ((long long)ty << 16) | (long long)tz;
+    if (tz < 0 || tz > PCC_KEY_FIELD) continue;
+    const long long key =
+        (d.b << PCC_KEY_B_SHIFT) | ((long long)tx << PCC_KEY_X_SHIFT) | ((long long)ty << PCC_KEY_Y_SHIFT) | (long long)tz;
     const int row = pcc_find((const int64_t*)a.keys, a.n, key);
     if (row >= 0) visit(k, row);
   }
@@ -205,19 +208,11 @@ static int ch_args(ChArgs& a, const int64_t* keys, int64_t n, const float* feat,
               who, kernel_size, c);
   PCC_REQUIRE(ncol >= 1 && ncol <= kernel_size * kernel_size && ntaps >= 1 && ntaps <= kernel_size * kernel_size * kernel_size,
               "%s: %d columns / %d taps do not fit kernel_size %d", who, ncol, ntaps, kernel_size);
-  PCC_REQUIRE(step >= 1 && (step & (step - 1)) == 0, "%s: step %d is not a power of two", who, step);
+  PCC_REQUIRE(pcc_is_pow2(step), "%s: step %d is not a power of two", who, step);
   PCC_REQUIRE(cols && widx && (nq == 0 || query_keys) && (n == 0 || (keys && feat)), "%s: NULL array", who);
   PCC_REQUIRE(n < (1ll << 31) && nq < (1ll << 40), "%s: too many rows", who);
-  if (grid_bits) {
-    PCC_REQUIRE(grid_rank && h_grid, "%s: grid needs rank[] and its 8 host parameters", who);
-    PCC_REQUIRE(h_grid[6] == step, "%s: grid pitch %d differs from the tap step %d", who, h_grid[6], step);
-    a.g.bits = (const unsigned long long*)grid_bits;
-    a.g.rank = grid_rank;
-    for (int i = 0; i < 3; ++i) { a.g.lo[i] = h_grid[i]; a.g.dims[i] = h_grid[3 + i]; }
-    int l = 0; while ((1 << l) < step) ++l;
-    a.g.ts_log2 = l;
-    a.g.nbatch = h_grid[7];
-  }
+  PCC_TRY(pcc_grid_from_host(grid_bits, grid_rank, h_grid, who, &a.g));
+  PCC_REQUIRE(!grid_bits || h_grid[6] == step, "%s: grid pitch %d differs from the tap step %d", who, h_grid[6], step);
   a.keys = (const long long*)keys; a.n = (int)n; a.feat = feat; a.c = c; a.step = step;
   a.cols = cols; a.ncol = ncol; a.widx = widx; a.ntaps = ntaps; a.radius = kernel_size / 2;
   a.q = (const long long*)query_keys; a.nq = nq;

@@ -82,15 +82,6 @@ static inline bool conv_has_h(int K, int cin, int cout) {
   return K >= 64 && cin % 32 == 0 && cin <= 256 && cout % 4 == 0 && bn_for(cout) == 128;
 }
 
-static inline int ilog2_i(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-static inline PccGrid grid_from_host(const uint64_t* bits, const int32_t* rank, const int32_t* h) {
-  PccGrid g;
-  g.bits = (const unsigned long long*)bits; g.rank = rank;
-  for (int i = 0; i < 3; ++i) { g.lo[i] = h[i]; g.dims[i] = h[3 + i]; }
-  g.ts_log2 = ilog2_i(h[6]); g.nbatch = h[7];
-  return g;
-}
-
 // ---- pure device helpers of the VALU kernels: one scalar or one float4 of channels per lane (the thin kernels of
 //      pcc_conv_thin.hip and the gather-sums of pcc_convt.hip), and the activation every epilogue applies ------------------------
 template <int VEC> struct ThinVec;

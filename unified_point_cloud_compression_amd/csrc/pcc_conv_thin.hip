@@ -689,8 +689,8 @@ __global__ void k_band_segments(const long long* __restrict__ keys, long long n,
   long long b = 0, e = 0;
   if (cy0 < cy1) {
     const long long y0 = (long long)lo_y + (long long)cy0 * ts + PCC_BIAS, y1 = (long long)lo_y + (long long)cy1 * ts + PCC_BIAS;
-    b = lower((x << 32) | (y0 << 16));
-    e = lower((x << 32) | (y1 << 16));
+    b = lower((x << PCC_KEY_X_SHIFT) | (y0 << PCC_KEY_Y_SHIFT));      // (batch 0, below every z)
+    e = lower((x << PCC_KEY_X_SHIFT) | (y1 << PCC_KEY_Y_SHIFT));
   }
   seg_row0[sidx] = (int)b;
   seg_tiles[sidx] = (int)((e - b + 15) / 16);
@@ -805,11 +805,12 @@ __global__ void __launch_bounds__(256) k_thin_gather_grid(ThinGridArgs a) {
   if (p >= a.n) return;
   const PccGrid& g = a.g;
   const long long key = a.keys[p];
-  const int b = (int)(key >> 48);
-  const int cx = (((int)((key >> 32) & 0xFFFF) - (int)PCC_BIAS - g.lo[0]) >> g.ts_log2);
-  const int cy = (((int)((key >> 16) & 0xFFFF) - (int)PCC_BIAS - g.lo[1]) >> g.ts_log2);
-  const int cz = (((int)(key & 0xFFFF) - (int)PCC_BIAS - g.lo[2]) >> g.ts_log2);
-  const int z_lo = cz > 0 ? cz - 1 : 0, z_hi = cz + 1 < g.dims[2] ? cz + 1 : g.dims[2] - 1;
+  const PccLattice& L = g.lat;
+  const int b = pcc_key_b(key);
+  const int cx = (pcc_key_x(key) - L.lo[0]) >> L.ts_log2;
+  const int cy = (pcc_key_y(key) - L.lo[1]) >> L.ts_log2;
+  const int cz = (pcc_key_z(key) - L.lo[2]) >> L.ts_log2;
+  const int z_lo = cz > 0 ? cz - 1 : 0, z_hi = cz + 1 < L.dims[2] ? cz + 1 : L.dims[2] - 1;
   const int nz = z_hi - z_lo + 1;
   float acc[COUT_MAX];
 #pragma unroll
@@ -818,8 +819,9 @@ __global__ void __launch_bounds__(256) k_thin_gather_grid(ThinGridArgs a) {
 #pragma unroll
   for (int c = 0; c < 9; ++c) {
     const int nx = cx + c % 3 - 1, ny = cy + c / 3 - 1;
-    if (nx < 0 || ny < 0 || nx >= g.dims[0] || ny >= g.dims[1]) continue;
-    const long long cell = (((long long)b * g.dims[0] + nx) * g.dims[1] + ny) * g.dims[2] + z_lo;
+    if (nx < 0 || ny < 0 || nx >= L.dims[0] || ny >= L.dims[1]) continue;
+    // (spelled out: through pcc_lat_cell this kernel comes out with other instructions, tools/kernel_identity.py)
+    const long long cell = (((long long)b * L.dims[0] + nx) * L.dims[1] + ny) * L.dims[2] + z_lo;
     const long long wi = cell >> 6;
     const int sh = (int)(cell & 63);
     const unsigned long long w0 = g.bits[wi];
@@ -851,11 +853,12 @@ __global__ void __launch_bounds__(256) k_thin_gather_grid1(ThinGridArgs a) {
   if (p >= a.n) return;
   const PccGrid& g = a.g;
   const long long key = a.keys[p];
-  const int b = (int)(key >> 48);
-  const int cx = (((int)((key >> 32) & 0xFFFF) - (int)PCC_BIAS - g.lo[0]) >> g.ts_log2);
-  const int cy = (((int)((key >> 16) & 0xFFFF) - (int)PCC_BIAS - g.lo[1]) >> g.ts_log2);
-  const int cz = (((int)(key & 0xFFFF) - (int)PCC_BIAS - g.lo[2]) >> g.ts_log2);
-  const int z_lo = cz > 0 ? cz - 1 : 0, z_hi = cz + 1 < g.dims[2] ? cz + 1 : g.dims[2] - 1;
+  const PccLattice& L = g.lat;
+  const int b = pcc_key_b(key);
+  const int cx = (pcc_key_x(key) - L.lo[0]) >> L.ts_log2;
+  const int cy = (pcc_key_y(key) - L.lo[1]) >> L.ts_log2;
+  const int cz = (pcc_key_z(key) - L.lo[2]) >> L.ts_log2;
+  const int z_lo = cz > 0 ? cz - 1 : 0, z_hi = cz + 1 < L.dims[2] ? cz + 1 : L.dims[2] - 1;
   const int nz = z_hi - z_lo + 1;
   const int dz0 = z_lo - cz + 1;
   unsigned long long w0[9], w1[9];
@@ -864,8 +867,8 @@ __global__ void __launch_bounds__(256) k_thin_gather_grid1(ThinGridArgs a) {
 #pragma unroll
   for (int c = 0; c < 9; ++c) {
     const int nx = cx + c % 3 - 1, ny = cy + c / 3 - 1;
-    ok[c] = !(nx < 0 || ny < 0 || nx >= g.dims[0] || ny >= g.dims[1]);
-    const long long cell = ok[c] ? (((long long)b * g.dims[0] + nx) * g.dims[1] + ny) * g.dims[2] + z_lo : 0ll;
+    ok[c] = !(nx < 0 || ny < 0 || nx >= L.dims[0] || ny >= L.dims[1]);
+    const long long cell = ok[c] ? pcc_lat_cell(L, b, nx, ny, z_lo) : 0ll;
     const long long wi = cell >> 6;
     sh[c] = (int)(cell & 63);
     w0[c] = g.bits[wi];
@@ -970,11 +973,12 @@ __global__ void __launch_bounds__(256) k_thin_gather_grid1z(ThinGridArgs a) {
   if (p >= a.n) return;
   const PccGrid& g = a.g;
   const long long key = a.keys[p];
-  const int b = (int)(key >> 48);
-  const int cx = (((int)((key >> 32) & 0xFFFF) - (int)PCC_BIAS - g.lo[0]) >> g.ts_log2);
-  const int cy = (((int)((key >> 16) & 0xFFFF) - (int)PCC_BIAS - g.lo[1]) >> g.ts_log2);
-  const int cz = (((int)(key & 0xFFFF) - (int)PCC_BIAS - g.lo[2]) >> g.ts_log2);
-  const int z_lo = cz > 0 ? cz - 1 : 0, z_hi = cz + 1 < g.dims[2] ? cz + 1 : g.dims[2] - 1;
+  const PccLattice& L = g.lat;
+  const int b = pcc_key_b(key);
+  const int cx = (pcc_key_x(key) - L.lo[0]) >> L.ts_log2;
+  const int cy = (pcc_key_y(key) - L.lo[1]) >> L.ts_log2;
+  const int cz = (pcc_key_z(key) - L.lo[2]) >> L.ts_log2;
+  const int z_lo = cz > 0 ? cz - 1 : 0, z_hi = cz + 1 < L.dims[2] ? cz + 1 : L.dims[2] - 1;
   const int nz = z_hi - z_lo + 1;
   const int dz0 = z_lo - cz + 1;                                      // dz index (0, 1, 2 = -1, 0, +1) of the field's bit 0
   unsigned long long w0[9], w1[9];
@@ -983,8 +987,8 @@ __global__ void __launch_bounds__(256) k_thin_gather_grid1z(ThinGridArgs a) {
 #pragma unroll
   for (int c = 0; c < 9; ++c) {
     const int nx = cx + c % 3 - 1, ny = cy + c / 3 - 1;
-    ok[c] = !(nx < 0 || ny < 0 || nx >= g.dims[0] || ny >= g.dims[1]);
-    const long long cell = ok[c] ? (((long long)b * g.dims[0] + nx) * g.dims[1] + ny) * g.dims[2] + z_lo : 0ll;
+    ok[c] = !(nx < 0 || ny < 0 || nx >= L.dims[0] || ny >= L.dims[1]);
+    const long long cell = ok[c] ? pcc_lat_cell(L, b, nx, ny, z_lo) : 0ll;
     const long long wi = cell >> 6;
     sh[c] = (int)(cell & 63);
     w0[c] = g.bits[wi];
@@ -1039,7 +1043,9 @@ extern "C" int pcc_conv_thin_grid_fwd(const float* feat, int64_t n, int32_t cin,
                                       void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (n <= 0) return PCC_OK;
-  PCC_REQUIRE(feat && packed_w && keys && bits && rank && h_grid && out && ws, "pcc_conv_thin_grid_fwd: NULL array");
+  PCC_REQUIRE(feat && packed_w && keys && bits && rank && out && ws, "pcc_conv_thin_grid_fwd: NULL array");
+  PccGrid g;
+  PCC_TRY(pcc_grid_from_host(bits, rank, h_grid, "pcc_conv_thin_grid_fwd", &g));
   PCC_REQUIRE(cout >= 1 && cout <= 4 && conv_kind(27, cin, cout) == KIND_THIN_T, "pcc_conv_thin_grid_fwd: unsupported shape cin=%d cout=%d", cin, cout);
   if (ws_bytes < pcc_thin_grid_ws_bytes(n, cout)) { pcc_set_error("pcc_conv_thin_grid_fwd: workspace too small"); return PCC_EWS; }
   float* t = (float*)ws;
@@ -1049,7 +1055,7 @@ extern "C" int pcc_conv_thin_grid_fwd(const float* feat, int64_t n, int32_t cin,
     k_thin_project_z<16><<<(unsigned)pcc_cdiv(n, 256), 256, (size_t)27 * 16 * sizeof(float), s>>>(
         feat, (const long long*)keys, n, (long long)h_grid[6], packed_w, t);
     ThinGridArgs az;
-    az.t = t; az.bias = bias; az.keys = (const long long*)keys; az.g = grid_from_host(bits, rank, h_grid); az.out = out; az.n = n; az.cout = 1;
+    az.t = t; az.bias = bias; az.keys = (const long long*)keys; az.g = g; az.out = out; az.n = n; az.cout = 1;
     k_thin_gather_grid1z<<<(unsigned)pcc_cdiv(n, 256), 256, 0, s>>>(az);
     PCC_LAUNCH_CHECK();
     return PCC_OK;
@@ -1062,7 +1068,7 @@ extern "C" int pcc_conv_thin_grid_fwd(const float* feat, int64_t n, int32_t cin,
     default: PCC_TRY(launch_project<64>(feat, n, packed_w, kc, t, s)); break;
   }
   ThinGridArgs a;
-  a.t = t; a.bias = bias; a.keys = (const long long*)keys; a.g = grid_from_host(bits, rank, h_grid); a.out = out; a.n = n; a.cout = cout;
+  a.t = t; a.bias = bias; a.keys = (const long long*)keys; a.g = g; a.out = out; a.n = n; a.cout = cout;
   if (cout == 1 && (size_t)27 * n * 4 <= (size_t)BUF_MAX_BYTES) k_thin_gather_grid1<<<(unsigned)pcc_cdiv(n, 256), 256, 0, s>>>(a);
   else if (cout == 1) k_thin_gather_grid<1><<<(unsigned)pcc_cdiv(n, 256), 256, 0, s>>>(a);
   else k_thin_gather_grid<4><<<(unsigned)pcc_cdiv(n, 256), 256, 0, s>>>(a);

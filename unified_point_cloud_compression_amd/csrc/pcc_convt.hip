@@ -388,17 +388,18 @@ __global__ void __launch_bounds__(256) k_convt_gather_csr(GatherCsrArgs a) {
     present = m;
   } else if (a.ex_grid.bits) {
     const PccGrid& g = a.ex_grid;
+    const PccLattice& L = g.lat;
     const long long key = a.out_keys[o];
-    const int b = (int)(key >> 48);
-    const int cx = (((int)((key >> 32) & 0xFFFF) - (int)PCC_BIAS - g.lo[0]) >> g.ts_log2);
-    const int cy = (((int)((key >> 16) & 0xFFFF) - (int)PCC_BIAS - g.lo[1]) >> g.ts_log2);
-    const int cz = (((int)(key & 0xFFFF) - (int)PCC_BIAS - g.lo[2]) >> g.ts_log2);
-    const int z_lo = cz > 0 ? cz - 1 : 0, z_hi = cz + 1 < g.dims[2] ? cz + 1 : g.dims[2] - 1;
+    const int b = pcc_key_b(key);
+    const int cx = (pcc_key_x(key) - L.lo[0]) >> L.ts_log2;
+    const int cy = (pcc_key_y(key) - L.lo[1]) >> L.ts_log2;
+    const int cz = (pcc_key_z(key) - L.lo[2]) >> L.ts_log2;
+    const int z_lo = cz > 0 ? cz - 1 : 0, z_hi = cz + 1 < L.dims[2] ? cz + 1 : L.dims[2] - 1;
     p_nz = z_hi - z_lo + 1;
     p_dz0 = z_lo - cz + 1;
-    const long long col_stride = g.dims[2], slab_stride = (long long)g.dims[1] * g.dims[2];
-    const long long cell0 = (((long long)b * g.dims[0] + cx) * g.dims[1] + cy) * g.dims[2] + z_lo;
-    const long long cells = (long long)g.nbatch * g.dims[0] * slab_stride;
+    const long long col_stride = L.dims[2], slab_stride = (long long)L.dims[1] * L.dims[2];
+    const long long cell0 = pcc_lat_cell(L, b, cx, cy, z_lo);
+    const long long cells = (long long)L.nbatch * L.dims[0] * slab_stride;
     const long long last_dw = 2 * ((cells + 63) >> 6) - 2;
     const unsigned* const bits32 = reinterpret_cast<const unsigned*>(g.bits);
     const int step = lpr < 9 ? lpr : 9;
@@ -407,7 +408,7 @@ __global__ void __launch_bounds__(256) k_convt_gather_csr(GatherCsrArgs a) {
       const int c = cl + t * step;
       const int dx = c % 3 - 1, dy = c / 3 - 1;
       const int nx = cx + dx, ny = cy + dy;
-      const bool ok = c < 9 && (lpr >= 9 ? t == 0 : true) && nx >= 0 && ny >= 0 && nx < g.dims[0] && ny < g.dims[1];
+      const bool ok = c < 9 && (lpr >= 9 ? t == 0 : true) && nx >= 0 && ny >= 0 && nx < L.dims[0] && ny < L.dims[1];
       const long long cell = ok ? cell0 + dx * slab_stride + dy * col_stride : 0ll;
       const long long dw = cell >> 5, dw2 = dw < last_dw ? dw : last_dw;
       psh[t] = ok ? (int)(cell & 31) + 32 * (int)(dw - dw2) : 64;
@@ -555,8 +556,9 @@ extern "C" int pcc_convt_fwd_csr_grid(const float* feat_in, int64_t n_in, int32_
                                       const int64_t* out_keys, const uint64_t* out_bits, const int32_t* out_rank,
                                       const int32_t* h_out, const float* ex_bias, const int32_t* wg_end, int32_t arith,
                                       int32_t* d_guard, void* stream) {
-  PCC_REQUIRE(out_keys && out_bits && out_rank && h_out && ex_bias, "pcc_convt_fwd_csr_grid: NULL array");
-  const PccGrid ex = grid_from_host(out_bits, out_rank, h_out);
+  PCC_REQUIRE(out_keys && out_bits && out_rank && ex_bias, "pcc_convt_fwd_csr_grid: NULL array");
+  PccGrid ex;
+  PCC_TRY(pcc_grid_from_host(out_bits, out_rank, h_out, "pcc_convt_fwd_csr_grid", &ex));
   return convt_fwd_csr_impl(feat_in, n_in, cin, packed_w, bias, K, cout, first, pair_ids, n_out, T, out, act, slope,
                             nullptr, 27, ex_bias, &ex, (const long long*)out_keys, arith, d_guard, stream, wg_end);
 }

@@ -26,7 +26,7 @@ __global__ void __launch_bounds__(256) k_gauss(const float* __restrict__ y, cons
   const float scale = params[r * 2 * c + ch];
   const float mean = params[r * 2 * c + c + ch];
   float g = 1.f;
-  if (gain) g = gain[(keys[r] >> 48) * c + ch];
+  if (gain) g = gain[(keys[r] >> PCC_KEY_B_SHIFT) * c + ch];
   const float s = gauss_bound_scale(scale, g);
   if (idx) idx[t] = table_index(s, tab, nt);
   if (ENCODE) {
@@ -497,7 +497,7 @@ __global__ void __launch_bounds__(256) k_focal_rows(const float* __restrict__ lo
   const bool inside = v >= 1e-2f;                      // (v <= 1 always)
   const float pt = inside ? v : 1e-2f;
   const float a = occ ? alpha : 1.f - alpha;
-  const float w = q_map[(keys[t] >> 48) * q_pitch];
+  const float w = q_map[(keys[t] >> PCC_KEY_B_SHIFT) * q_pitch];
   const float om = 1.f - pt;
   const float pw = powf(om, gamma), lg = logf(pt);
   f[t] = -a * pw * lg * w;

@@ -21,8 +21,7 @@ static constexpr int GEOM_LDS = GEOM_CTX * 255 + 8;     // byte 0 does not occur
 
 __device__ inline bool geom_has(const PccGrid& g, const int64_t* __restrict__ keys, int n, int x, int y, int z) {
   if ((x | y | z) < 0 || x >= (int)PCC_BIAS || y >= (int)PCC_BIAS || z >= (int)PCC_BIAS) return false;
-  const int64_t q = ((int64_t)(x + (int)PCC_BIAS) << 32) | ((int64_t)(y + (int)PCC_BIAS) << 16) | (int64_t)(z + (int)PCC_BIAS);
-  return pcc_lookup(g, keys, n, q) >= 0;
+  return pcc_lookup(g, keys, n, pcc_key_pack(0, x, y, z)) >= 0;
 }
 
 __global__ void __launch_bounds__(256) k_geom_occ_ctx(const int64_t* __restrict__ keys, int n, PccGrid g, int pitch,
@@ -31,9 +30,7 @@ __global__ void __launch_bounds__(256) k_geom_occ_ctx(const int64_t* __restrict_
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int64_t key = keys[i];
-  const int x = (int)((key >> 32) & 0xFFFF) - (int)PCC_BIAS;
-  const int y = (int)((key >> 16) & 0xFFFF) - (int)PCC_BIAS;
-  const int z = (int)(key & 0xFFFF) - (int)PCC_BIAS;
+  const int x = pcc_key_x(key), y = pcc_key_y(key), z = pcc_key_z(key);
   int c = 0;
   c |= geom_has(g, keys, n, x - pitch, y, z) ? 1 : 0;
   c |= geom_has(g, keys, n, x + pitch, y, z) ? 2 : 0;
@@ -100,7 +97,8 @@ __global__ void __launch_bounds__(256) k_geom_expand(const int64_t* __restrict__
     const int j = __ffs(s) - 1;
     s &= s - 1;
     if (o >= 0 && o < cap)
-      out[o] = key + ((int64_t)(((j >> 2) & 1) * cp) << 32) + ((int64_t)(((j >> 1) & 1) * cp) << 16) + (int64_t)((j & 1) * cp);
+      out[o] = key + ((int64_t)(((j >> 2) & 1) * cp) << PCC_KEY_X_SHIFT) + ((int64_t)(((j >> 1) & 1) * cp) << PCC_KEY_Y_SHIFT) +
+               (int64_t)((j & 1) * cp);
     ++o;
   }
 }
@@ -110,12 +108,14 @@ __global__ void __launch_bounds__(256) k_geom_finish(const int64_t* __restrict__
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int64_t key = keys[i];
-  const int x = (int)((key >> 32) & 0xFFFF) - (int)PCC_BIAS + ox;
-  const int y = (int)((key >> 16) & 0xFFFF) - (int)PCC_BIAS + oy;
-  const int z = (int)(key & 0xFFFF) - (int)PCC_BIAS + oz;
-  if (out_keys)
-    out_keys[i] = ((int64_t)((x + (int)PCC_BIAS) & 0xFFFF) << 32) | ((int64_t)((y + (int)PCC_BIAS) & 0xFFFF) << 16) |
-                  (int64_t)((z + (int)PCC_BIAS) & 0xFFFF);
+  // (fields read in place, not through pcc_key_x/y/z: with the accessors the compiler no longer cancels the two biases below and
+  //  this kernel comes out with other instructions, tools/kernel_identity.py)
+  const int x = (int)((key >> PCC_KEY_X_SHIFT) & PCC_KEY_FIELD) - (int)PCC_BIAS + ox;
+  const int y = (int)((key >> PCC_KEY_Y_SHIFT) & PCC_KEY_FIELD) - (int)PCC_BIAS + oy;
+  const int z = (int)(key & PCC_KEY_FIELD) - (int)PCC_BIAS + oz;
+  if (out_keys)      // (batch 0; each field wraps inside its 16 bits, so a coordinate outside the key range cannot carry into the next)
+    out_keys[i] = ((int64_t)((x + (int)PCC_BIAS) & PCC_KEY_FIELD) << PCC_KEY_X_SHIFT) |
+                  ((int64_t)((y + (int)PCC_BIAS) & PCC_KEY_FIELD) << PCC_KEY_Y_SHIFT) | (int64_t)((z + (int)PCC_BIAS) & PCC_KEY_FIELD);
   if (out_xyz) { out_xyz[3 * i] = x; out_xyz[3 * i + 1] = y; out_xyz[3 * i + 2] = z; }
 }
 
@@ -230,27 +230,21 @@ __global__ void __launch_bounds__(256) k_geom_state_update(unsigned long long* _
   if (i < GEOM_HIST) A[i] = (A[i] >> 1) + hist[i];
 }
 
-static bool geom_pitch_ok(int p) { return p >= 1 && p <= (1 << 15) && (p & (p - 1)) == 0; }
-
-static PccGrid geom_grid(const uint64_t* bits, const int32_t* rank, const int32_t* h) {
-  if (bits && rank && h) return grid_from_host(bits, rank, h);
-  PccGrid g{};
-  return g;                                   // bits == nullptr: binary search over the keys
-}
-
 extern "C" int pcc_geom_occ_ctx(const int64_t* keys, int64_t n, int32_t pitch, const uint64_t* bits, const int32_t* rank,
                                 const int32_t* h_grid, const int64_t* child_keys, int64_t n_child, const uint64_t* child_bits,
                                 const int32_t* child_rank, const int32_t* h_child, int32_t* sym, int32_t* ctx, void* stream) {
   PCC_REQUIRE(keys && ctx && n > 0 && n < (1ll << 31), "pcc_geom_occ_ctx: bad arguments");
-  PCC_REQUIRE(geom_pitch_ok(pitch), "pcc_geom_occ_ctx: pitch %d is not a power of two in [1, 2^15]", pitch);
+  PCC_REQUIRE(pcc_is_pow2(pitch) && pitch <= (1 << 15), "pcc_geom_occ_ctx: pitch %d is not a power of two in [1, 2^15]", pitch);
+  PccGrid g, cg;                              // bits == NULL: binary search over the keys
+  PCC_TRY(pcc_grid_from_host(bits, rank, h_grid, "pcc_geom_occ_ctx", &g));
+  PCC_TRY(pcc_grid_from_host(sym ? child_bits : nullptr, child_rank, h_child, "pcc_geom_occ_ctx", &cg));
   PCC_REQUIRE(!h_grid || h_grid[6] == pitch, "pcc_geom_occ_ctx: the level's grid has another pitch");
   if (sym) {
     PCC_REQUIRE(child_keys && n_child > 0 && n_child < (1ll << 31) && pitch >= 2, "pcc_geom_occ_ctx: bytes need a child set at half the pitch");
     PCC_REQUIRE(!h_child || h_child[6] == pitch / 2, "pcc_geom_occ_ctx: the child grid has another pitch");
   }
-  k_geom_occ_ctx<<<(unsigned)pcc_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(
-      keys, (int)n, geom_grid(bits, rank, h_grid), pitch, child_keys, (int)n_child,
-      sym ? geom_grid(child_bits, child_rank, h_child) : geom_grid(nullptr, nullptr, nullptr), sym, ctx);
+  k_geom_occ_ctx<<<(unsigned)pcc_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(keys, (int)n, g, pitch, child_keys, (int)n_child, cg, sym,
+                                                                             ctx);
   PCC_LAUNCH_CHECK();
   return PCC_OK;
 }
@@ -286,7 +280,7 @@ extern "C" int pcc_geom_child_offsets(const int32_t* sym, int64_t n, int32_t* of
 extern "C" int pcc_geom_expand(const int64_t* keys, const int32_t* sym, const int32_t* off, int64_t n, int32_t child_pitch,
                                int64_t* out_keys, int64_t cap, void* stream) {
   PCC_REQUIRE(keys && sym && off && out_keys && n > 0 && n < (1ll << 27) && cap >= n, "pcc_geom_expand: bad arguments");
-  PCC_REQUIRE(geom_pitch_ok(child_pitch) && child_pitch < (1 << 15), "pcc_geom_expand: bad child pitch %d", child_pitch);
+  PCC_REQUIRE(pcc_is_pow2(child_pitch) && child_pitch < (1 << 15), "pcc_geom_expand: bad child pitch %d", child_pitch);
   k_geom_expand<<<(unsigned)pcc_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(keys, sym, off, (int)n, child_pitch, cap, out_keys);
   PCC_LAUNCH_CHECK();
   return PCC_OK;

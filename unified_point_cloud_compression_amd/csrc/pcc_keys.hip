@@ -38,23 +38,18 @@ extern "C" int pcc_device_info(int* h_cu_count, char* h_arch, int h_arch_len) {
 // ------------------------------------------------------------------------------------------
 // pack / unpack
 // ------------------------------------------------------------------------------------------
-__device__ inline int64_t pack4(int b, int x, int y, int z) {
-  return ((int64_t)b << 48) | ((int64_t)(x + PCC_BIAS) << 32) | ((int64_t)(y + PCC_BIAS) << 16) |
-         (int64_t)(z + PCC_BIAS);
-}
-
 __global__ void k_pack_i32(const int4* __restrict__ c, int64_t n, int64_t* __restrict__ keys) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int4 v = c[i];
-  keys[i] = pack4(v.x, v.y, v.z, v.w);
+  keys[i] = pcc_key_pack(v.x, v.y, v.z, v.w);
 }
 
 __global__ void k_pack_f32(const float4* __restrict__ c, int64_t n, int64_t* __restrict__ keys) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float4 v = c[i];
-  keys[i] = pack4((int)floorf(v.x), (int)floorf(v.y), (int)floorf(v.z), (int)floorf(v.w));
+  keys[i] = pcc_key_pack((int)floorf(v.x), (int)floorf(v.y), (int)floorf(v.z), (int)floorf(v.w));
 }
 
 __global__ void k_unpack(const int64_t* __restrict__ keys, int64_t n, int4* __restrict__ c) {
@@ -62,10 +57,10 @@ __global__ void k_unpack(const int64_t* __restrict__ keys, int64_t n, int4* __re
   if (i >= n) return;
   const int64_t k = keys[i];
   int4 v;
-  v.x = (int)(k >> 48);
-  v.y = (int)((k >> 32) & 0xFFFF) - (int)PCC_BIAS;
-  v.z = (int)((k >> 16) & 0xFFFF) - (int)PCC_BIAS;
-  v.w = (int)(k & 0xFFFF) - (int)PCC_BIAS;
+  v.x = pcc_key_b(k);
+  v.y = pcc_key_x(k);
+  v.z = pcc_key_y(k);
+  v.w = pcc_key_z(k);
   c[i] = v;
 }
 
@@ -103,7 +98,7 @@ __global__ void k_batch_bounds(const long long* __restrict__ keys, const long lo
                                long long* __restrict__ out_a, long long* __restrict__ out_b, long long* __restrict__ out_c) {
   const int e = threadIdx.x;
   if (e >= entries) return;
-  const long long n = d_n ? *d_n : n_host, target = (long long)e << 48;
+  const long long n = d_n ? *d_n : n_host, target = (long long)e << PCC_KEY_B_SHIFT;
   long long lo = 0, hi = n;
   while (lo < hi) {
     const long long mid = (lo + hi) >> 1;
@@ -519,7 +514,6 @@ __global__ void k_mask_keys(const int64_t* __restrict__ in, int64_t n, int64_t m
   if (i < n) out[i] = in[i] & mask;
 }
 
-static bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
 extern "C" size_t pcc_stride_ws_bytes(int64_t n) {
   if (n <= 0) return 256;
@@ -531,7 +525,7 @@ extern "C" int pcc_coords_stride(const int64_t* keys, int64_t n, int32_t new_str
                                  void* stream) {
   hipStream_t s = (hipStream_t)stream;
   PCC_REQUIRE(d_count, "pcc_coords_stride: d_count is NULL");
-  PCC_REQUIRE(is_pow2(new_stride) && new_stride <= (1 << 14), "pcc_coords_stride: tensor stride %d is not a power of two",
+  PCC_REQUIRE(pcc_is_pow2(new_stride) && new_stride <= (1 << 14), "pcc_coords_stride: tensor stride %d is not a power of two",
               new_stride);
   if (n <= 0) {
     PCC_CHECK_HIP(hipMemsetAsync(d_count, 0, sizeof(int64_t), s));
@@ -542,8 +536,8 @@ extern "C" int pcc_coords_stride(const int64_t* keys, int64_t n, int32_t new_str
     return PCC_EWS;
   }
   // floor(c/m)*m on a biased field == clearing its low bits (2^15 is a multiple of m)
-  const int64_t fm = 0xFFFF & ~(int64_t)(new_stride - 1);
-  const int64_t mask = (int64_t)((0xFFFFull << 48) | ((uint64_t)fm << 32) | ((uint64_t)fm << 16) | (uint64_t)fm);
+  const uint64_t fm = PCC_KEY_FIELD & ~(uint64_t)(new_stride - 1);
+  const int64_t mask = (int64_t)(((uint64_t)PCC_KEY_FIELD << PCC_KEY_B_SHIFT) | (fm << PCC_KEY_X_SHIFT) | (fm << PCC_KEY_Y_SHIFT) | fm);
   char* p = (char*)ws;
   int64_t* masked = (int64_t*)p;  p += pcc_align_up((size_t)n * 8);
   int64_t* sorted = (int64_t*)p;  p += pcc_align_up((size_t)n * 8);
@@ -609,20 +603,13 @@ extern "C" int pcc_coords_expand(const int64_t* keys, int64_t n, int32_t kernel_
 //   transposed map, with no neighbour search at all.  The sort is stable, so each list is ordered by pair id:
 //   a fixed summation order (deterministic).
 // ------------------------------------------------------------------------------------------
-struct Lattice { int lo[3]; int dims[3]; int ts_log2; int nbatch; };
-
-__global__ void k_expand_cells(const int64_t* __restrict__ in, int64_t n, int K, int ks, int step, Lattice L,
+__global__ void k_expand_cells(const int64_t* __restrict__ in, int64_t n, int K, int ks, int step, PccLattice L,
                                unsigned* __restrict__ cells) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n * K) return;
   const int64_t i = t / K;
   const int k = (int)(t - i * K);
-  const int64_t key = in[i] + pcc_delta_of(k, ks, step);
-  const int b = (int)(key >> 48);
-  const int cx = ((int)((key >> 32) & 0xFFFF) - (int)PCC_BIAS - L.lo[0]) >> L.ts_log2;
-  const int cy = ((int)((key >> 16) & 0xFFFF) - (int)PCC_BIAS - L.lo[1]) >> L.ts_log2;
-  const int cz = ((int)(key & 0xFFFF) - (int)PCC_BIAS - L.lo[2]) >> L.ts_log2;
-  cells[t] = (unsigned)((((long long)b * L.dims[0] + cx) * L.dims[1] + cy) * L.dims[2] + cz);
+  cells[t] = (unsigned)pcc_lat_cell_of_key(L, in[i] + pcc_delta_of(k, ks, step));
 }
 
 __global__ void k_cell_flags(const unsigned* __restrict__ c, int64_t n, int* __restrict__ flag) {
@@ -630,7 +617,7 @@ __global__ void k_cell_flags(const unsigned* __restrict__ c, int64_t n, int* __r
   if (i < n) flag[i] = (i == 0 || c[i] != c[i - 1]) ? 1 : 0;
 }
 
-__global__ void k_cell_unique(const unsigned* __restrict__ c, int64_t n, const int* __restrict__ pos, Lattice L,
+__global__ void k_cell_unique(const unsigned* __restrict__ c, int64_t n, const int* __restrict__ pos, PccLattice L,
                               int64_t* __restrict__ out_keys, int* __restrict__ first, int64_t* __restrict__ d_count) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -640,10 +627,7 @@ __global__ void k_cell_unique(const unsigned* __restrict__ c, int64_t n, const i
     const int cz = cell % L.dims[2]; cell /= L.dims[2];
     const int cy = cell % L.dims[1]; cell /= L.dims[1];
     const int cx = cell % L.dims[0]; cell /= L.dims[0];
-    const int64_t x = ((int64_t)cx << L.ts_log2) + L.lo[0] + PCC_BIAS;
-    const int64_t y = ((int64_t)cy << L.ts_log2) + L.lo[1] + PCC_BIAS;
-    const int64_t z = ((int64_t)cz << L.ts_log2) + L.lo[2] + PCC_BIAS;
-    out_keys[pos[i]] = ((int64_t)cell << 48) | (x << 32) | (y << 16) | z;
+    out_keys[pos[i]] = pcc_lat_key(L, (int)cell, cx, cy, cz);
     first[pos[i]] = (int)i;
   }
   if (i == n - 1) {
@@ -665,8 +649,10 @@ extern "C" int pcc_coords_expand_csr(const int64_t* keys, int64_t n, int32_t ker
                                      const int32_t* h_lattice, int64_t* out_keys, int64_t* d_count,
                                      int32_t* pair_ids, int32_t* first, void* ws, size_t ws_bytes, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  PCC_REQUIRE(d_count && h_lattice, "pcc_coords_expand_csr: NULL argument");
-  PCC_REQUIRE(kernel_size >= 1 && kernel_size <= 5 && ts_out >= 1 && (ts_out & (ts_out - 1)) == 0,
+  PccLattice L;
+  PCC_TRY(pcc_lattice_from_host(h_lattice, "pcc_coords_expand_csr", &L));
+  PCC_REQUIRE(d_count, "pcc_coords_expand_csr: NULL argument");
+  PCC_REQUIRE(kernel_size >= 1 && kernel_size <= 5 && pcc_is_pow2(ts_out),
               "pcc_coords_expand_csr: unsupported kernel_size %d / ts_out %d", kernel_size, ts_out);
   if (n <= 0) {
     PCC_CHECK_HIP(hipMemsetAsync(d_count, 0, sizeof(int64_t), s));
@@ -674,11 +660,7 @@ extern "C" int pcc_coords_expand_csr(const int64_t* keys, int64_t n, int32_t ker
     return PCC_OK;
   }
   PCC_REQUIRE(keys && out_keys && pair_ids && first && ws, "pcc_coords_expand_csr: NULL array");
-  Lattice L;
-  for (int i = 0; i < 3; ++i) { L.lo[i] = h_lattice[i]; L.dims[i] = h_lattice[3 + i]; }
   PCC_REQUIRE(h_lattice[6] == ts_out, "pcc_coords_expand_csr: lattice pitch must equal ts_out");
-  int l = 0; while ((1 << l) < ts_out) ++l;
-  L.ts_log2 = l; L.nbatch = h_lattice[7];
   const long long cells = (long long)L.nbatch * L.dims[0] * L.dims[1] * L.dims[2];
   PCC_REQUIRE(cells > 0 && cells <= 0xFFFFFFFFll, "pcc_coords_expand_csr: lattice has %lld cells (needs <= 2^32; use pcc_coords_expand)", cells);
   const int K = kernel_size * kernel_size * kernel_size;
@@ -795,14 +777,14 @@ __global__ void __launch_bounds__(256) k_frame_intake(const float* __restrict__ 
     const float2* r = reinterpret_cast<const float2*>(pc + i * 6);
     const float2 a = r[0], b = r[1], c = r[2];                       // x y | z r | g b
     const int x = (int)floorf(a.x), y = (int)floorf(a.y), z = (int)floorf(b.x);
-    const long long k = pack4(0, x, y, z);
+    const long long k = pcc_key_pack(0, x, y, z);
     keys[i] = k;
     feats[i] = make_float4(1.f, b.y, c.x, c.y);
     v[1] = min(v[1], x); v[2] = min(v[2], y); v[3] = min(v[3], z);
     v[5] = min(v[5], -x); v[6] = min(v[6], -y); v[7] = min(v[7], -z);
     if (i > 0) {
       const float* q = pc + (i - 1) * 6;
-      if (k <= pack4(0, (int)floorf(q[0]), (int)floorf(q[1]), (int)floorf(q[2]))) v[8] = 0;
+      if (k <= pcc_key_pack(0, (int)floorf(q[0]), (int)floorf(q[1]), (int)floorf(q[2]))) v[8] = 0;
     }
   }
   intake_block_reduce(v, part);
@@ -814,13 +796,13 @@ __global__ void __launch_bounds__(256) k_coords_intake_i32(const int4* __restric
   int v[9] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF, 1};
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
     const int4 c = c4[i];
-    const long long k = pack4(c.x, c.y, c.z, c.w);
+    const long long k = pcc_key_pack(c.x, c.y, c.z, c.w);
     keys[i] = k;
     v[0] = min(v[0], c.x); v[1] = min(v[1], c.y); v[2] = min(v[2], c.z); v[3] = min(v[3], c.w);
     v[4] = min(v[4], -c.x); v[5] = min(v[5], -c.y); v[6] = min(v[6], -c.z); v[7] = min(v[7], -c.w);
     if (i > 0) {
       const int4 q = c4[i - 1];
-      if (k <= pack4(q.x, q.y, q.z, q.w)) v[8] = 0;
+      if (k <= pcc_key_pack(q.x, q.y, q.z, q.w)) v[8] = 0;
     }
   }
   intake_block_reduce(v, part);
@@ -882,9 +864,9 @@ __global__ void __launch_bounds__(256) k_decode_finish(const long long* __restri
   if (i >= n) return;
   const long long k = keys[i];
   float v[6];
-  v[0] = (float)((int)((k >> 32) & 0xFFFF) - (int)PCC_BIAS);
-  v[1] = (float)((int)((k >> 16) & 0xFFFF) - (int)PCC_BIAS);
-  v[2] = (float)((int)(k & 0xFFFF) - (int)PCC_BIAS);
+  v[0] = (float)pcc_key_x(k);
+  v[1] = (float)pcc_key_y(k);
+  v[2] = (float)pcc_key_z(k);
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     float t = rintf(f[i * 3 + c] * 255.0f);

@@ -140,23 +140,24 @@ __global__ void __launch_bounds__(256) k_map_conv_z(PccGrid g, const int64_t* __
   int hits = 0;
   if (o < n_out) {
     const int64_t key = out_keys[rows ? rows[o] : o];
-    const int b = (int)(key >> 48);
-    const int x = (int)((key >> 32) & 0xFFFF) - (int)PCC_BIAS - g.lo[0] + (kxy % KS - H) * step;
-    const int y = (int)((key >> 16) & 0xFFFF) - (int)PCC_BIAS - g.lo[1] + (kxy / KS - H) * step;
-    const int z0 = (int)(key & 0xFFFF) - (int)PCC_BIAS - g.lo[2];
-    const int tm = (1 << g.ts_log2) - 1;
-    const int cx = x >> g.ts_log2, cy = y >> g.ts_log2;
-    const bool col_ok = (x | y) >= 0 && b < g.nbatch && !((x | y) & tm) && cx < g.dims[0] && cy < g.dims[1];
-    const long long cell0 = (((long long)b * g.dims[0] + cx) * g.dims[1] + cy) * g.dims[2];
+    const PccLattice& L = g.lat;
+    const int b = pcc_key_b(key);
+    const int x = pcc_key_x(key) - L.lo[0] + (kxy % KS - H) * step;
+    const int y = pcc_key_y(key) - L.lo[1] + (kxy / KS - H) * step;
+    const int z0 = pcc_key_z(key) - L.lo[2];
+    const int tm = (1 << L.ts_log2) - 1;
+    const int cx = x >> L.ts_log2, cy = y >> L.ts_log2;
+    const bool col_ok = (x | y) >= 0 && b < L.nbatch && !((x | y) & tm) && cx < L.dims[0] && cy < L.dims[1];
+    const long long cell0 = pcc_lat_cell(L, b, cx, cy, 0);
     long long wi = -1;
     unsigned long long w = 0;
     int rk = 0;
 #pragma unroll
     for (int iz = 0; iz < KS; ++iz) {
       const int z = z0 + (iz - H) * step;
-      const int cz = z >> g.ts_log2;
+      const int cz = z >> L.ts_log2;
       int idx = -1;
-      if (col_ok && z >= 0 && !(z & tm) && cz < g.dims[2]) {
+      if (col_ok && z >= 0 && !(z & tm) && cz < L.dims[2]) {
         const long long cell = cell0 + cz;
         if ((cell >> 6) != wi) { wi = cell >> 6; w = g.bits[wi]; rk = g.rank[wi]; }
         const int bit = (int)(cell & 63);
@@ -194,13 +195,13 @@ __global__ void k_morton(const int64_t* __restrict__ keys, int64_t n, int log2_s
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int64_t k = keys[i];
-  const uint32_t x = (uint32_t)((k >> 32) & 0xFFFF) >> log2_step;
-  const uint32_t y = (uint32_t)((k >> 16) & 0xFFFF) >> log2_step;
-  const uint32_t z = (uint32_t)(k & 0xFFFF) >> log2_step;
-  const uint64_t b = (uint64_t)(k >> 48) & 0xFFFF;
+  const uint32_t x = (uint32_t)((k >> PCC_KEY_X_SHIFT) & PCC_KEY_FIELD) >> log2_step;     // (biased fields: the order is what counts)
+  const uint32_t y = (uint32_t)((k >> PCC_KEY_Y_SHIFT) & PCC_KEY_FIELD) >> log2_step;
+  const uint32_t z = (uint32_t)(k & PCC_KEY_FIELD) >> log2_step;
+  const uint64_t b = (uint64_t)(k >> PCC_KEY_B_SHIFT) & PCC_KEY_FIELD;
   // batch index stays the major key (48 bits of interleaved coordinates below it); 16-bit batch ids would overflow
   // 64 bits together with 48 coordinate bits only for >= 2^16 batches, which the key format excludes
-  code[i] = (b << 48) | spread3(z) | (spread3(y) << 1) | (spread3(x) << 2);
+  code[i] = (b << PCC_KEY_B_SHIFT) | spread3(z) | (spread3(y) << 1) | (spread3(x) << 2);
 }
 
 // transposed: class id per output row (as a sortable 64-bit key)
@@ -210,9 +211,9 @@ __global__ void k_classify(const int64_t* __restrict__ out_keys, int64_t n_out, 
   if (o >= n_out) return;
   const int64_t k = out_keys[o];
   const int m = stride - 1;
-  const int rx = (int)((k >> 32) & 0xFFFF) >> log2_step & m;
-  const int ry = (int)((k >> 16) & 0xFFFF) >> log2_step & m;
-  const int rz = (int)(k & 0xFFFF) >> log2_step & m;
+  const int rx = (int)((k >> PCC_KEY_X_SHIFT) & PCC_KEY_FIELD) >> log2_step & m;     // (biased: 2^15 is a multiple of the step)
+  const int ry = (int)((k >> PCC_KEY_Y_SHIFT) & PCC_KEY_FIELD) >> log2_step & m;
+  const int rz = (int)(k & PCC_KEY_FIELD) >> log2_step & m;
   cls[o] = (uint64_t)(rx + stride * (ry + stride * rz));
 }
 
@@ -258,7 +259,6 @@ __global__ void __launch_bounds__(256) k_map_transposed(PccGrid grid, const int6
   count_pairs(hit, d_pairs);
 }
 
-static int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 static int max_class_k(int ks, int stride) {
   // offsets per axis congruent to a residue: max over residues
   int best = 0;
@@ -293,20 +293,10 @@ extern "C" int pcc_kernel_map_build(const int64_t* in_keys, int64_t n_in, const 
                                     const int32_t* h_grid, void* ws, size_t ws_bytes, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   PccGrid grid;
-  memset(&grid, 0, sizeof(grid));
-  if (grid_bits) {
-    PCC_REQUIRE(grid_rank && h_grid, "pcc_kernel_map_build: grid needs rank[] and its 8 host parameters");
-    grid.bits = (const unsigned long long*)grid_bits;
-    grid.rank = grid_rank;
-    for (int i = 0; i < 3; ++i) { grid.lo[i] = h_grid[i]; grid.dims[i] = h_grid[3 + i]; }
-    PCC_REQUIRE(h_grid[6] >= 1 && (h_grid[6] & (h_grid[6] - 1)) == 0, "pcc_kernel_map_build: grid pitch must be a power of two");
-    int l = 0; while ((1 << l) < h_grid[6]) ++l;
-    grid.ts_log2 = l;
-    grid.nbatch = h_grid[7];
-  }
+  PCC_TRY(pcc_grid_from_host(grid_bits, grid_rank, h_grid, "pcc_kernel_map_build", &grid));
   PCC_REQUIRE(hdr, "pcc_kernel_map_build: hdr is NULL");
   PCC_REQUIRE(kernel_size >= 1 && kernel_size <= 5, "pcc_kernel_map_build: kernel_size %d unsupported", kernel_size);
-  PCC_REQUIRE(step >= 1 && (step & (step - 1)) == 0, "pcc_kernel_map_build: step %d is not a power of two", step);
+  PCC_REQUIRE(pcc_is_pow2(step), "pcc_kernel_map_build: step %d is not a power of two", step);
   PCC_REQUIRE(n_in < (1ll << 31) && n_out < (1ll << 31), "pcc_kernel_map_build: too many rows");
   const int K = kernel_size * kernel_size * kernel_size;
   if (d_pairs) PCC_CHECK_HIP(hipMemsetAsync(d_pairs, 0, sizeof(int64_t), s));
@@ -341,7 +331,7 @@ extern "C" int pcc_kernel_map_build(const int64_t* in_keys, int64_t n_in, const 
       char* p = (char*)ws + bc_bytes;
       uint64_t* code = (uint64_t*)p;         p += pcc_align_up((size_t)n_out * 8);
       uint64_t* code_sorted = (uint64_t*)p;  p += pcc_align_up((size_t)n_out * 8) + 1024;
-      k_morton<<<(unsigned)pcc_cdiv(n_out, 256), 256, 0, s>>>(out_keys, n_out, ilog2(step), code);
+      k_morton<<<(unsigned)pcc_cdiv(n_out, 256), 256, 0, s>>>(out_keys, n_out, pcc_ilog2(step), code);
       PCC_LAUNCH_CHECK();
       PCC_TRY(pcc_sort_keys((const int64_t*)code, n_out, 0x7FFFFFFFFFFFFFFFull, (int64_t*)code_sorted, rows, p,
                             ws_bytes - (size_t)(p - (char*)ws), s));
@@ -392,7 +382,7 @@ extern "C" int pcc_kernel_map_build(const int64_t* in_keys, int64_t n_in, const 
   int* class_begin = (int*)p;           p += 1024;
   void* sort_ws = p;
   dim3 g1((unsigned)pcc_cdiv(n_out, 256));
-  k_classify<<<g1, 256, 0, s>>>(out_keys, n_out, ilog2(step), stride, cls);
+  k_classify<<<g1, 256, 0, s>>>(out_keys, n_out, pcc_ilog2(step), stride, cls);
   PCC_LAUNCH_CHECK();
   // stable counting sort by class == one radix pass; payload = output row of each position
   PCC_TRY(pcc_sort_keys((const int64_t*)cls, n_out, 0xFFull, (int64_t*)cls_sorted, rows, sort_ws,
@@ -413,28 +403,19 @@ extern "C" int pcc_kernel_map_build(const int64_t* in_keys, int64_t n_in, const 
 }
 
 // ---- grid index build ---------------------------------------------------------------------------------
-static int grid_rank(const unsigned long long* b, int64_t words, int32_t* rank, const int32_t* h, int tsl, int64_t* out_keys,
+static int grid_rank(const unsigned long long* b, int64_t words, int32_t* rank, const PccLattice& L, int64_t* out_keys,
                      int64_t* d_count, void* ws, size_t ws_bytes, hipStream_t s);
-__device__ inline long long grid_cell(const int64_t key, const int lo0, const int lo1, const int lo2, const int d0,
-                                      const int d1, const int d2, const int tsl) {
-  const int b = (int)(key >> 48);
-  const int cx = ((int)((key >> 32) & 0xFFFF) - (int)PCC_BIAS - lo0) >> tsl;
-  const int cy = ((int)((key >> 16) & 0xFFFF) - (int)PCC_BIAS - lo1) >> tsl;
-  const int cz = ((int)(key & 0xFFFF) - (int)PCC_BIAS - lo2) >> tsl;
-  return (((long long)b * d0 + cx) * d1 + cy) * d2 + cz;
-}
 
 // keys are sorted => cells ascending: the first row of each word ORs the bits of its (<= 64) followers; no atomics
-__global__ void k_grid_bits(const int64_t* __restrict__ keys, int64_t n, int lo0, int lo1, int lo2, int d0, int d1,
-                            int d2, int tsl, unsigned long long* __restrict__ bits) {
+__global__ void k_grid_bits(const int64_t* __restrict__ keys, int64_t n, PccLattice L, unsigned long long* __restrict__ bits) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const long long c = grid_cell(keys[i], lo0, lo1, lo2, d0, d1, d2, tsl);
+  const long long c = pcc_lat_cell_of_key(L, keys[i]);
   const long long w = c >> 6;
-  if (i > 0 && (grid_cell(keys[i - 1], lo0, lo1, lo2, d0, d1, d2, tsl) >> 6) == w) return;
+  if (i > 0 && (pcc_lat_cell_of_key(L, keys[i - 1]) >> 6) == w) return;
   unsigned long long acc = 1ull << (c & 63);
   for (int64_t t = i + 1; t < n && t < i + 64; ++t) {
-    const long long c2 = grid_cell(keys[t], lo0, lo1, lo2, d0, d1, d2, tsl);
+    const long long c2 = pcc_lat_cell_of_key(L, keys[t]);
     if ((c2 >> 6) != w) break;
     acc |= 1ull << (c2 & 63);
   }
@@ -446,11 +427,10 @@ __global__ void k_grid_popc(const unsigned long long* __restrict__ bits, int64_t
   if (i < words) cnt[i] = __popcll(bits[i]);
 }
 
+// (a size query returns no status: a header the decoder refuses has no words, and pcc_last_error() says why)
 extern "C" int64_t pcc_grid_words(const int32_t* h_grid) {
-  const long long cells = (long long)h_grid[7] * h_grid[3] * h_grid[4] * h_grid[5];
-  // an EVEN number of 64-bit words: hipMemsetAsync clears a size that is not a multiple of 16 bytes with two kernels (bulk + an
-  // 8-byte tail, each a launch: tools/probes/memset_probe.hip), and a step clears ~20 bitmaps
-  return ((cells + 63) / 64 + 1) / 2 * 2;
+  PccLattice L;
+  return pcc_lattice_from_host(h_grid, "pcc_grid_words", &L) == PCC_OK ? pcc_lattice_words(L) : 0;
 }
 
 extern "C" size_t pcc_grid_ws_bytes(int64_t words) { return pcc_scan_ws_bytes(words) + 256; }
@@ -458,10 +438,11 @@ extern "C" size_t pcc_grid_ws_bytes(int64_t words) { return pcc_scan_ws_bytes(wo
 extern "C" int pcc_grid_build(const int64_t* keys, int64_t n, const int32_t* h_grid, uint64_t* bits, int32_t* rank,
                               void* ws, size_t ws_bytes, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  PCC_REQUIRE(h_grid && bits && rank, "pcc_grid_build: NULL array");
-  const int64_t words = pcc_grid_words(h_grid);
+  PccLattice L;
+  PCC_TRY(pcc_lattice_from_host(h_grid, "pcc_grid_build", &L));
+  PCC_REQUIRE(bits && rank, "pcc_grid_build: NULL array");
+  const int64_t words = pcc_lattice_words(L);
   PCC_REQUIRE(words >= 1 && words < (1ll << 31), "pcc_grid_build: lattice too large (%lld words)", (long long)words);
-  PCC_REQUIRE(h_grid[6] >= 1 && (h_grid[6] & (h_grid[6] - 1)) == 0, "pcc_grid_build: pitch must be a power of two");
   if (ws_bytes < pcc_grid_ws_bytes(words)) {
     pcc_set_error("pcc_grid_build: workspace too small");
     return PCC_EWS;
@@ -469,11 +450,10 @@ extern "C" int pcc_grid_build(const int64_t* keys, int64_t n, const int32_t* h_g
   PCC_CHECK_HIP(hipMemsetAsync(bits, 0, (size_t)words * 8, s));
   if (n > 0) {
     PCC_REQUIRE(keys, "pcc_grid_build: keys is NULL");
-    k_grid_bits<<<(unsigned)pcc_cdiv(n, 256), 256, 0, s>>>(keys, n, h_grid[0], h_grid[1], h_grid[2], h_grid[3], h_grid[4],
-                                                          h_grid[5], ilog2(h_grid[6]), (unsigned long long*)bits);
+    k_grid_bits<<<(unsigned)pcc_cdiv(n, 256), 256, 0, s>>>(keys, n, L, (unsigned long long*)bits);
     PCC_LAUNCH_CHECK();
   }
-  return grid_rank((const unsigned long long*)bits, words, rank, h_grid, 0, nullptr, nullptr, ws, ws_bytes, s);
+  return grid_rank((const unsigned long long*)bits, words, rank, L, nullptr, nullptr, ws, ws_bytes, s);
 }
 
 // ---- strided coordinate set straight from the occupancy bitmap --------------------------------------------
@@ -482,13 +462,13 @@ extern "C" int pcc_grid_build(const int64_t* keys, int64_t n, const int32_t* h_g
 // set's grid index (bits + rank) falls out for free.  A handful of launches where the sort took ~35.
 // d_n (nullable): the row count lives on the device (a set whose size the host has not read yet); n is then the capacity
 // the grid was sized for, and threads past *d_n leave.
-__global__ void k_grid_bits_any(const int64_t* __restrict__ keys, int64_t n, const int64_t* __restrict__ d_n, int lo0, int lo1,
-                                int lo2, int d0, int d1, int d2, int tsl, unsigned long long* __restrict__ bits) {
+__global__ void k_grid_bits_any(const int64_t* __restrict__ keys, int64_t n, const int64_t* __restrict__ d_n, PccLattice L,
+                                unsigned long long* __restrict__ bits) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (d_n ? *d_n : n)) return;
-  const long long c = grid_cell(keys[i], lo0, lo1, lo2, d0, d1, d2, tsl);
+  const long long c = pcc_lat_cell_of_key(L, keys[i]);
   // neighbours in fine order often share the coarse cell (z pairs): only the first of a run issues the atomic
-  if (i > 0 && grid_cell(keys[i - 1], lo0, lo1, lo2, d0, d1, d2, tsl) == c) return;
+  if (i > 0 && pcc_lat_cell_of_key(L, keys[i - 1]) == c) return;
   // many fine rows per coarse cell (user-ordered rows, large pitch ratios): a cell already marked needs no atomic.  The
   // load goes to L2 (agent scope), so it sees the marks of other CUs; a stale 0 only costs a redundant atomicOr.
   const unsigned long long m = 1ull << (c & 63);
@@ -496,15 +476,10 @@ __global__ void k_grid_bits_any(const int64_t* __restrict__ keys, int64_t n, con
   atomicOr(&bits[c >> 6], m);
 }
 
-__global__ void k_grid_enumerate(const unsigned long long* __restrict__ bits, const int* __restrict__ rank,
-                                 int64_t words, int lo0, int lo1, int lo2, int d0, int d1, int d2, int tsl,
-                                 int64_t* __restrict__ keys, int64_t* __restrict__ count) {
-  const int64_t wi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (wi >= words) return;
-  unsigned long long w = bits[wi];
-  int r = rank[wi];
-  if (wi == words - 1) *count = (int64_t)r + __popcll(w);
-  if (!w) return;
+// read-out of one bitmap word: the canonical keys of the set bits of word wi (w != 0) go to keys[r], keys[r + 1], ...
+__device__ __forceinline__ void grid_word_keys(const PccLattice& L, int64_t wi, unsigned long long w, int r,
+                                               int64_t* __restrict__ keys) {
+  const int d0 = L.dims[0], d1 = L.dims[1], d2 = L.dims[2];
   // cell of the word's first bit, decomposed once (three 64-bit divisions per WORD, not per set bit); a bit's z may run past
   // the end of the z axis and carry into y / x / batch
   long long cell = wi * 64;
@@ -520,10 +495,18 @@ __global__ void k_grid_enumerate(const unsigned long long* __restrict__ bits, co
       cz -= d2;
       if (++cy == d1) { cy = 0; if (++cx == d0) { cx = 0; ++b; } }
     }
-    const int64_t x = (int64_t)(lo0 + (cx << tsl)) + PCC_BIAS, y = (int64_t)(lo1 + (cy << tsl)) + PCC_BIAS,
-                  z = (int64_t)(lo2 + (cz << tsl)) + PCC_BIAS;
-    keys[r++] = ((int64_t)b << 48) | (x << 32) | (y << 16) | z;
+    keys[r++] = pcc_lat_key(L, b, cx, cy, cz);
   }
+}
+
+__global__ void k_grid_enumerate(const unsigned long long* __restrict__ bits, const int* __restrict__ rank,
+                                 int64_t words, PccLattice L, int64_t* __restrict__ keys, int64_t* __restrict__ count) {
+  const int64_t wi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (wi >= words) return;
+  const unsigned long long w = bits[wi];
+  const int r = rank[wi];
+  if (wi == words - 1) *count = (int64_t)r + __popcll(w);
+  if (w) grid_word_keys(L, wi, w, r, keys);
 }
 
 // rank (+ read-out) of a bitmap in two launches (round 3; popcount kernel + scan (2 launches) + read-out kernel before, each
@@ -558,9 +541,8 @@ __global__ void __launch_bounds__(256) k_grid_rank_reduce(const unsigned long lo
 // builds about ten such grids (the hyper-prior's sets, the coarse end of the stride chain); ONE launch does all three.
 template <bool ENUM, bool SELF = false>
 __global__ void __launch_bounds__(256) k_grid_rank_apply(const unsigned long long* __restrict__ bits, int64_t words,
-                                                         const int* __restrict__ sums, int* __restrict__ rank, int lo0, int lo1,
-                                                         int lo2, int d0, int d1, int d2, int tsl, int64_t* __restrict__ keys,
-                                                         int64_t* __restrict__ count) {
+                                                         const int* __restrict__ sums, int* __restrict__ rank, PccLattice L,
+                                                         int64_t* __restrict__ keys, int64_t* __restrict__ count) {
   __shared__ int wsum[4];
   __shared__ int s_off;
   __shared__ int rk_s[ENUM ? GR_B : 1];
@@ -620,36 +602,19 @@ __global__ void __launch_bounds__(256) k_grid_rank_apply(const unsigned long lon
     const int li = t * 256 + (int)threadIdx.x;
     const int64_t wi = (int64_t)blockIdx.x * GR_B + li;
     if (wi >= words) break;
-    unsigned long long x = bits[wi];                                              // (L1 / L2 hit: this workgroup just read it)
-    if (!x) continue;
-    int r = rk_s[li];
-    long long cell = wi * 64;
-    const int z0 = (int)(cell % d2); cell /= d2;
-    const int y0 = (int)(cell % d1); cell /= d1;
-    const int x0 = (int)(cell % d0);
-    const int b0 = (int)(cell / d0);
-    while (x) {
-      const int bit = __ffsll((long long)x) - 1;
-      x &= x - 1;
-      int cz = z0 + bit, cy = y0, cx = x0, b = b0;
-      while (cz >= d2) {
-        cz -= d2;
-        if (++cy == d1) { cy = 0; if (++cx == d0) { cx = 0; ++b; } }
-      }
-      const int64_t X = (int64_t)(lo0 + (cx << tsl)) + PCC_BIAS, Y = (int64_t)(lo1 + (cy << tsl)) + PCC_BIAS,
-                    Z = (int64_t)(lo2 + (cz << tsl)) + PCC_BIAS;
-      keys[r++] = ((int64_t)b << 48) | (X << 32) | (Y << 16) | Z;
-    }
+    const unsigned long long x = bits[wi];                                        // (L1 / L2 hit: this workgroup just read it)
+    if (x) grid_word_keys(L, wi, x, rk_s[li], keys);
   }
 }
 
-// rank[] of a marked bitmap and, with out_keys, the canonical keys of its set bits + their count.  ws: pcc_grid_ws_bytes(words).
-static int grid_rank(const unsigned long long* b, int64_t words, int32_t* rank, const int32_t* h, int tsl, int64_t* out_keys,
+// rank[] of a marked bitmap and, with out_keys, the canonical keys of its set bits + their count (without out_keys nothing reads
+// the lattice L).  ws: pcc_grid_ws_bytes(words).
+static int grid_rank(const unsigned long long* b, int64_t words, int32_t* rank, const PccLattice& L, int64_t* out_keys,
                      int64_t* d_count, void* ws, size_t ws_bytes, hipStream_t s) {
   const int64_t nb = pcc_cdiv(words, GR_B);
   if (nb <= GR_SELF_NB && (((uintptr_t)b | (uintptr_t)rank) & 15) == 0) {      // small lattice: one launch
-    if (out_keys) k_grid_rank_apply<true, true><<<(unsigned)nb, 256, 0, s>>>(b, words, nullptr, rank, h[0], h[1], h[2], h[3], h[4], h[5], tsl, out_keys, d_count);
-    else k_grid_rank_apply<false, true><<<(unsigned)nb, 256, 0, s>>>(b, words, nullptr, rank, 0, 0, 0, 1, 1, 1, 0, nullptr, nullptr);
+    if (out_keys) k_grid_rank_apply<true, true><<<(unsigned)nb, 256, 0, s>>>(b, words, nullptr, rank, L, out_keys, d_count);
+    else k_grid_rank_apply<false, true><<<(unsigned)nb, 256, 0, s>>>(b, words, nullptr, rank, L, nullptr, nullptr);
     PCC_LAUNCH_CHECK();
     return PCC_OK;
   }
@@ -659,10 +624,10 @@ static int grid_rank(const unsigned long long* b, int64_t words, int32_t* rank, 
     // (the read-out inside the apply pass -- k_grid_rank_apply<true>, 8 words per thread -- measured 2x slower than the
     //  word-per-thread read-out kernel: 0.61 against 0.27 ms per step; the rank passes alone save the popcount kernel and
     //  its 200 MB round trip on the large lattices)
-    k_grid_rank_apply<false><<<(unsigned)nb, 256, 0, s>>>(b, words, sums, rank, 0, 0, 0, 1, 1, 1, 0, nullptr, nullptr);
+    k_grid_rank_apply<false><<<(unsigned)nb, 256, 0, s>>>(b, words, sums, rank, L, nullptr, nullptr);
     PCC_LAUNCH_CHECK();
     if (out_keys) {
-      k_grid_enumerate<<<(unsigned)pcc_cdiv(words, 256), 256, 0, s>>>(b, rank, words, h[0], h[1], h[2], h[3], h[4], h[5], tsl, out_keys, d_count);
+      k_grid_enumerate<<<(unsigned)pcc_cdiv(words, 256), 256, 0, s>>>(b, rank, words, L, out_keys, d_count);
       PCC_LAUNCH_CHECK();
     }
     return PCC_OK;
@@ -671,7 +636,7 @@ static int grid_rank(const unsigned long long* b, int64_t words, int32_t* rank, 
   PCC_LAUNCH_CHECK();
   PCC_TRY(pcc_scan_exclusive_i32(rank, rank, words, ws, ws_bytes, s));
   if (out_keys) {
-    k_grid_enumerate<<<(unsigned)pcc_cdiv(words, 256), 256, 0, s>>>(b, rank, words, h[0], h[1], h[2], h[3], h[4], h[5], tsl, out_keys, d_count);
+    k_grid_enumerate<<<(unsigned)pcc_cdiv(words, 256), 256, 0, s>>>(b, rank, words, L, out_keys, d_count);
     PCC_LAUNCH_CHECK();
   }
   return PCC_OK;
@@ -683,11 +648,12 @@ extern "C" int pcc_coords_stride_grid(const int64_t* keys, int64_t n, const int6
                                       int32_t* rank, int64_t* out_keys, int64_t* d_count, void* ws, size_t ws_bytes,
                                       void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  PCC_REQUIRE(h_grid && bits && rank && out_keys && d_count, "pcc_coords_stride_grid: NULL array");
-  const int64_t words = pcc_grid_words(h_grid);
+  PccLattice L;
+  PCC_TRY(pcc_lattice_from_host(h_grid, "pcc_coords_stride_grid", &L));
+  PCC_REQUIRE(bits && rank && out_keys && d_count, "pcc_coords_stride_grid: NULL array");
+  const int64_t words = pcc_lattice_words(L);
   PCC_REQUIRE(words >= 1 && words < (1ll << 31), "pcc_coords_stride_grid: lattice too large (%lld words)", (long long)words);
   const int P = h_grid[6];
-  PCC_REQUIRE(P >= 1 && (P & (P - 1)) == 0, "pcc_coords_stride_grid: pitch must be a power of two");
   PCC_REQUIRE(h_grid[0] % P == 0 && h_grid[1] % P == 0 && h_grid[2] % P == 0,
               "pcc_coords_stride_grid: lattice origin must be a multiple of the pitch %d", P);
   if (ws_bytes < pcc_grid_ws_bytes(words)) {
@@ -697,33 +663,31 @@ extern "C" int pcc_coords_stride_grid(const int64_t* keys, int64_t n, const int6
   PCC_CHECK_HIP(hipMemsetAsync(bits, 0, (size_t)words * 8, s));
   if (n > 0) {
     PCC_REQUIRE(keys, "pcc_coords_stride_grid: keys is NULL");
-    k_grid_bits_any<<<(unsigned)pcc_cdiv(n, 256), 256, 0, s>>>(keys, n, d_n, h_grid[0], h_grid[1], h_grid[2], h_grid[3],
-                                                              h_grid[4], h_grid[5], ilog2(P), (unsigned long long*)bits);
+    k_grid_bits_any<<<(unsigned)pcc_cdiv(n, 256), 256, 0, s>>>(keys, n, d_n, L, (unsigned long long*)bits);
     PCC_LAUNCH_CHECK();
   }
-  return grid_rank((const unsigned long long*)bits, words, rank, h_grid, ilog2(P), out_keys, d_count, ws, ws_bytes, s);
+  return grid_rank((const unsigned long long*)bits, words, rank, L, out_keys, d_count, ws, ws_bytes, s);
 }
 
 // ---- canonical order of user-ordered rows through the bitmap (ME.SparseTensor construction, a1) ------------------
-__global__ void k_grid_bits_each(const int64_t* __restrict__ keys, int64_t n, int lo0, int lo1, int lo2, int d0, int d1,
-                                 int d2, int tsl, unsigned long long* __restrict__ bits, int64_t* __restrict__ off_lattice) {
+__global__ void k_grid_bits_each(const int64_t* __restrict__ keys, int64_t n, PccLattice L, unsigned long long* __restrict__ bits,
+                                 int64_t* __restrict__ off_lattice) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int64_t key = keys[i];
-  const int x = (int)((key >> 32) & 0xFFFF) - (int)PCC_BIAS - lo0, y = (int)((key >> 16) & 0xFFFF) - (int)PCC_BIAS - lo1,
-            z = (int)(key & 0xFFFF) - (int)PCC_BIAS - lo2;
-  if ((x | y | z) & ((1 << tsl) - 1)) { *off_lattice = 1; return; }      // not a multiple of the pitch: caller falls back
-  const long long c = grid_cell(key, lo0, lo1, lo2, d0, d1, d2, tsl);
+  const int x = pcc_key_x(key) - L.lo[0], y = pcc_key_y(key) - L.lo[1], z = pcc_key_z(key) - L.lo[2];
+  if ((x | y | z) & ((1 << L.ts_log2) - 1)) { *off_lattice = 1; return; }      // not a multiple of the pitch: caller falls back
+  const long long c = pcc_lat_cell_of_key(L, key);
   atomicOr(&bits[c >> 6], 1ull << (c & 63));
 }
 
 // canonical position of every user row; the smallest user row of a cell wins (first duplicate kept)
-__global__ void k_grid_first_user(const int64_t* __restrict__ keys, int64_t n, int lo0, int lo1, int lo2, int d0, int d1,
-                                  int d2, int tsl, const unsigned long long* __restrict__ bits,
-                                  const int* __restrict__ rank, int* __restrict__ first_user) {
+__global__ void k_grid_first_user(const int64_t* __restrict__ keys, int64_t n, PccLattice L,
+                                  const unsigned long long* __restrict__ bits, const int* __restrict__ rank,
+                                  int* __restrict__ first_user) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const long long c = grid_cell(keys[i], lo0, lo1, lo2, d0, d1, d2, tsl);
+  const long long c = pcc_lat_cell_of_key(L, keys[i]);
   const unsigned long long w = bits[c >> 6];
   const int r = rank[c >> 6] + __popcll(w & ((1ull << (c & 63)) - 1ull));
   atomicMin(&first_user[r], (int)i);
@@ -736,25 +700,22 @@ extern "C" int pcc_keys_canonicalize_grid(const int64_t* keys, int64_t n, const 
                                           int32_t* rank, int64_t* out_keys, int32_t* first_user, int64_t* d_count,
                                           void* ws, size_t ws_bytes, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  PCC_REQUIRE(keys && h_grid && bits && rank && out_keys && first_user && d_count && n > 0 && n < (1ll << 31),
+  PccLattice L;
+  PCC_TRY(pcc_lattice_from_host(h_grid, "pcc_keys_canonicalize_grid", &L));
+  PCC_REQUIRE(keys && bits && rank && out_keys && first_user && d_count && n > 0 && n < (1ll << 31),
               "pcc_keys_canonicalize_grid: bad arguments");
-  const int64_t words = pcc_grid_words(h_grid);
+  const int64_t words = pcc_lattice_words(L);
   PCC_REQUIRE(words >= 1 && words < (1ll << 31), "pcc_keys_canonicalize_grid: lattice too large (%lld words)", (long long)words);
-  const int P = h_grid[6];
-  PCC_REQUIRE(P >= 1 && (P & (P - 1)) == 0, "pcc_keys_canonicalize_grid: pitch must be a power of two");
   if (ws_bytes < pcc_grid_ws_bytes(words)) { pcc_set_error("pcc_keys_canonicalize_grid: workspace too small"); return PCC_EWS; }
-  const int tsl = ilog2(P);
   unsigned long long* b = (unsigned long long*)bits;
   PCC_CHECK_HIP(hipMemsetAsync(bits, 0, (size_t)words * 8, s));
   PCC_CHECK_HIP(hipMemsetAsync(first_user, 0x7F, (size_t)n * 4, s));
   PCC_CHECK_HIP(hipMemsetAsync(d_count, 0, 2 * sizeof(int64_t), s));
   const unsigned g = (unsigned)pcc_cdiv(n, 256);
-  k_grid_bits_each<<<g, 256, 0, s>>>(keys, n, h_grid[0], h_grid[1], h_grid[2], h_grid[3], h_grid[4], h_grid[5], tsl, b,
-                                     d_count + 1);
+  k_grid_bits_each<<<g, 256, 0, s>>>(keys, n, L, b, d_count + 1);
   PCC_LAUNCH_CHECK();
-  PCC_TRY(grid_rank(b, words, rank, h_grid, tsl, out_keys, d_count, ws, ws_bytes, s));
-  k_grid_first_user<<<g, 256, 0, s>>>(keys, n, h_grid[0], h_grid[1], h_grid[2], h_grid[3], h_grid[4], h_grid[5], tsl, b,
-                                      rank, first_user);
+  PCC_TRY(grid_rank(b, words, rank, L, out_keys, d_count, ws, ws_bytes, s));
+  k_grid_first_user<<<g, 256, 0, s>>>(keys, n, L, b, rank, first_user);
   PCC_LAUNCH_CHECK();
   return PCC_OK;
 }
@@ -767,19 +728,17 @@ extern "C" int pcc_keys_canonicalize_grid(const int64_t* keys, int64_t n, const 
 //            descending, i.e. in ascending input row: exactly the pair-id order a stable sort by cell would give.
 //            One pass counts, a scan gives first[], a second pass writes pair ids i*K + k.
 template <int KS>
-__global__ void __launch_bounds__(256) k_expand_mark(const int64_t* __restrict__ keys, int64_t n, int ts_out, int lo0,
-                                                     int lo1, int lo2, int d0, int d1, int d2, int tsl,
+__global__ void __launch_bounds__(256) k_expand_mark(const int64_t* __restrict__ keys, int64_t n, int ts_out, PccLattice L,
                                                      unsigned long long* __restrict__ bits) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   constexpr int H = (KS & 1) ? (KS - 1) / 2 : 0;
   const int kxy = blockIdx.y;
   const int64_t key = keys[i];
-  const int b = (int)(key >> 48);
-  const int cx = ((int)((key >> 32) & 0xFFFF) - (int)PCC_BIAS - lo0 + (kxy % KS - H) * ts_out) >> tsl;
-  const int cy = ((int)((key >> 16) & 0xFFFF) - (int)PCC_BIAS - lo1 + (kxy / KS - H) * ts_out) >> tsl;
-  const int cz = ((int)(key & 0xFFFF) - (int)PCC_BIAS - lo2 - H * ts_out) >> tsl;
-  const long long cell = (((long long)b * d0 + cx) * d1 + cy) * d2 + cz;     // KS consecutive cells along z
+  const int cx = (pcc_key_x(key) - L.lo[0] + (kxy % KS - H) * ts_out) >> L.ts_log2;
+  const int cy = (pcc_key_y(key) - L.lo[1] + (kxy / KS - H) * ts_out) >> L.ts_log2;
+  const int cz = (pcc_key_z(key) - L.lo[2] - H * ts_out) >> L.ts_log2;
+  const long long cell = pcc_lat_cell(L, pcc_key_b(key), cx, cy, cz);        // KS consecutive cells along z
   const int bit = (int)(cell & 63);
   const unsigned long long m = (1ull << KS) - 1ull;
   atomicOr(&bits[cell >> 6], m << bit);
@@ -822,23 +781,21 @@ template <int KS>
 __device__ __forceinline__ void csr_columns(const ExpandCsrArgs& a, long long o, CsrCols<KS>& c) {
   constexpr int H = (KS & 1) ? (KS - 1) / 2 : 0;
   const int64_t key = a.out_keys[o];
-  c.b = (int)(key >> 48);
-  const int p[3] = {(int)((key >> 32) & 0xFFFF) - (int)PCC_BIAS - a.in.lo[0],
-                    (int)((key >> 16) & 0xFFFF) - (int)PCC_BIAS - a.in.lo[1],
-                    (int)(key & 0xFFFF) - (int)PCC_BIAS - a.in.lo[2]};
-  const int tm = (1 << a.in.ts_log2) - 1;
-  c.step = (1 << a.in.ts_log2) / a.ts_out;
-  if ((KS & 1) && a.ts_out * 2 == (1 << a.in.ts_log2)) {
+  c.b = pcc_key_b(key);
+  const int p[3] = {pcc_key_x(key) - a.in.lat.lo[0], pcc_key_y(key) - a.in.lat.lo[1], pcc_key_z(key) - a.in.lat.lo[2]};
+  const int tm = (1 << a.in.lat.ts_log2) - 1;
+  c.step = (1 << a.in.lat.ts_log2) / a.ts_out;
+  if ((KS & 1) && a.ts_out * 2 == (1 << a.in.lat.ts_log2)) {
     // up-sampling by 2 with an odd kernel (the generative convolutions of the codec): in units of the output pitch the
     // source cell cc holds offset index ia = P + H - 2 cc, so the compatible cells are the run
     // [ceil((P - H) / 2), floor((P + H) / 2)] cut to the lattice -- closed form instead of a scan over the KS offsets
-    const int tl = a.in.ts_log2 - 1;
+    const int tl = a.in.lat.ts_log2 - 1;
 #pragma unroll
     for (int ax = 0; ax < 3; ++ax) {
       const int P = p[ax] >> tl;                         // (p is a multiple of the output pitch)
       int c0 = (P - H + 1) >> 1, c1 = (P + H) >> 1;
       c0 = c0 < 0 ? 0 : c0;
-      c1 = c1 >= a.in.dims[ax] ? a.in.dims[ax] - 1 : c1;
+      c1 = c1 >= a.in.lat.dims[ax] ? a.in.lat.dims[ax] - 1 : c1;
       const int m = c1 - c0 + 1;
       c.set(ax, c0, P + H - 2 * c0, (m > 0 && !(p[ax] & (a.ts_out - 1))) ? m : 0);      // (rows off the output lattice have no source)
     }
@@ -850,8 +807,8 @@ __device__ __forceinline__ void csr_columns(const ExpandCsrArgs& a, long long o,
 #pragma unroll
     for (int ia = KS - 1; ia >= 0; --ia) {
       const int rel = p[ax] - (ia - H) * a.ts_out;
-      const int cc = rel >> a.in.ts_log2;
-      if (rel >= 0 && !(rel & tm) && cc < a.in.dims[ax]) {
+      const int cc = rel >> a.in.lat.ts_log2;
+      if (rel >= 0 && !(rel & tm) && cc < a.in.lat.dims[ax]) {
         if (m == 0) { c0 = cc; i0 = ia; }
         ++m;
       }
@@ -883,17 +840,17 @@ __global__ void __launch_bounds__(256) k_expand_csr_count(ExpandCsrArgs a) {
   CsrCols<KS> c;
   csr_columns<KS>(a, o, c);
   int total = 0;
-  if (c.b < a.in.nbatch && c.cnt(2) > 0) {
+  if (c.b < a.in.lat.nbatch && c.cnt(2) > 0) {
     // All (x, y) columns at once: a column's z field (<= 4 bits) is cut out of the 64-bit window that starts at the 32-bit
     // word holding its first cell -- it never straddles, so a column is ONE unconditional load (absent columns re-read cell 0
     // and are masked) and the <= 16 loads of a row are in flight together.  (The loop form waited for each column's word.)
     const unsigned* const bits32 = reinterpret_cast<const unsigned*>(a.in.bits);
-    const long long cells = (long long)a.in.nbatch * a.in.dims[0] * a.in.dims[1] * a.in.dims[2];
+    const long long cells = (long long)a.in.lat.nbatch * a.in.lat.dims[0] * a.in.lat.dims[1] * a.in.lat.dims[2];
     const long long last_dw = 2 * ((cells + 63) >> 6) - 2;       // last 32-bit word a 64-bit window may start at
     const unsigned fmask = (1u << c.cnt(2)) - 1u;
     // (cell of column (jx, jy) = cell of column (0, 0) + jx slabs + jy columns: one multiply chain per row, not per column)
-    const long long cell00 = (((long long)c.b * a.in.dims[0] + c.cell(0, 0)) * a.in.dims[1] + c.cell(1, 0)) * a.in.dims[2] + c.cell(2, 0);
-    const long long slab = (long long)a.in.dims[1] * a.in.dims[2];
+    const long long cell00 = pcc_lat_cell(a.in.lat, c.b, c.cell(0, 0), c.cell(1, 0), c.cell(2, 0));
+    const long long slab = (long long)a.in.lat.dims[1] * a.in.lat.dims[2];
     // two x slabs (2 M windows) per trip: 8 loads in flight at 7-wide lists, and half the registers of all 16 at once
     // (129 VGPRs = 3 waves per SIMD before; the pass is latency-bound, occupancy is what hides it)
     constexpr int G = M >= 4 ? 2 : M;
@@ -907,7 +864,7 @@ __global__ void __launch_bounds__(256) k_expand_csr_count(ExpandCsrArgs a) {
         for (int jy = 0; jy < M; ++jy) {
           const int jx = jx0 + gx;
           const bool ok = jx < c.cnt(0) && jy < c.cnt(1);
-          const long long cell = ok ? cell00 + jx * slab + (long long)jy * a.in.dims[2] : 0ll;
+          const long long cell = ok ? cell00 + jx * slab + (long long)jy * a.in.lat.dims[2] : 0ll;
           const long long dw = cell >> 5, dw2 = dw < last_dw ? dw : last_dw;
           sh[gx * M + jy] = ok ? (int)(cell & 31) + 32 * (int)(dw - dw2) : 64;
           const unsigned lo = bits32[dw2], hi = bits32[dw2 + 1];
@@ -926,19 +883,19 @@ template <int KS, typename F>
 __device__ __forceinline__ void csr_probe(const ExpandCsrArgs& a, long long o, F&& on_hit) {
   CsrCols<KS> c;
   csr_columns<KS>(a, o, c);
-  if (c.b >= a.in.nbatch || c.cnt(2) == 0) return;
+  if (c.b >= a.in.lat.nbatch || c.cnt(2) == 0) return;
   // The y columns of one x slab together (round 3): per column the aligned 64-bit word of its first cell, the 32 bits after it
   // (a field of <= 4 bits never reaches past them) and the word's rank -- three unconditional loads, absent columns re-read
   // cell 0 and are masked -- so a slab's <= 12-15 loads are in flight at once.  (The column-by-column loop waited for each
   // column's word, and for its rank behind a branch: 16 exposed L2 latencies per row of the 7-wide lists.)
   constexpr int MY = KS == 7 ? 4 : KS;                 // compatible offsets per axis: <= (KS + 1) / 2 at a pitch ratio of 2, KS at 1
   const unsigned* const bits32 = reinterpret_cast<const unsigned*>(a.in.bits);
-  const long long cells = (long long)a.in.nbatch * a.in.dims[0] * a.in.dims[1] * a.in.dims[2];
+  const long long cells = (long long)a.in.lat.nbatch * a.in.lat.dims[0] * a.in.lat.dims[1] * a.in.lat.dims[2];
   const long long last_w = ((cells + 63) >> 6) - 1;
   const unsigned fmask = (1u << c.cnt(2)) - 1u;
   const int kzs = a.zk ? 1 : KS * KS;
-  const long long cell00 = (((long long)c.b * a.in.dims[0] + c.cell(0, 0)) * a.in.dims[1] + c.cell(1, 0)) * a.in.dims[2] + c.cell(2, 0);
-  const long long slab = (long long)a.in.dims[1] * a.in.dims[2];
+  const long long cell00 = pcc_lat_cell(a.in.lat, c.b, c.cell(0, 0), c.cell(1, 0), c.cell(2, 0));
+  const long long slab = (long long)a.in.lat.dims[1] * a.in.lat.dims[2];
   for (int jx = 0; jx < c.cnt(0); ++jx) {
     unsigned long long w0[MY];
     unsigned nx[MY];
@@ -946,7 +903,7 @@ __device__ __forceinline__ void csr_probe(const ExpandCsrArgs& a, long long o, F
 #pragma unroll
     for (int jy = 0; jy < MY; ++jy) {
       const bool ok = jy < c.cnt(1);
-      const long long cell = ok ? cell00 + jx * slab + (long long)jy * a.in.dims[2] : 0ll;
+      const long long cell = ok ? cell00 + jx * slab + (long long)jy * a.in.lat.dims[2] : 0ll;
       const long long wi = cell >> 6;
       sh[jy] = ok ? (int)(cell & 63) : 64;
       w0[jy] = a.in.bits[wi];
@@ -1045,22 +1002,22 @@ extern "C" int pcc_coords_expand_grid(const int64_t* keys, int64_t n, int32_t ke
                                       uint64_t* bits, int32_t* rank, int64_t* out_keys, int64_t* d_count, void* ws,
                                       size_t ws_bytes, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  PCC_REQUIRE(keys && h_out && bits && rank && out_keys && d_count && n > 0, "pcc_coords_expand_grid: bad arguments");
+  PccLattice L;
+  PCC_TRY(pcc_lattice_from_host(h_out, "pcc_coords_expand_grid", &L));
+  PCC_REQUIRE(keys && bits && rank && out_keys && d_count && n > 0, "pcc_coords_expand_grid: bad arguments");
   PCC_REQUIRE(kernel_size == 2 || kernel_size == 3 || kernel_size == 5, "pcc_coords_expand_grid: kernel_size %d unsupported", kernel_size);
-  const int64_t words = pcc_grid_words(h_out);
+  const int64_t words = pcc_lattice_words(L);
   PCC_REQUIRE(words >= 1 && words < (1ll << 31), "pcc_coords_expand_grid: lattice too large (%lld words)", (long long)words);
   const int ts_out = h_out[6];
-  PCC_REQUIRE(ts_out >= 1 && (ts_out & (ts_out - 1)) == 0, "pcc_coords_expand_grid: pitch must be a power of two");
   if (ws_bytes < pcc_grid_ws_bytes(words)) { pcc_set_error("pcc_coords_expand_grid: workspace too small"); return PCC_EWS; }
   PCC_CHECK_HIP(hipMemsetAsync(bits, 0, (size_t)words * 8, s));
   const dim3 g((unsigned)pcc_cdiv(n, 256), (unsigned)(kernel_size * kernel_size));
   unsigned long long* b = (unsigned long long*)bits;
-  const int tsl = ilog2(ts_out);
-  if (kernel_size == 2) k_expand_mark<2><<<g, 256, 0, s>>>(keys, n, ts_out, h_out[0], h_out[1], h_out[2], h_out[3], h_out[4], h_out[5], tsl, b);
-  else if (kernel_size == 3) k_expand_mark<3><<<g, 256, 0, s>>>(keys, n, ts_out, h_out[0], h_out[1], h_out[2], h_out[3], h_out[4], h_out[5], tsl, b);
-  else k_expand_mark<5><<<g, 256, 0, s>>>(keys, n, ts_out, h_out[0], h_out[1], h_out[2], h_out[3], h_out[4], h_out[5], tsl, b);
+  if (kernel_size == 2) k_expand_mark<2><<<g, 256, 0, s>>>(keys, n, ts_out, L, b);
+  else if (kernel_size == 3) k_expand_mark<3><<<g, 256, 0, s>>>(keys, n, ts_out, L, b);
+  else k_expand_mark<5><<<g, 256, 0, s>>>(keys, n, ts_out, L, b);
   PCC_LAUNCH_CHECK();
-  return grid_rank(b, words, rank, h_out, tsl, out_keys, d_count, ws, ws_bytes, s);
+  return grid_rank(b, words, rank, L, out_keys, d_count, ws, ws_bytes, s);
 }
 
 extern "C" size_t pcc_expand_grid_csr_ws_bytes(int64_t n_out) { return pcc_scan_ws_bytes(n_out + 1) + 256; }
@@ -1089,18 +1046,17 @@ static int expand_grid_csr(const int64_t* out_keys, int64_t n_out, int32_t kerne
                            int64_t n_in, int32_t* first, int32_t* pair_ids, int64_t* d_total, void* ws, size_t ws_bytes, int zk,
                            void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  PCC_REQUIRE(out_keys && in_bits && in_rank && h_in && first && pair_ids && n_out > 0, "pcc_coords_expand_grid_csr: bad arguments");
+  ExpandCsrArgs a;
+  PCC_TRY(pcc_lattice_from_host(h_in, zk ? "pcc_coords_expand_grid_csr_zk" : "pcc_coords_expand_grid_csr", &a.in.lat));
+  PCC_REQUIRE(out_keys && in_bits && in_rank && first && pair_ids && n_out > 0, "pcc_coords_expand_grid_csr: bad arguments");
   PCC_REQUIRE(kernel_size == 2 || kernel_size == 3 || kernel_size == 5 || kernel_size == 7,
               "pcc_coords_expand_grid_csr: kernel_size %d unsupported", kernel_size);
   const int K = kernel_size * kernel_size * kernel_size;
   PCC_REQUIRE(n_in * K < (1ll << 31), "pcc_coords_expand_grid_csr: too many pairs");
   if (ws_bytes < pcc_expand_grid_csr_ws_bytes(n_out)) { pcc_set_error("pcc_coords_expand_grid_csr: workspace too small"); return PCC_EWS; }
-  ExpandCsrArgs a;
   a.out_keys = out_keys; a.n_out = n_out; a.ts_out = ts_out; a.K = K; a.first = first; a.pair_ids = pair_ids; a.zk = zk;
   a.d_total = (long long*)d_total;
   a.in.bits = (const unsigned long long*)in_bits; a.in.rank = in_rank;
-  for (int i = 0; i < 3; ++i) { a.in.lo[i] = h_in[i]; a.in.dims[i] = h_in[3 + i]; }
-  a.in.ts_log2 = ilog2(h_in[6]); a.in.nbatch = h_in[7];
   const unsigned g = (unsigned)pcc_cdiv(n_out, 256);
   // pitch ratio: >= 2 leaves at most (KS + 1) / 2 compatible offsets per axis; 1 (stride-1 generative transpose) all KS
   PCC_REQUIRE(ts_out >= 1 && h_in[6] >= ts_out && h_in[6] % ts_out == 0, "pcc_coords_expand_grid_csr: input pitch %d is not a multiple of the output pitch %d", h_in[6], ts_out);
@@ -1138,19 +1094,18 @@ extern "C" int pcc_coords_expand_grid_csr_slots(const int64_t* out_keys, int64_t
                                                 int32_t* first, int32_t* pair_ids, int32_t* wg_end, int64_t* d_total, int32_t zk,
                                                 void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  PCC_REQUIRE(out_keys && in_bits && in_rank && h_in && first && pair_ids && wg_end && n_out > 0, "pcc_coords_expand_grid_csr_slots: bad arguments");
+  ExpandCsrArgs a;
+  PCC_TRY(pcc_lattice_from_host(h_in, "pcc_coords_expand_grid_csr_slots", &a.in.lat));
+  PCC_REQUIRE(out_keys && in_bits && in_rank && first && pair_ids && wg_end && n_out > 0, "pcc_coords_expand_grid_csr_slots: bad arguments");
   PCC_REQUIRE(kernel_size == 5 || kernel_size == 7, "pcc_coords_expand_grid_csr_slots: kernel_size %d unsupported", kernel_size);
   const int K = kernel_size * kernel_size * kernel_size;
   PCC_REQUIRE(n_in * K < (1ll << 31), "pcc_coords_expand_grid_csr_slots: too many pairs");
   PCC_REQUIRE(pcc_expand_grid_csr_slot_elems(n_out, kernel_size) < (1ll << 31), "pcc_coords_expand_grid_csr_slots: too many rows for 32-bit list positions");
   PCC_REQUIRE(ts_out >= 1 && h_in[6] >= 2 * ts_out && h_in[6] % ts_out == 0,
               "pcc_coords_expand_grid_csr_slots: the input pitch %d must be at least twice the output pitch %d", h_in[6], ts_out);
-  ExpandCsrArgs a;
   a.out_keys = out_keys; a.n_out = n_out; a.ts_out = ts_out; a.K = K; a.first = first; a.pair_ids = pair_ids; a.zk = zk;
   a.d_total = (long long*)d_total;
   a.in.bits = (const unsigned long long*)in_bits; a.in.rank = in_rank;
-  for (int i = 0; i < 3; ++i) { a.in.lo[i] = h_in[i]; a.in.dims[i] = h_in[3 + i]; }
-  a.in.ts_log2 = ilog2(h_in[6]); a.in.nbatch = h_in[7];
   const unsigned g = (unsigned)pcc_cdiv(n_out, 256);
   const int slot = 256 * csr_slot_rows(kernel_size);
   if (d_total) PCC_CHECK_HIP(hipMemsetAsync(d_total, 0, sizeof(int64_t), s));

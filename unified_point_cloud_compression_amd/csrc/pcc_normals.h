@@ -22,13 +22,15 @@ struct NrmArgs {
 template <typename F, bool ROWS, typename Use>
 __device__ inline void nrm_field(const NrmArgs& a, long long b, int X, int Y, int Z, int dx, int dy, int zr, Use use) {
   if (a.g.bits) {
-    const int nx = X - (int)PCC_BIAS - a.g.lo[0] + dx, ny = Y - (int)PCC_BIAS - a.g.lo[1] + dy;
-    if (nx < 0 || ny < 0 || nx >= a.g.dims[0] || ny >= a.g.dims[1]) return;
-    const int z = Z - (int)PCC_BIAS - a.g.lo[2];
-    const int zlo = max(z - zr, 0), zhi = min(z + zr, a.g.dims[2] - 1);
-    if (zlo > zhi || b >= a.g.nbatch) return;                    // (a key of the set never is outside its own lattice)
+    const PccLattice& L = a.g.lat;
+    const int nx = X - (int)PCC_BIAS - L.lo[0] + dx, ny = Y - (int)PCC_BIAS - L.lo[1] + dy;
+    if (nx < 0 || ny < 0 || nx >= L.dims[0] || ny >= L.dims[1]) return;
+    const int z = Z - (int)PCC_BIAS - L.lo[2];
+    const int zlo = max(z - zr, 0), zhi = min(z + zr, L.dims[2] - 1);
+    if (zlo > zhi || b >= L.nbatch) return;                      // (a key of the set never is outside its own lattice)
     const int nz = zhi - zlo + 1;
-    const long long cell = ((b * a.g.dims[0] + nx) * a.g.dims[1] + ny) * (long long)a.g.dims[2] + zlo;
+    // (spelled out: through pcc_lat_cell the pcqm kernels come out with other instructions, tools/kernel_identity.py)
+    const long long cell = ((b * L.dims[0] + nx) * L.dims[1] + ny) * (long long)L.dims[2] + zlo;
     const long long wi = cell >> 6;
     const int sh = (int)(cell & 63);
     unsigned long long f64 = a.g.bits[wi] >> sh;
@@ -38,9 +40,9 @@ __device__ inline void nrm_field(const NrmArgs& a, long long b, int X, int Y, in
     return;
   }
   const int tx = X + dx, ty = Y + dy;
-  if (tx < 0 || ty < 0 || tx > 0xFFFF || ty > 0xFFFF) return;
-  const int zlo = max(Z - zr, 0), zhi = min(Z + zr, 0xFFFF);
-  const long long col = (b << 48) | ((long long)tx << 32) | ((long long)ty << 16);
+  if (tx < 0 || ty < 0 || tx > PCC_KEY_FIELD || ty > PCC_KEY_FIELD) return;
+  const int zlo = max(Z - zr, 0), zhi = min(Z + zr, PCC_KEY_FIELD);
+  const long long col = (b << PCC_KEY_B_SHIFT) | ((long long)tx << PCC_KEY_X_SHIFT) | ((long long)ty << PCC_KEY_Y_SHIFT);
   const long long klo = col | zlo, khi = col | zhi;
   int lo = 0, hi = a.n;                                          // first key >= klo
   while (lo < hi) {
@@ -53,7 +55,7 @@ __device__ inline void nrm_field(const NrmArgs& a, long long b, int X, int Y, in
   for (; lo < a.n; ++lo) {                                       // at most 2 * zr + 1 keys
     const long long k = a.keys[lo];
     if (k > khi) break;
-    f |= (F)1 << (int)((k & 0xFFFF) - zlo);
+    f |= (F)1 << (int)((k & PCC_KEY_FIELD) - zlo);
   }
   if (f) use(f, zlo - Z, row0);
 }
@@ -104,14 +106,11 @@ __device__ inline int nrm_column_half_height(int lim, int dx, int dy) {
 static inline int nrm_fill_args(NrmArgs& a, const char* who, const int64_t* keys, int64_t n, const uint64_t* grid_bits,
                                 const int32_t* grid_rank, const int32_t* h_grid, int32_t lim) {
   a = NrmArgs();
-  if (grid_bits) {
-    PCC_REQUIRE(h_grid, "%s: grid needs its 8 host parameters", who);
+  if (grid_bits) {                               // (rank[] is optional here: only the kernels that read rows need it)
+    PCC_TRY(pcc_lattice_from_host(h_grid, who, &a.g.lat));
     PCC_REQUIRE(h_grid[6] == 1, "%s: grid pitch %d, the set must be at pitch 1", who, h_grid[6]);
     a.g.bits = (const unsigned long long*)grid_bits;
     a.g.rank = grid_rank;
-    for (int i = 0; i < 3; ++i) { a.g.lo[i] = h_grid[i]; a.g.dims[i] = h_grid[3 + i]; }
-    a.g.ts_log2 = 0;
-    a.g.nbatch = h_grid[7];
   }
   a.keys = (const long long*)keys; a.n = (int)n; a.lim = lim;
   a.R = 0;

@@ -43,13 +43,14 @@ __device__ inline void nrm_add_column(NrmMoments& m, unsigned f, int base, int d
 // z field of column (dx, dy), half-height zr, around the point with key `key` (decoded: b, X, Y, Z biased fields)
 __device__ inline void nrm_column(const NrmArgs& a, NrmMoments& m, long long b, int X, int Y, int Z, int dx, int dy, int zr) {
   if (a.g.bits) {
-    const int nx = X - (int)PCC_BIAS - a.g.lo[0] + dx, ny = Y - (int)PCC_BIAS - a.g.lo[1] + dy;
-    if (nx < 0 || ny < 0 || nx >= a.g.dims[0] || ny >= a.g.dims[1]) return;
-    const int z = Z - (int)PCC_BIAS - a.g.lo[2];
-    const int zlo = max(z - zr, 0), zhi = min(z + zr, a.g.dims[2] - 1);
-    if (zlo > zhi || b >= a.g.nbatch) return;                    // (a key of the set never is outside its own lattice)
+    const PccLattice& L = a.g.lat;
+    const int nx = X - (int)PCC_BIAS - L.lo[0] + dx, ny = Y - (int)PCC_BIAS - L.lo[1] + dy;
+    if (nx < 0 || ny < 0 || nx >= L.dims[0] || ny >= L.dims[1]) return;
+    const int z = Z - (int)PCC_BIAS - L.lo[2];
+    const int zlo = max(z - zr, 0), zhi = min(z + zr, L.dims[2] - 1);
+    if (zlo > zhi || b >= L.nbatch) return;                      // (a key of the set never is outside its own lattice)
     const int nz = zhi - zlo + 1;
-    const long long cell = ((b * a.g.dims[0] + nx) * a.g.dims[1] + ny) * (long long)a.g.dims[2] + zlo;
+    const long long cell = pcc_lat_cell(L, b, nx, ny, zlo);
     const long long wi = cell >> 6;
     const int sh = (int)(cell & 63);
     unsigned long long f64 = a.g.bits[wi] >> sh;
@@ -59,9 +60,9 @@ __device__ inline void nrm_column(const NrmArgs& a, NrmMoments& m, long long b, 
     return;
   }
   const int tx = X + dx, ty = Y + dy;
-  if (tx < 0 || ty < 0 || tx > 0xFFFF || ty > 0xFFFF) return;
-  const int zlo = max(Z - zr, 0), zhi = min(Z + zr, 0xFFFF);
-  const long long col = (b << 48) | ((long long)tx << 32) | ((long long)ty << 16);
+  if (tx < 0 || ty < 0 || tx > PCC_KEY_FIELD || ty > PCC_KEY_FIELD) return;
+  const int zlo = max(Z - zr, 0), zhi = min(Z + zr, PCC_KEY_FIELD);
+  const long long col = (b << PCC_KEY_B_SHIFT) | ((long long)tx << PCC_KEY_X_SHIFT) | ((long long)ty << PCC_KEY_Y_SHIFT);
   const long long klo = col | zlo, khi = col | zhi;
   int lo = 0, hi = a.n;                                          // first key >= klo
   while (lo < hi) {
@@ -72,7 +73,7 @@ __device__ inline void nrm_column(const NrmArgs& a, NrmMoments& m, long long b, 
   for (; lo < a.n; ++lo) {                                       // at most 2 * zr + 1 <= 15 keys
     const long long k = a.keys[lo];
     if (k > khi) break;
-    f |= 1u << (int)((k & 0xFFFF) - zlo);
+    f |= 1u << (int)((k & PCC_KEY_FIELD) - zlo);
   }
   if (f) nrm_add_column(m, f, zlo - Z, dx, dy);
 }
@@ -90,8 +91,8 @@ __global__ void __launch_bounds__(256) k_normals(NrmArgs a, float* __restrict__ 
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.n) return;
   const long long key = a.keys[i];
-  const long long b = key >> 48;
-  const int X = (int)((key >> 32) & 0xFFFF), Y = (int)((key >> 16) & 0xFFFF), Z = (int)(key & 0xFFFF);
+  const long long b = key >> PCC_KEY_B_SHIFT;
+  const int X = (int)((key >> PCC_KEY_X_SHIFT) & PCC_KEY_FIELD), Y = (int)((key >> PCC_KEY_Y_SHIFT) & PCC_KEY_FIELD), Z = (int)(key & PCC_KEY_FIELD);
   NrmMoments m = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (int dy = -a.R; dy <= a.R; ++dy)
     for (int dx = -a.R; dx <= a.R; ++dx) {

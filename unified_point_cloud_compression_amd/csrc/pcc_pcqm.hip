@@ -43,8 +43,8 @@ __global__ void __launch_bounds__(256) k_curvature(NrmArgs a, double* __restrict
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.n) return;
   const long long key = a.keys[i];
-  const long long b = key >> 48;
-  const int X = (int)((key >> 32) & 0xFFFF), Y = (int)((key >> 16) & 0xFFFF), Z = (int)(key & 0xFFFF);
+  const long long b = key >> PCC_KEY_B_SHIFT;
+  const int X = (int)((key >> PCC_KEY_X_SHIFT) & PCC_KEY_FIELD), Y = (int)((key >> PCC_KEY_Y_SHIFT) & PCC_KEY_FIELD), Z = (int)(key & PCC_KEY_FIELD);
   const int side = 2 * a.R + 1;
 
   long long cnt = 0, sx = 0, sy = 0, sz = 0, sxx = 0, syy = 0, szz = 0, sxy = 0, sxz = 0, syz = 0;
@@ -181,8 +181,8 @@ __global__ void __launch_bounds__(256) k_pcqm_features(NrmArgs a, double inv_two
   const long long i = (long long)blockIdx.x * (blockDim.x / PCC_WAVE) + threadIdx.x / PCC_WAVE;
   if (i >= a.n) return;                           // (whole waves leave; no barrier follows)
   const long long key = a.keys[i];
-  const long long b = key >> 48;
-  const int X = (int)((key >> 32) & 0xFFFF), Y = (int)((key >> 16) & 0xFFFF), Z = (int)(key & 0xFFFF);
+  const long long b = key >> PCC_KEY_B_SHIFT;
+  const int X = (int)((key >> PCC_KEY_X_SHIFT) & PCC_KEY_FIELD), Y = (int)((key >> PCC_KEY_Y_SHIFT) & PCC_KEY_FIELD), Z = (int)(key & PCC_KEY_FIELD);
   const int side = 2 * a.R + 1;
   const double* own = table + i * PCQM_COLS;
   const double k0 = own[0], l0 = own[2], a0 = own[4], b0 = own[6], c0 = own[8];

@@ -60,9 +60,7 @@ __host__ __device__ inline void raht_inv(long long a, long long b, long long lo,
 // rows of the eight children (-1: absent); returns the occupancy byte
 __device__ inline int raht_kids(const RahtLevel& L, int i, int kid[8]) {
   const int64_t key = L.keys[i];
-  const int x = (int)((key >> 32) & 0xFFFF) - (int)PCC_BIAS;
-  const int y = (int)((key >> 16) & 0xFFFF) - (int)PCC_BIAS;
-  const int z = (int)(key & 0xFFFF) - (int)PCC_BIAS;
+  const int x = pcc_key_x(key), y = pcc_key_y(key), z = pcc_key_z(key);
   const int cp = L.pitch >> 1;
   int mask = 0;
 #pragma unroll
@@ -70,8 +68,7 @@ __device__ inline int raht_kids(const RahtLevel& L, int i, int kid[8]) {
     const int cx = x + ((j >> 2) & 1) * cp, cy = y + ((j >> 1) & 1) * cp, cz = z + (j & 1) * cp;
     int r = -1;
     if ((cx | cy | cz) >= 0 && cx < (int)PCC_BIAS && cy < (int)PCC_BIAS && cz < (int)PCC_BIAS) {
-      const int64_t q = ((int64_t)(cx + (int)PCC_BIAS) << 32) | ((int64_t)(cy + (int)PCC_BIAS) << 16) | (int64_t)(cz + (int)PCC_BIAS);
-      r = pcc_lookup(L.cg, L.ckeys, L.nc, q);
+      r = pcc_lookup(L.cg, L.ckeys, L.nc, pcc_key_pack(0, cx, cy, cz));
       if (r >= L.nc) r = -1;
     }
     kid[j] = r;
@@ -325,17 +322,16 @@ static bool raht_level(const char* what, const int64_t* keys, int64_t n, int32_t
     pcc_set_error("%s: bad arguments (a level of n >= 1 nodes with n .. 2^26 - 1 children)", what);
     return false;
   }
-  if (!(pitch >= 2 && pitch <= (1 << 15) && (pitch & (pitch - 1)) == 0)) {
+  if (!(pitch >= 2 && pitch <= (1 << 15) && pcc_is_pow2(pitch))) {
     pcc_set_error("%s: pitch %d is not a power of two in [2, 2^15]", what, pitch);
     return false;
   }
-  if (child_bits && child_rank && h_child && h_child[6] != pitch / 2) {
+  if (pcc_grid_from_host(child_bits, child_rank, h_child, what, &L->cg) != PCC_OK) return false;   // bits == NULL: binary search
+  if (L->cg.bits && h_child[6] != pitch / 2) {
     pcc_set_error("%s: the child grid has another pitch", what);
     return false;
   }
   L->keys = keys; L->n = (int)n; L->pitch = pitch; L->ckeys = child_keys; L->nc = (int)n_child;
-  if (child_bits && child_rank && h_child) L->cg = grid_from_host(child_bits, child_rank, h_child);
-  else { PccGrid g{}; L->cg = g; }            // bits == nullptr: binary search over the keys
   return true;
 }
 

@@ -114,9 +114,9 @@ __device__ __forceinline__ void vox_butterfly(double (&acc)[NCH]) {
 template <int NCH>
 __device__ __forceinline__ void vox_write(const VoxArgs& A, int r, int count, const double (&acc)[NCH]) {
   const long long key = A.ukeys[r];
-  A.index[r * 3LL + 0] = (int)((key >> 32) & 0xFFFF) - (int)PCC_BIAS;
-  A.index[r * 3LL + 1] = (int)((key >> 16) & 0xFFFF) - (int)PCC_BIAS;
-  A.index[r * 3LL + 2] = (int)(key & 0xFFFF) - (int)PCC_BIAS;
+  A.index[r * 3LL + 0] = pcc_key_x(key);
+  A.index[r * 3LL + 1] = pcc_key_y(key);
+  A.index[r * 3LL + 2] = pcc_key_z(key);
   A.counts[r] = count;
   const double cnt = (double)count;
 #pragma unroll
