@@ -690,6 +690,49 @@ int pcc_raht_hist(const int32_t* sym, const int32_t* grp, int64_t n_sym, int32_t
 int pcc_raht_finish(const int32_t* values, int64_t n, int32_t channels, int32_t colour, uint8_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 8f-3d lossless attribute coder over the same level sets: the levels, stages, slot pairs, rows and
+ *       groups of 8f-3c (pcc_raht_mask / pcc_raht_weights / pcc_raht_index / pcc_raht_hist and pcc_geom_child_offsets serve both)
+ *       with a reversible arithmetic.  Values are plain int32 levels [rows, channels], 1 <= channels <= 8: 0..255, and with
+ *       colour != 0 (channels == 3) YCoCg-R: Co = R - B, t = B + (Co >> 1), Cg = G - t, Y = t + (Cg >> 1), Co and Cg in
+ *       -255..255.  Butterfly of present siblings (w1, x1), (w2, x2): H = x2 - x1, L = x1 + floor(w2 * H / (w1 + w2)); inverse
+ *       x1 = L - floor(w2 * H / (w1 + w2)), x2 = H + x1.  Prediction of a child (dx, dy, dz): over the present cells node + d * b
+ *       of the node's own level, d = 2 * (dx, dy, dz) - 1, b in {0, 1}^3, weights 27 / 9 / 3 / 1 by the non-zero components of b,
+ *       floor((sum wt * value + (sum wt >> 1)) / sum wt); the children's predictions go through the same lifting and give Hp per
+ *       butterfly; the coded symbol is H - Hp.  A level is given as in 8f-3c; bits / rank / h_grid are the NODE level's own grid
+ *       index (pitch h_grid[6] == pitch) or three NULLs: binary search over keys.  Same bits either way.
+ * pcc_lift_pair / pcc_lift_predict  HOST: the kernels' own arithmetic for the CPU tests.  pair: h_out[4] = L, H and the
+ *                      inverse's x1, x2 (weights >= 1, below 2^27 in total; |x| <= 1023).  predict: *h_out = the prediction from
+ *                      h_values[8] (cell b = bx<<2 | by<<1 | bz, |value| <= 1023) and the presence mask 1..255.
+ * pcc_lift_prepare     uint8 attrs [n, channels] (row perm[i] of the caller's order, perm NULL: row i) -> values.
+ * pcc_lift_forward     w[i], v[i, :] (the node's rounded mean) and H of the node's butterflies at its rows.
+ * pcc_lift_residual    rows of the level -= Hp, from the level's own values v [n, channels] (all levels' v and the H rows exist
+ *                      after the forward pass; the levels are independent here).
+ * pcc_lift_inverse     child_v of every child from v and the rows' symbols: H = symbol + Hp (predict != 0) or symbol.  A symbol
+ *                      is clamped to +-1023 and every reconstructed value into its channel's range; a clamp sets bit 0 of
+ *                      *d_flag (device int32 zeroed by the caller).
+ * pcc_lift_finish      values -> uint8 (inverse YCoCg-R for colour != 0); a level outside 0..255 is clamped and sets *d_flag.
+ * ---------------------------------------------------------------------------------------- */
+int pcc_lift_pair(uint32_t w1, uint32_t w2, int32_t x1, int32_t x2, int64_t* h_out /*[4]*/);
+int pcc_lift_predict(const int32_t* h_values /*[8]*/, int32_t mask, int32_t* h_out);
+int pcc_lift_prepare(const uint8_t* attrs, const int64_t* perm /*nullable*/, int64_t n, int32_t channels, int32_t colour,
+                     int32_t* values, void* stream);
+int pcc_lift_forward(const int64_t* keys, int64_t n, int32_t pitch, const int64_t* child_keys, int64_t n_child,
+                     const uint64_t* child_bits, const int32_t* child_rank, const int32_t* h_child, const int32_t* off,
+                     const int32_t* child_w /*nullable*/, const int32_t* child_v, int32_t channels, int32_t* w, int32_t* v,
+                     int32_t* coef, int64_t row_base, int64_t rows_total, void* stream);
+int pcc_lift_residual(const int64_t* keys, int64_t n, int32_t pitch, const uint64_t* bits, const int32_t* rank,
+                      const int32_t* h_grid, const int64_t* child_keys, int64_t n_child, const uint64_t* child_bits,
+                      const int32_t* child_rank, const int32_t* h_child, const int32_t* off, const int32_t* child_w /*nullable*/,
+                      const int32_t* v, int32_t channels, int32_t* coef, int64_t row_base, int64_t rows_total, void* stream);
+int pcc_lift_inverse(const int64_t* keys, int64_t n, int32_t pitch, const uint64_t* bits, const int32_t* rank,
+                     const int32_t* h_grid, const int64_t* child_keys, int64_t n_child, const uint64_t* child_bits,
+                     const int32_t* child_rank, const int32_t* h_child, const int32_t* off, const int32_t* child_w /*nullable*/,
+                     const int32_t* v, int32_t channels, int32_t colour, int32_t predict, const int32_t* coef, int64_t row_base,
+                     int64_t rows_total, int32_t* child_v, int32_t* d_flag, void* stream);
+int pcc_lift_finish(const int32_t* values, int64_t n, int32_t channels, int32_t colour, uint8_t* out, int32_t* d_flag,
+                    void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * 8f-4  nearest-neighbour association of the distortion report (replaces the two Open3D KD-trees and the per-point
  *       Python loop of PointCloudMetric.__init__, metrics/metric.py:36-43).  Exact, integer coordinates.
  *       a_xyz [n_a,3] int32 queries (any order; canonical order is fastest); b_xyz [n_b,3] int32 SORTED BY x ascending

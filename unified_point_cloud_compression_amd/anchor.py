@@ -8,6 +8,11 @@ their mean colour (`voxelize.voxel_grid`); the lossless octree (`geometry.encode
 (`attributes.encode_attributes`).
 
     container = u8 0xC1 | f64 position_scale | u32 len_geometry | geometry stream | attribute stream
+
+`compress_lossless` / `decompress_lossless` return a voxel cloud bit for bit: the same octree with the
+lossless colour coder (`attributes.encode_attributes_lossless`), no scaling and no merging.
+
+    container = u8 0xC2 | u32 len_geometry | geometry stream | attribute stream
 """
 import math
 import struct
@@ -16,7 +21,7 @@ import torch
 
 from . import lib as L
 from . import sparse as S
-from .attributes import decode_attributes, encode_attributes
+from .attributes import decode_attributes, decode_attributes_lossless, encode_attributes, encode_attributes_lossless
 from .geometry import decode_geometry, encode_geometry
 from .voxelize import voxel_grid
 
@@ -82,3 +87,55 @@ def decompress_anchor(data, device):
     xyz = cs.coords()[:cs.n, 1:].to(torch.float64) / torch.tensor(scale, dtype=torch.float64, device=dev)
     rgb = levels.to(torch.float64) / torch.tensor(255.0, dtype=torch.float64, device=dev)
     return torch.cat([xyz, rgb], dim=1).to(torch.float32)
+
+
+# ---- the lossless codec --------------------------------------------------------------------------------------------------
+LOSSLESS_MAGIC = 0xC2
+LOSSLESS_HEADER = struct.Struct("<BI")
+
+
+def parse_lossless_container(data):
+    """(geometry stream, attribute stream); PccError on a bad magic byte or length."""
+    if len(data) < LOSSLESS_HEADER.size:
+        raise L.PccError("lossless stream truncated inside the header")
+    magic, len_g = LOSSLESS_HEADER.unpack_from(data, 0)
+    if magic != LOSSLESS_MAGIC:
+        raise L.PccError(f"lossless stream: magic byte {magic:#x}, this build reads {LOSSLESS_MAGIC:#x}")
+    if LOSSLESS_HEADER.size + len_g > len(data):
+        raise L.PccError("lossless stream truncated inside the geometry stream")
+    return bytes(data[LOSSLESS_HEADER.size:LOSSLESS_HEADER.size + len_g]), bytes(data[LOSSLESS_HEADER.size + len_g:])
+
+
+@torch.no_grad()
+def compress_lossless(cloud):
+    """[N, 6] GPU cloud of distinct voxels (integer xyz, rgb in [0, 1]: colours become round(255 c)) -> bytes from which
+    `decompress_lossless` returns the same voxels with the same levels.  Non-integer coordinates and repeated voxels raise
+    PccError: voxelise first (`voxelize.voxel_grid`)."""
+    what = "compress_lossless"
+    if not torch.is_tensor(cloud) or cloud.dim() != 2 or cloud.shape[1] != 6 or cloud.shape[0] == 0:
+        raise L.PccError(f"{what}: a non-empty [N, 6] cloud (xyz, rgb in [0, 1]) is required")
+    if not cloud.is_cuda:
+        raise L.PccError(f"{what} operates on GPU tensors only (no CPU fallback)")
+    xyz = cloud[:, :3]
+    if xyz.dtype.is_floating_point and not bool((xyz == torch.floor(xyz)).all()):
+        raise L.PccError(f"{what}: coordinates are not integers; voxelise the cloud first (voxelize.voxel_grid)")
+    c4 = torch.cat([torch.zeros((cloud.shape[0], 1), dtype=torch.int32, device=cloud.device), xyz.to(torch.int32)], dim=1).contiguous()
+    cs, perm, keep = S.coordset_from_coords(c4, 1)
+    if keep is not None:
+        raise L.PccError(f"{what}: {cloud.shape[0] - cs.n} rows repeat a voxel; merge them first (voxelize.voxel_grid)")
+    levels = torch.round(cloud[:, 3:6].to(torch.float64) * 255.0).clamp_(0, 255).to(torch.uint8)
+    levels = (levels if perm is None else levels[perm]).contiguous()
+    geometry = encode_geometry(cs)
+    attributes = encode_attributes_lossless(cs, attrs=levels)
+    return LOSSLESS_HEADER.pack(LOSSLESS_MAGIC, len(geometry)) + geometry + attributes
+
+
+@torch.no_grad()
+def decompress_lossless(data, device):
+    """bytes -> [n, 6] float32 on `device` in canonical order: the exact coordinates, colours level / 255 (round(255 c) of
+    them gives the levels back)."""
+    geometry, attributes = parse_lossless_container(data)
+    cs = decode_geometry(geometry, device, as_set=True)
+    levels = decode_attributes_lossless(attributes, cs)
+    rgb = levels.to(torch.float64) / torch.tensor(255.0, dtype=torch.float64, device=cs.device)
+    return torch.cat([cs.coords()[:cs.n, 1:].to(torch.float64), rgb], dim=1).to(torch.float32)

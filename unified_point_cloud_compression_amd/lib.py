@@ -166,6 +166,14 @@ SIGNATURES = {
     "pcc_raht_index": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p, _i64, _i64, _p]),
     "pcc_raht_hist": (C.c_int, [_p, _p, _i64, _i32, _p, _p]),
     "pcc_raht_finish": (C.c_int, [_p, _i64, _i32, _i32, _p, _p]),
+    "pcc_lift_pair": (C.c_int, [C.c_uint32, C.c_uint32, _i32, _i32, C.POINTER(_i64)]),
+    "pcc_lift_predict": (C.c_int, [C.POINTER(_i32), _i32, C.POINTER(_i32)]),
+    "pcc_lift_prepare": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p]),
+    "pcc_lift_forward": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _i64, _i64, _p]),
+    "pcc_lift_residual": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _i32, _p, _i64, _i64, _p]),
+    "pcc_lift_inverse": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _i64, _p, _p,
+                                   _p]),
+    "pcc_lift_finish": (C.c_int, [_p, _i64, _i32, _i32, _p, _p, _p]),
     "pcc_conv_pairs_supported": (C.c_int, [_i32, _i32, _i32]),
     "pcc_pair_plan_ws_bytes": (_sz, [_i64, _i32]),
     "pcc_pair_plan_rank": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _sz, _p]),
