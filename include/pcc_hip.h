@@ -349,6 +349,14 @@ int pcc_gdn_pack(const float* beta_raw, const float* gamma_raw, int32_t c, float
                  float* packed, int64_t packed_cap, float* beta_eff, void* stream);
 int pcc_gdn_fwd(const float* x, int64_t n, int32_t c, const float* packed, const float* beta_eff,
                 int32_t inverse, float* out, int32_t arith, void* stream);
+/* {kernel, row tile, column tile, inverse} of the most recent pcc_gdn_fwd that launched (a call with n <= 0 launches nothing and
+ * leaves the record).  GDN launches are not event-timed, so pcc_prof_sequence never lists them; this query costs a few integer
+ * stores per call and lets a test READ the regime a call reached.  Process state, like the profiling record; not thread-safe. */
+#define PCC_GDN_KERNEL_NONE 0      /* no pcc_gdn_fwd has launched yet */
+#define PCC_GDN_KERNEL_CONV_F32 1  /* k_conv_mfma in GDN mode: fp32-input MFMA (c = 8, 16; PCC_ARITH_F32; PCC_MFMA_BUF=0) */
+#define PCC_GDN_KERNEL_CONV_BF 2   /* k_conv_mfma_bf in GDN mode: six bf16 terms over planes k_feat_split wrote */
+#define PCC_GDN_KERNEL_FUSED 3     /* k_gdn_bf: six bf16 terms, the split folded into the staging */
+int pcc_gdn_last_launch(int32_t* h_rec /* [4] */);
 
 /* ------------------------------------------------------------------------------------------
  * Frame intake and hand-over of UnifiedModel.compress / decompress (model/model.py:141-161, 240-250), one launch each.

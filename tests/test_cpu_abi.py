@@ -40,6 +40,20 @@ def test_size_queries_are_pure_host_functions():
     assert L.pcc_gdn_packed_elems(128) == 128 * 128 * 5 // 2 and L.pcc_gdn_packed_elems(24) == 0
 
 
+def test_gdn_refuses_unsupported_channel_counts_with_the_true_rule():
+    """`MinkowskiGDN._pack` sizes its buffers with the host query `pcc_gdn_packed_elems`: 4 and 24 channels are refused before
+    anything is allocated, with the rule the library states (8, 16 or a multiple of 32 -- not 4)."""
+    from unified_point_cloud_compression_amd import lib
+    from unified_point_cloud_compression_amd.model.blocks import MinkowskiGDN
+    for c in (4, 24):
+        with pytest.raises(lib.PccError, match=rf"channel count {c} unsupported \(needs 8, 16 or a multiple of 32\)"):
+            MinkowskiGDN(c)._pack()
+    rec = (ctypes.c_int32 * 4)(7, 7, 7, 7)
+    assert lib.load().pcc_gdn_last_launch(rec) == 0 and 0 <= rec[0] <= 3 and rec[3] in (0, 1)    # a host query: no launch
+    assert (rec[0] == 0) == (tuple(rec) == (0, 0, 0, 0))
+    assert lib.load().pcc_gdn_last_launch(None) != 0
+
+
 def test_round4_training_queries_are_pure_host_functions():
     """Support predicates and workspace queries of the round-4 training entry points (no launch, no GPU needed)."""
     from unified_point_cloud_compression_amd import lib
