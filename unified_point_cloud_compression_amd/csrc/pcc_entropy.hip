@@ -74,30 +74,34 @@ extern "C" int pcc_gauss_decode(const int32_t* sym, const float* params, const i
 // ------------------------------------------------------------------------------------------
 // factorised prior, filters (3,3,3,3): packed [c][58]
 // ------------------------------------------------------------------------------------------
+// The two evaluations of one element (x = v - 0.5 and v + 0.5) must round alike: in a channel whose logits are an odd function
+// of x they are exact negatives of each other, and sg = -sign(lo + up) decides on that sum being exactly 0.  Left to the
+// compiler, the contraction of a*b + c into a fused multiply-add is a choice per inlined copy (the last layer came out as three
+// chained fmas in one copy and as a packed multiply, one fma and an addition in the other), so the sums are written out here,
+// with contraction off, once for every user.
+__device__ inline float eb_dot3(const float* __restrict__ m, const float* h, float b) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(m[2], h[2], __builtin_fmaf(m[1], h[1], m[0] * h[0])) + b;
+}
+
+__device__ inline float eb_gate(float a, float f) {           // a + f tanh(a)
+#pragma clang fp contract(off)
+  return __builtin_fmaf(f, tanhf(a), a);
+}
+
 __device__ inline float eb_logits(const float* __restrict__ p, float x) {
-  const float* m0 = p;        const float* M1 = p + 3;  const float* M2 = p + 12; const float* M3 = p + 21;
-  const float* m4 = p + 30;   const float* b = p + 33;  const float* f = p + 46;
+  const float* m0 = p;        const float* Ms = p + 3;  const float* m4 = p + 30;   const float* b = p + 33;  const float* f = p + 46;
   float h[3], g[3];
 #pragma unroll
-  for (int i = 0; i < 3; ++i) { h[i] = m0[i] * x + b[i]; h[i] += f[i] * tanhf(h[i]); }
+  for (int i = 0; i < 3; ++i) h[i] = eb_gate(__builtin_fmaf(m0[i], x, b[i]), f[i]);
 #pragma unroll
-  for (int l = 0; l < 3; ++l) {
-    const float* M = (l == 0) ? M1 : (l == 1 ? M2 : M3);
+  for (int l = 1; l < 4; ++l) {
 #pragma unroll
-    for (int o = 0; o < 3; ++o) {
-      float v = M[o * 3 + 0] * h[0];
-      v += M[o * 3 + 1] * h[1];
-      v += M[o * 3 + 2] * h[2];
-      v += b[3 + 3 * l + o];
-      g[o] = v + f[3 + 3 * l + o] * tanhf(v);
-    }
+    for (int o = 0; o < 3; ++o) g[o] = eb_gate(eb_dot3(Ms + 9 * (l - 1) + o * 3, h, b[3 * l + o]), f[3 * l + o]);
 #pragma unroll
     for (int o = 0; o < 3; ++o) h[o] = g[o];
   }
-  float v = m4[0] * h[0];
-  v += m4[1] * h[1];
-  v += m4[2] * h[2];
-  return v + b[12];
+  return eb_dot3(m4, h, b[12]);
 }
 
 __device__ inline float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
@@ -145,27 +149,19 @@ extern "C" int pcc_eb_encode(const float* z, int64_t n, int32_t c, const float* 
 // ------------------------------------------------------------------------------------------
 struct EbTape { float a[4][3]; float h[5][3]; };       // pre-activations of the four gated layers, inputs of the five linear maps
 
-__device__ inline float eb_logits_tape(const float* __restrict__ p, float x, EbTape& t) {
+__device__ inline float eb_logits_tape(const float* __restrict__ p, float x, EbTape& t) {      // eb_logits, the same roundings
   const float* m0 = p;        const float* Ms = p + 3;  const float* m4 = p + 30;   const float* b = p + 33;  const float* f = p + 46;
 #pragma unroll
-  for (int i = 0; i < 3; ++i) { t.a[0][i] = m0[i] * x + b[i]; t.h[1][i] = t.a[0][i] + f[i] * tanhf(t.a[0][i]); }
+  for (int i = 0; i < 3; ++i) { t.a[0][i] = __builtin_fmaf(m0[i], x, b[i]); t.h[1][i] = eb_gate(t.a[0][i], f[i]); }
 #pragma unroll
   for (int l = 1; l < 4; ++l) {
-    const float* M = Ms + 9 * (l - 1);
 #pragma unroll
     for (int o = 0; o < 3; ++o) {
-      float v = M[o * 3 + 0] * t.h[l][0];
-      v += M[o * 3 + 1] * t.h[l][1];
-      v += M[o * 3 + 2] * t.h[l][2];
-      v += b[3 * l + o];
-      t.a[l][o] = v;
-      t.h[l + 1][o] = v + f[3 * l + o] * tanhf(v);
+      t.a[l][o] = eb_dot3(Ms + 9 * (l - 1) + o * 3, t.h[l], b[3 * l + o]);
+      t.h[l + 1][o] = eb_gate(t.a[l][o], f[3 * l + o]);
     }
   }
-  float v = m4[0] * t.h[4][0];
-  v += m4[1] * t.h[4][1];
-  v += m4[2] * t.h[4][2];
-  return v + b[12];
+  return eb_dot3(m4, t.h[4], b[12]);
 }
 
 // reverse pass of eb_logits for the upstream gradient gout: dp[58] += d out / d packed * gout; returns d out / d x * gout
