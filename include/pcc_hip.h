@@ -932,6 +932,45 @@ int pcc_voxel_means(const float* points, const float* attrs /*nullable*/, int32_
                     size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 12   multi-tensor optimiser step: clip_grad_norm_ + Adam / SGD with momentum over all tensors of an optimiser
+ *      (reference train.py:224-227: torch.nn.utils.clip_grad_norm_, optim.Adam / optim.SGD(momentum=0.9)).
+ * ---------------------------------------------------------------------------------------- */
+#define PCC_OPTIM_CHUNK 16384     /* elements of one tensor per workgroup */
+#define PCC_OPTIM_SEG_WORDS 6     /* int64 words per row of the segment table */
+#define PCC_OPTIM_ADAM 0
+#define PCC_OPTIM_SGD 1
+/* Segment table (device) [n_segs][PCC_OPTIM_SEG_WORDS] int64, one row per tensor: param*, grad*, state1*, state2*, n, t.
+ * All arrays fp32 with n elements.  grad* = 0: the tensor has no gradient this step; nothing of it is read or written.
+ * state1 = exp_avg (Adam) / momentum_buffer (SGD); state2 = exp_avg_sq (Adam; unused and may be 0 for SGD).  t = the
+ * tensor's step count with this step counted (1 = its first step): a tensor that was skipped keeps its own count, as in
+ * torch, so t travels with the gradient pointers and not as one kernel argument.
+ * Chunk table (device) [n_chunks][2] int32 = (segment, chunk index inside it): chunk i of a tensor holds its elements
+ * [i * PCC_OPTIM_CHUNK, min(n, (i + 1) * PCC_OPTIM_CHUNK)).  Sizes never change, so it is built once, on the host:
+ * pcc_optim_build_chunks returns the number of chunks of tensors of the given sizes (a tensor of 0 elements has none) and,
+ * when h_chunks is not NULL, writes the first `cap` entries; -1 for a negative size or count, or 2^31 chunks or more.
+ * An entry that names no segment or lies outside its tensor is skipped by the kernels, never dereferenced. */
+int32_t pcc_optim_chunk_elems(void);
+int64_t pcc_optim_build_chunks(const int64_t* h_sizes, int32_t n_segs, int32_t* h_chunks /*nullable*/, int64_t cap);
+size_t pcc_optim_ws_bytes(int64_t n_chunks); /* the fp64 partials, one per chunk */
+/* ws[chunk] = sum of g * g over the chunk in fp64 (0 for a tensor without gradient), in an order fixed by the chunk's
+ * length: no atomics, equal inputs give equal bits.  One launch of n_chunks workgroups.  PCC_EINVAL / PCC_EWS before any
+ * launch for n_segs < 0, n_chunks outside 0..2^31-1, a NULL table, a workspace below pcc_optim_ws_bytes(n_chunks). */
+int pcc_optim_sqnorm(const int64_t* d_segs, int32_t n_segs, const int32_t* d_chunks, int64_t n_chunks, void* ws, size_t ws_bytes,
+                     void* stream);
+/* One launch: every workgroup adds ws[0..n_chunks) in the same fixed order, norm = (float)sqrt(sum),
+ * coef = min(1, max_norm / (norm + 1e-6)) in fp32 (clip_grad_norm_'s rule; a NaN norm gives a NaN coefficient, an
+ * infinite one 0, as torch's arithmetic does), and updates its chunk with g * coef:
+ *   PCC_OPTIM_ADAM  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  p -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+ *                   (torch.optim.Adam without amsgrad and weight decay; the bias corrections in fp64)
+ *   PCC_OPTIM_SGD   buf = g when t = 1, else beta1 buf + g;  p -= lr buf      (beta1 = the momentum; beta2, eps unused)
+ * The gradients themselves are NOT overwritten with g * coef (clip_grad_norm_ does overwrite them).  max_norm <= 0: no
+ * clipping, ws is not read (pcc_optim_sqnorm need not have run) and *d_norm is not written; otherwise workgroup 0
+ * stores the norm to *d_norm (device fp32, nullable).  Refusals as for pcc_optim_sqnorm, and an unknown mode. */
+int pcc_optim_step(const int64_t* d_segs, int32_t n_segs, const int32_t* d_chunks, int64_t n_chunks, const void* ws, size_t ws_bytes,
+                   int32_t mode, double lr, double beta1, double beta2, double eps, double max_norm, float* d_norm /*nullable*/,
+                   void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * measurement support: per-launch HIP-event timing of the conv kernel (bench.py roofline)
  * ---------------------------------------------------------------------------------------- */
 int pcc_prof_enable(int32_t on);

@@ -8,6 +8,8 @@ Layout
   compressai/             `compressai.*` compatible surface
   model/                  UnifiedModel.compress()/decompress() counterpart of the reference's model/
   data.py                 training batches: cube slicing, colour jitter, rotation, collation on the GPU (reference data/)
+  optim.py                clip + Adam / SGD-momentum for all parameters in two launches (csrc/pcc_optim.hip)
+  train.py                the training loop: epochs, StepLR, validation, resumable checkpoints (reference train.py)
   frames.py               frame/block sharding across GPUs (one process per GPU, RCCL gather)
   ply.py                  PLY point clouds in and out: header in Python, body converted on the GPU
   voxelize.py             voxel-grid down-sampling with averaged attributes (Open3D's voxel_down_sample), reproducible bits

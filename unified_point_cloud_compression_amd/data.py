@@ -325,7 +325,7 @@ class TrainBatcher:
             generator = torch.Generator()
             generator.seed()
         self.generator = generator
-        self._stage, self._turn = [None, None], 0       # pinned staging buffers, each with the event of its last copy
+        self._staging = L.PinnedStaging(torch.int32)    # pinned staging buffers, each with the event of its last copy
 
     def __len__(self):
         return -(-len(self.eligible) // self.batch_size)
@@ -355,22 +355,11 @@ class TrainBatcher:
         the event recorded behind its last copy: a buffer is rewritten only after that event has completed, so the device
         copy the kernels index by is always the host copy that was validated, however much work the stream still holds and
         whether or not the step reads anything back."""
-        words = desc.size + blocks.size
-        k = self._turn = self._turn ^ 1
-        st = self._stage[k]
-        if st is None or st[0].numel() < words:
-            if st is not None:
-                st[1].synchronize()                        # the copy out of the buffer that is being replaced
-            st = self._stage[k] = (torch.empty(max(words * 2, 4096), dtype=torch.int32).pin_memory(), torch.cuda.Event())
-        else:
-            st[1].synchronize()
-        h = st[0][:words]
+        h = self._staging.acquire(desc.size + blocks.size)
         hn = h.numpy()
         hn[:desc.size] = desc.reshape(-1)
         hn[desc.size:] = blocks.reshape(-1)
-        d = h.to(self.table.device, non_blocking=True)
-        st[1].record()
-        return h, d
+        return h, self._staging.upload(h, self.table.device)
 
     def assemble(self, cube_indices, params, deduplicate=True):
         """The batch of the given cubes under the given parameters: one dict per slot with optional entries "jitter"

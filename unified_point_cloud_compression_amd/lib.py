@@ -200,6 +200,12 @@ SIGNATURES = {
     "pcc_voxel_keys": (C.c_int, [_p, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p, _p]),
     "pcc_voxel_means_ws_bytes": (_sz, [_i64, _i32]),
     "pcc_voxel_means": (C.c_int, [_p, _p, _i32, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "pcc_optim_chunk_elems": (_i32, []),
+    "pcc_optim_build_chunks": (_i64, [_p, _i32, _p, _i64]),
+    "pcc_optim_ws_bytes": (_sz, [_i64]),
+    "pcc_optim_sqnorm": (C.c_int, [_p, _i32, _p, _i64, _p, _sz, _p]),
+    "pcc_optim_step": (C.c_int, [_p, _i32, _p, _i64, _p, _sz, _i32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                 _p, _p]),
     "pcc_prof_enable": (C.c_int, [_i32]),
     "pcc_prof_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(_i64)]),
     "pcc_prof_sequence": (_i64, [C.POINTER(_i32), _i64]),
@@ -291,6 +297,35 @@ def workspace(nbytes, device):
     if buf is None or buf.numel() < nbytes:
         _ws[key] = buf = torch.empty(max(int(nbytes * 1.25), 1 << 20), dtype=torch.uint8, device=device)
     return buf
+
+
+class PinnedStaging:
+    """Small per-step tables to the device through pinned staging buffers and one asynchronous copy.  Two buffers take
+    turns, and each carries the event recorded behind its last copy: a buffer is rewritten only after that event has
+    completed, so the device copy the kernels index by is always the host copy that was filled in, however much work the
+    stream still holds and whether or not the step reads anything back."""
+
+    def __init__(self, dtype, min_elems=4096):
+        self.dtype, self.min_elems = dtype, min_elems
+        self._stage, self._turn = [None, None], 0
+
+    def acquire(self, elems):
+        """The next buffer's first `elems` elements (a pinned CPU tensor), free to be written."""
+        k = self._turn = self._turn ^ 1
+        st = self._stage[k]
+        if st is None or st[0].numel() < elems:
+            if st is not None:
+                st[1].synchronize()                        # the copy out of the buffer that is being replaced
+            st = self._stage[k] = (torch.empty(max(elems * 2, self.min_elems), dtype=self.dtype).pin_memory(), torch.cuda.Event())
+        else:
+            st[1].synchronize()
+        return st[0][:elems]
+
+    def upload(self, h, device):
+        """Device copy of what `acquire` returned last, queued on the current stream."""
+        d = h.to(device, non_blocking=True)
+        self._stage[self._turn][1].record()
+        return d
 
 
 # ---- device counters -----------------------------------------------------------------------------------------
