@@ -651,6 +651,59 @@ int pcc_geom_tables(const uint64_t* state, const uint32_t* h_pop, int32_t* cdf, 
 int pcc_geom_state_update(uint64_t* state, const uint32_t* hist, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 8f-3b' inter-frame lossless geometry (stream format 0xA8): the levels at and below the block pitch
+ *       2^block_log2 (block_log2 <= 4; a block is a node of that level) are coded against a reference cloud displaced per block
+ *       by one of the (2 search + 1)^3 integer vectors, search <= 2, ordered by |v|^2 and then lexicographically (index 0 = zero).
+ *       The displaced reference is held as one occupancy pyramid per block, pcc_geom_inter_pyramid_words() = 75 uint64 words:
+ *       tier e (cells of side 2^(block_log2 - e), bit lx << 2e | ly << e | lz) at word 0 / 64 / 72 / 73 / 74 for e = 4 .. 0.
+ *       The reference set is given in ABSOLUTE coordinates with its pitch-1 grid index (or three NULLs: binary search; n_ref == 0:
+ *       an empty reference); (ox, oy, oz) is the origin the coder's cells are relative to.  Integers only, no arrival order.
+ * pcc_geom_inter_candidates  HOST: the vector table h_out[n, 3] (nullable) of a search range; returns n, -1 on a bad range.
+ * pcc_geom_inter_block_bits  pyramid[b] of every block: cell p is set when source(origin + p - v[vec[b]]) is occupied; vec NULL:
+ *                            no displacement.  An index outside the table sets *d_bad and counts as 0.
+ * pcc_geom_inter_motion      vec[b] = the candidate with the most voxels p of the block (cur_pyramid, built from the current frame
+ *                            itself) for which reference(origin + p - v) is occupied; ties to the lowest index.  counts
+ *                            (nullable) receives the [n_blocks, candidates] match counts.
+ * pcc_geom_inter_occ_ctx     the counterpart of pcc_geom_occ_ctx for a level at 2 <= pitch <= 2^block_log2: idx[i] = context +
+ *                            64 * present, r[i] (nullable) = the predicted node's child byte (0: absent); with byte / sym
+ *                            non-NULL (encoder, needs the child set) the occupancy byte and the coded symbol: the byte for an
+ *                            absent node, rho^-1(byte ^ r) for a present one, rho = 0..255 ordered by (popcount, value).
+ *                            block_*: the canonical level at pitch 2^block_log2 and its grid index (or NULLs).
+ * pcc_geom_inter_map         inverse != 0: out = the byte of symbol in[i] under (idx, r); else the symbol of byte in[i].  What
+ *                            cannot occur (an absent node's value outside 1..255, a present node's byte 0) sets *d_bad, byte 1.
+ * pcc_geom_inter_hist        hist[pcc_geom_inter_hist_words() = 128 * 256 + 8 + 9] (uint32, zeroed here): hist[idx * 256 + sym],
+ *                            then the popcount classes of the absent nodes and the distance classes popcount(byte ^ r) of the
+ *                            present ones.  Integer atomics, reduced in LDS (32 rows per workgroup) first.
+ * pcc_geom_inter_tables      the decoder's 128 rows of one level from state[128 * 256] (uint64, device; rows 0..63 are the state of
+ *                            pcc_geom_tables) and the HOST class histograms: cdf int32 [128, 258] (rows 0..63: 257 entries) and
+ *                            the decoder table blob (pcc_geom_inter_dec_table_bytes(), padding zeroed by the caller).
+ *                            The state is updated by pcc_geom_state_update on each half.
+ * ---------------------------------------------------------------------------------------- */
+int32_t pcc_geom_inter_pyramid_words(void);
+int32_t pcc_geom_inter_candidates(int32_t search, int32_t* h_out /*nullable [n,3]*/);
+int pcc_geom_inter_block_bits(const int64_t* block_keys, int64_t n_blocks, int32_t block_log2, const int64_t* src_keys,
+                              int64_t n_src, const uint64_t* src_bits, const int32_t* src_rank, const int32_t* h_src,
+                              int32_t ox, int32_t oy, int32_t oz, const int32_t* vec /*nullable*/, int32_t search, uint64_t* pyramid,
+                              int32_t* d_bad, void* stream);
+int pcc_geom_inter_motion(const int64_t* block_keys, int64_t n_blocks, int32_t block_log2, const uint64_t* cur_pyramid,
+                          const int64_t* ref_keys, int64_t n_ref, const uint64_t* ref_bits, const int32_t* ref_rank,
+                          const int32_t* h_ref, int32_t ox, int32_t oy, int32_t oz, int32_t search, int32_t* counts /*nullable*/,
+                          int32_t* vec, void* stream);
+int pcc_geom_inter_occ_ctx(const int64_t* keys, int64_t n, int32_t pitch, const uint64_t* bits, const int32_t* rank,
+                           const int32_t* h_grid, const int64_t* child_keys, int64_t n_child, const uint64_t* child_bits,
+                           const int32_t* child_rank, const int32_t* h_child, const int64_t* block_keys, int64_t n_blocks,
+                           const uint64_t* block_bits, const int32_t* block_rank, const int32_t* h_block, int32_t block_log2,
+                           const uint64_t* pyramid, int32_t* byte /*nullable*/, int32_t* sym /*nullable*/, int32_t* r /*nullable*/,
+                           int32_t* idx, void* stream);
+int pcc_geom_inter_map(const int32_t* in, const int32_t* idx, const int32_t* r, int64_t n, int32_t inverse, int32_t* out,
+                       int32_t* d_bad, void* stream);
+int32_t pcc_geom_inter_hist_words(void);
+int pcc_geom_inter_hist(const int32_t* sym, const int32_t* idx, int64_t n, uint32_t* hist, int32_t* d_bad, void* stream);
+int64_t pcc_geom_inter_dec_table_bytes(void);
+int pcc_geom_inter_tables(const uint64_t* state, const uint32_t* h_pop, const uint32_t* h_dist, int32_t* cdf, void* dec_table,
+                          void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * 8f-3c RAHT colour coder over the level sets of 8f-3b: the anchor the reference compares against is
  *       `tmc3 --transformType=0` (`utils.py:505-529`); this is the same transform family in our own stream, no G-PCC syntax.
  *       A level is given as its canonical node keys at `pitch` plus the canonical child set at pitch / 2 with that set's grid

@@ -57,9 +57,11 @@ def scaled_voxels(cloud, position_scale):
 
 
 @torch.no_grad()
-def compress_anchor(cloud, qp, position_scale=1.0, chroma_qp_offset=-2):
+def compress_anchor(cloud, qp, position_scale=1.0, chroma_qp_offset=-2, reference=None):
     """[N, 6] GPU cloud (xyz, rgb in [0, 1]) -> bytes.  position_scale in (0, 1]: below 1 the points are scaled first; points
-    that then share a cell are merged with their mean colour.  qp, chroma_qp_offset: `attributes.encode_attributes`."""
+    that then share a cell are merged with their mean colour.  qp, chroma_qp_offset: `attributes.encode_attributes`.
+    reference: voxels IN THE SCALED DOMAIN that `decompress_anchor` will be given too (the previous frame's decoded geometry,
+    say): the geometry is then coded against them where that is shorter (`geometry.encode_geometry`); colour stays intra."""
     what = "compress_anchor"
     if not torch.is_tensor(cloud) or cloud.dim() != 2 or cloud.shape[1] != 6 or cloud.shape[0] == 0:
         raise L.PccError(f"{what}: a non-empty [N, 6] cloud (xyz, rgb in [0, 1]) is required")
@@ -72,16 +74,17 @@ def compress_anchor(cloud, qp, position_scale=1.0, chroma_qp_offset=-2):
     c4 = torch.cat([torch.zeros((g.index.shape[0], 1), dtype=torch.int32, device=cloud.device), g.index], dim=1).contiguous()
     cs = S.coordset_from_coords(c4, 1)[0]                    # the grid's rows are ascending: canonical as they are
     levels = torch.round(g.attrs.to(torch.float64) * 255.0).clamp_(0, 255).to(torch.uint8)
-    geometry = encode_geometry(cs)
+    geometry = encode_geometry(cs, reference=reference)
     attributes = encode_attributes(cs, qp, chroma_qp_offset, attrs=levels)
     return HEADER.pack(MAGIC, scale, len(geometry)) + geometry + attributes
 
 
 @torch.no_grad()
-def decompress_anchor(data, device):
-    """bytes -> [n, 6] float32 on `device`: positions divided by the scale, colours / 255, in canonical order."""
+def decompress_anchor(data, device, reference=None):
+    """bytes -> [n, 6] float32 on `device`: positions divided by the scale, colours / 255, in canonical order.  reference:
+    the scaled-domain voxels `compress_anchor` was given."""
     scale, geometry, attributes = parse_container(data)
-    cs = decode_geometry(geometry, device, as_set=True)
+    cs = decode_geometry(geometry, device, as_set=True, reference=reference)
     levels = decode_attributes(attributes, cs)
     dev = cs.device
     xyz = cs.coords()[:cs.n, 1:].to(torch.float64) / torch.tensor(scale, dtype=torch.float64, device=dev)
@@ -107,10 +110,11 @@ def parse_lossless_container(data):
 
 
 @torch.no_grad()
-def compress_lossless(cloud):
+def compress_lossless(cloud, reference=None):
     """[N, 6] GPU cloud of distinct voxels (integer xyz, rgb in [0, 1]: colours become round(255 c)) -> bytes from which
     `decompress_lossless` returns the same voxels with the same levels.  Non-integer coordinates and repeated voxels raise
-    PccError: voxelise first (`voxelize.voxel_grid`)."""
+    PccError: voxelise first (`voxelize.voxel_grid`).  reference: a voxel cloud (its first three columns) the decoder holds
+    too, e.g. the previous frame: the geometry is coded against it where that is shorter; colour stays intra."""
     what = "compress_lossless"
     if not torch.is_tensor(cloud) or cloud.dim() != 2 or cloud.shape[1] != 6 or cloud.shape[0] == 0:
         raise L.PccError(f"{what}: a non-empty [N, 6] cloud (xyz, rgb in [0, 1]) is required")
@@ -125,17 +129,17 @@ def compress_lossless(cloud):
         raise L.PccError(f"{what}: {cloud.shape[0] - cs.n} rows repeat a voxel; merge them first (voxelize.voxel_grid)")
     levels = torch.round(cloud[:, 3:6].to(torch.float64) * 255.0).clamp_(0, 255).to(torch.uint8)
     levels = (levels if perm is None else levels[perm]).contiguous()
-    geometry = encode_geometry(cs)
+    geometry = encode_geometry(cs, reference=reference)
     attributes = encode_attributes_lossless(cs, attrs=levels)
     return LOSSLESS_HEADER.pack(LOSSLESS_MAGIC, len(geometry)) + geometry + attributes
 
 
 @torch.no_grad()
-def decompress_lossless(data, device):
+def decompress_lossless(data, device, reference=None):
     """bytes -> [n, 6] float32 on `device` in canonical order: the exact coordinates, colours level / 255 (round(255 c) of
-    them gives the levels back)."""
+    them gives the levels back).  reference: the cloud `compress_lossless` was given."""
     geometry, attributes = parse_lossless_container(data)
-    cs = decode_geometry(geometry, device, as_set=True)
+    cs = decode_geometry(geometry, device, as_set=True, reference=reference)
     levels = decode_attributes_lossless(attributes, cs)
     rgb = levels.to(torch.float64) / torch.tensor(255.0, dtype=torch.float64, device=cs.device)
     return torch.cat([cs.coords()[:cs.n, 1:].to(torch.float64), rgb], dim=1).to(torch.float32)

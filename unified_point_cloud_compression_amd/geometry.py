@@ -21,6 +21,24 @@ stream kernels.  Device->host reads, by construction: encode 5 (bounds, level si
 bytes, the payload; one more for the canonicalisation's count when tensor rows are not yet in canonical order); decode ONE,
 at the end (every level's rANS status, byte check, child total, popcount histogram and row count, and the bounds of `as_set`):
 the decoder derives its tables on the device (`pcc_geom_tables`, the same integer rule) and sizes everything by the header.
+
+Inter streams (`encode_geometry(x, reference=r)`, DESIGN.md section 7e "Inter frames"): with a reference cloud both sides hold,
+the levels at and below the block pitch 2^BLOCK_LOG2 are coded against a motion-compensated prediction.
+
+    stream  = u8 0xA8 | u32 n | u8 depth | 3 x i32 origin | u8 block_log2 | u8 search
+              | levels 0 .. first-1 as above | vectors | levels first .. depth-1          (first = max(0, depth - block_log2))
+    vectors = one index into `candidates(search)` per node of level `first` (a block), in canonical order:
+              raw:    one byte each                                            (fewer than RAW_NODES blocks)
+              coded:  u8 m | m x (u8 index, u32 count) ascending | u32 length | rANS container over the table of `vector_table`
+              nothing at all when search = 0
+    level   = raw:    the occupancy bytes of its nodes, as above
+              coded:  8 x u32 popcount classes of the nodes absent from the prediction | 9 x u32 distance classes of the present
+                      ones | u32 child total | u32 length | rANS container, table row = context + 64 * present
+
+The prediction is the reference displaced per block by the block's vector and clipped to the block; a node present in it codes
+rho^-1(byte XOR predicted byte), rho = 0..255 by (popcount, value), with table rows, adaptive counts and class correction of its
+own (`derive_tables_inter`).  The kernels are those of csrc/pcc_geom_inter.hip; the encoder's vectors ride in the read that
+fetches the raw levels' bytes, the decoder still reads ONCE, at the end.  `encode_sequence` / `decode_sequence` chain frames.
 """
 import ctypes as C
 import struct
@@ -100,16 +118,139 @@ def derive_tables(counts, pop):
 TABLE_SIZES = np.full(N_CTX, N_SYM + 2, dtype=np.int32)
 TABLE_OFFSETS = np.ones(N_CTX, dtype=np.int32)
 
+# ---- the inter stream, format 0xA8 (module docstring; DESIGN.md section 7e "Inter frames") -----------------------------------
+MAGIC_INTER = 0xA8
+BLOCK_LOG2 = 4            # blocks are the nodes at pitch 16: one motion vector each
+SEARCH = 2                # vectors in [-2, 2]^3: 125 candidates, an index fits a byte
+MAX_SEARCH = 2
+HEADER_INTER = struct.Struct("<BIB3iBB")
+SIDE_INTER = struct.Struct("<8I9III")      # popcount classes of the absent nodes | distance classes of the present | children | length
+N_ROWS = 2 * N_CTX        # table rows: context + 64 * present
+INTER_STRIDE = 258        # present rows: 256 symbols + the escape slot
+RHO = np.array(sorted(range(256), key=lambda t: (int(POPCOUNT[t]), t)), dtype=np.int64)     # symbol -> t = byte XOR prediction
+RHO_INV = np.argsort(RHO)
+INTER_SIZES = np.array([N_SYM + 2] * N_CTX + [INTER_STRIDE] * N_CTX, dtype=np.int32)
+INTER_OFFSETS = np.array([1] * N_CTX + [0] * N_CTX, dtype=np.int32)
 
-def parse_header(data):
+
+def candidates(search=SEARCH):
+    """The (2 * search + 1)^3 motion vectors by |v|^2, then lexicographically; index 0 is the zero vector."""
+    r = range(-search, search + 1)
+    return sorted(((dx, dy, dz) for dx in r for dy in r for dz in r), key=lambda v: (v[0] ** 2 + v[1] ** 2 + v[2] ** 2, v))
+
+
+def _family_rows(N, cls, classes, hist):
+    """Frequencies [64, nsym] of one population (steps 1-4 of `derive_tables`): N the live columns of its counts, cls the class
+    of each live symbol, hist the level's class histogram.  A population without a node in the level takes r = 1."""
+    nsym = N.shape[1]
+    shift = max(0, int(N.sum()).bit_length() - 20)
+    N = N >> shift
+    G = N.sum(axis=0)
+    gt = int(G.sum()) + nsym
+    W = N * gt + PRIOR_WEIGHT * (G + 1)[None, :]
+    q = 1 + (W << 20) // W.sum(axis=1, keepdims=True)
+    hist = [int(v) for v in hist]
+    ht = sum(hist)
+    r = np.full(classes, 1 if ht == 0 else 0, dtype=np.int64)
+    for k in range(classes):
+        if hist[k] > 0:
+            e = int((G[cls == k] + 1).sum())
+            r[k] = min(max((hist[k] * gt << 12) // (ht * e), 1), 1 << 20)
+    w = q * r[cls][None, :]
+    f = 1 + w * (65535 - nsym) // w.sum(axis=1, keepdims=True)
+    f[np.arange(N_CTX), np.argmax(f, axis=1)] += 65535 - f.sum(axis=1)
+    return f
+
+
+def derive_tables_inter(counts, pop, dist):
+    """Quantised CDF rows [128, 258] int32 of one inter level.  Rows 0..63, the nodes absent from the prediction: the rule of
+    `derive_tables` on counts[:64] and the popcount histogram of those nodes (257 entries).  Rows 64..127, the present nodes:
+    the same rule over the 256 symbols rho^-1(byte XOR prediction) with the 9 classes popcount(byte XOR prediction) and their
+    histogram dist[9] (258 entries).  The two populations are rescaled, mixed and corrected separately."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(N_ROWS, 256)
+    cdf = np.zeros((N_ROWS, INTER_STRIDE), dtype=np.int64)
+    cdf[:N_CTX, 1:N_SYM + 1] = np.cumsum(_family_rows(counts[:N_CTX, 1:], POPCOUNT[1:] - 1, 8, pop), axis=1)
+    cdf[:N_CTX, N_SYM + 1] = 65536
+    cdf[N_CTX:, 1:257] = np.cumsum(_family_rows(counts[N_CTX:], POPCOUNT[RHO], 9, dist), axis=1)
+    cdf[N_CTX:, 257] = 65536
+    return np.ascontiguousarray(cdf.astype(np.int32))
+
+
+def vector_table(hist):
+    """CDF row [1, K + 2] of the vector indices from their transmitted histogram hist[K]: f = 1 + hist * (65535 - K) // blocks,
+    what is left of 65535 to the first largest f, 1 for the escape slot."""
+    k = len(hist)
+    total = sum(int(v) for v in hist)
+    f = [1 + int(v) * (65535 - k) // total for v in hist]
+    f[f.index(max(f))] += 65535 - sum(f)
+    cdf = np.zeros((1, k + 2), dtype=np.int32)
+    cdf[0, 1:k + 1] = np.cumsum(f)
+    cdf[0, k + 1] = 65536
+    return cdf
+
+
+def _container_streams(data, at, nbytes, symbols, what):
+    """The stream count a container of `nbytes` bytes at data[at:] claims for `symbols` symbols; refuses what cannot be one."""
+    if nbytes < 8 or nbytes % 4 or at + nbytes > len(data):
+        raise L.PccError(f"geometry stream truncated inside the payload of {what}")
+    streams = int.from_bytes(data[at:at + 4], "little")
+    if not 1 <= streams <= min(symbols, 65536) or nbytes < 4 * (1 + streams):
+        raise L.PccError(f"geometry stream: {what} claims {streams} rANS streams for {symbols} symbols")
+    return streams
+
+
+def _parse_vectors(data, at, blocks, k):
+    """The vector list behind the levels above the blocks: (dict(raw, payload, hist, streams), end)."""
+    if k == 1:
+        return {"raw": True, "payload": (at, at), "hist": [blocks], "streams": 0}, at
+    if blocks < RAW_NODES:
+        if at + blocks > len(data):
+            raise L.PccError("geometry stream truncated inside the vector list")
+        if max(data[at:at + blocks]) >= k:
+            raise L.PccError(f"geometry stream: a vector index outside the {k} candidates")
+        return {"raw": True, "payload": (at, at + blocks), "hist": None, "streams": 0}, at + blocks
+    if at + 1 > len(data) or at + 1 + 5 * data[at] + 4 > len(data):
+        raise L.PccError("geometry stream truncated inside the vector histogram")
+    hist, last = [0] * k, -1
+    for j in range(data[at]):
+        i, c = struct.unpack_from("<BI", data, at + 1 + 5 * j)
+        if not last < i < k or c == 0:
+            raise L.PccError("geometry stream: the vector histogram lists indices in ascending order, each with a count")
+        hist[i], last = c, i
+    if sum(hist) != blocks:
+        raise L.PccError(f"geometry stream: the vector histogram counts {sum(hist)} of {blocks} blocks")
+    at += 1 + 5 * data[at]
+    nbytes = int.from_bytes(data[at:at + 4], "little")
+    at += 4
+    streams = _container_streams(data, at, nbytes, blocks, "the vector list")
+    return {"raw": False, "payload": (at, at + nbytes), "hist": hist, "streams": streams}, at + nbytes
+
+
+def parse_header(data, have_reference=True):
     """Walk the stream on the host: {n, depth, origin, levels}; levels[l] = dict(nodes, children, raw, payload=(begin, end),
-    pop).  Raises PccError on a bad magic byte, depth or n, on truncated or inconsistent side information and on trailing
+    pop).  An inter stream (0xA8) adds inter=True, block_log2, search, first (the level of the blocks) and vectors = dict(raw,
+    payload, hist, streams); its levels carry `inter` (coded against the prediction) and, coded ones of those, `dist`.  Raises PccError on a bad magic byte, depth, n, block size or search
+    range, on an inter stream when the caller has no reference, on truncated or inconsistent side information and on trailing
     bytes -- before any GPU work."""
     if len(data) < HEADER.size:
         raise L.PccError("geometry stream truncated inside the header")
     magic, n, depth, ox, oy, oz = HEADER.unpack_from(data, 0)
-    if magic != MAGIC:
-        raise L.PccError(f"geometry stream: magic byte {magic:#x}, this build reads {MAGIC:#x}")
+    if magic not in (MAGIC, MAGIC_INTER):
+        raise L.PccError(f"geometry stream: magic byte {magic:#x}, this build reads {MAGIC:#x} and {MAGIC_INTER:#x}")
+    inter = magic == MAGIC_INTER
+    at, first, k, block_log2, search = HEADER.size, depth, 1, 0, 0
+    if inter:
+        if not have_reference:
+            raise L.PccError("geometry stream: an inter stream (0xa8) decodes against a reference cloud, none was given")
+        if len(data) < HEADER_INTER.size:
+            raise L.PccError("geometry stream truncated inside the header")
+        block_log2, search = data[at], data[at + 1]
+        at = HEADER_INTER.size
+        if block_log2 != BLOCK_LOG2 or search > MAX_SEARCH:
+            raise L.PccError(f"geometry stream: block_log2 {block_log2} / search {search}, this build reads {BLOCK_LOG2} / 0..{MAX_SEARCH}")
+        if n == 0:
+            raise L.PccError("geometry stream: an empty cloud travels as an intra stream")
+        first, k = max(0, depth - block_log2), (2 * search + 1) ** 3
     if n == 0:
         if depth != 0 or len(data) != HEADER.size:
             raise L.PccError("geometry stream: an empty cloud has depth 0 and no levels")
@@ -121,8 +262,10 @@ def parse_header(data):
     reach = (1 << (depth - 1)) if depth > 1 else 0            # the largest cell has bit depth - 1 set (depth is minimal)
     if min(ox, oy, oz) < -S.BIAS + 64 or max(ox, oy, oz) + reach >= S.BIAS - 64:
         raise L.PccError(f"geometry stream: origin {(ox, oy, oz)} at depth {depth} leaves the 16-bit key range")
-    at, nodes, levels = HEADER.size, 1, []
+    nodes, levels, vectors = 1, [], None
     for lvl in range(depth):
+        if inter and lvl == first:
+            vectors, at = _parse_vectors(data, at, nodes, k)
         if nodes < RAW_NODES:
             if at + nodes > len(data):
                 raise L.PccError(f"geometry stream truncated inside raw level {lvl}")
@@ -132,6 +275,18 @@ def parse_header(data):
             children = sum(int(POPCOUNT[b]) for b in body)
             lv = {"nodes": nodes, "children": children, "raw": True, "payload": (at, at + nodes), "pop": None}
             at += nodes
+        elif lvl >= first:
+            if at + SIDE_INTER.size > len(data):
+                raise L.PccError(f"geometry stream truncated inside the side information of level {lvl}")
+            side = SIDE_INTER.unpack_from(data, at)
+            pop, dist, children, nbytes = list(side[:8]), list(side[8:17]), side[17], side[18]
+            at += SIDE_INTER.size
+            if sum(pop) + sum(dist) != nodes:
+                raise L.PccError(f"geometry stream: level {lvl} has {nodes} nodes, its class histograms count {sum(pop) + sum(dist)}")
+            streams = _container_streams(data, at, nbytes, nodes, f"level {lvl}")
+            lv = {"nodes": nodes, "children": children, "raw": False, "payload": (at, at + nbytes), "pop": pop, "dist": dist,
+                  "streams": streams}
+            at += nbytes
         else:
             if at + SIDE.size > len(data):
                 raise L.PccError(f"geometry stream truncated inside the side information of level {lvl}")
@@ -139,14 +294,12 @@ def parse_header(data):
             at += SIDE.size
             if sum(pop) != nodes:
                 raise L.PccError(f"geometry stream: level {lvl} has {nodes} nodes, its popcount histogram counts {sum(pop)}")
-            if nbytes < 8 or nbytes % 4 or at + nbytes > len(data):
-                raise L.PccError(f"geometry stream truncated inside the payload of level {lvl}")
-            streams = int.from_bytes(data[at:at + 4], "little")
-            if not 1 <= streams <= min(nodes, 65536) or nbytes < 4 * (1 + streams):
-                raise L.PccError(f"geometry stream: level {lvl} claims {streams} rANS streams for {nodes} nodes")
-            children = sum((k + 1) * v for k, v in enumerate(pop))
+            streams = _container_streams(data, at, nbytes, nodes, f"level {lvl}")
+            children = sum((k_ + 1) * v for k_, v in enumerate(pop))
             lv = {"nodes": nodes, "children": children, "raw": False, "payload": (at, at + nbytes), "pop": pop, "streams": streams}
             at += nbytes
+        if inter:
+            lv["inter"] = lvl >= first
         # a zero byte is unrepresentable: a level's child total is at least its node count, and never more than n
         if not nodes <= children <= n:
             raise L.PccError(f"geometry stream: level {lvl} expands {nodes} nodes to {children} for {n} points")
@@ -156,7 +309,10 @@ def parse_header(data):
         raise L.PccError(f"geometry stream: the last level gives {nodes} points, the header says {n}")
     if at != len(data):
         raise L.PccError("geometry stream: trailing bytes")
-    return {"n": n, "depth": depth, "origin": (ox, oy, oz), "levels": levels}
+    hdr = {"n": n, "depth": depth, "origin": (ox, oy, oz), "levels": levels}
+    if inter:                                  # (an intra stream's dictionary is what it always was)
+        hdr.update(inter=True, block_log2=block_log2, search=search, first=first, vectors=vectors)
+    return hdr
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -225,12 +381,224 @@ def level_sets(cs, origin, depth):
     return sets[::-1]
 
 
+def reference_set(reference, what="encode_geometry"):
+    """The reference cloud of an inter stream as a canonical pitch-1 single-batch CoordSet in absolute coordinates (the rules of
+    `canonical_rows`), or None for an empty one."""
+    if torch.is_tensor(reference) and reference.dim() == 2 and reference.shape[1] >= 3 and reference.is_cuda and reference.shape[0] == 0:
+        return None
+    rs = canonical_rows(reference, f"{what} (reference)")[0]
+    return rs if rs.n else None
+
+
 @torch.no_grad()
-def encode_geometry(x, segment_nodes=SEGMENT_NODES, timings=None):
+def encode_geometry(x, segment_nodes=SEGMENT_NODES, timings=None, reference=None, mode="auto"):
     """[N, >= 3] GPU tensor (any row order, duplicates allowed, floats floored) or pitch-1 CoordSet -> bytes.
     segment_nodes: nodes per rANS stream (tests lower it to cut small levels into several streams; the decoder reads the
-    stream count from each container).  timings: a dict that receives per-level device events (tools/geometry_timing.py)."""
+    stream count from each container).  timings: a dict that receives per-level device events (tools/geometry_timing.py).
+    reference: a voxel cloud the decoder holds too (same kinds of input as x), against which the levels at and below the block
+    pitch are predicted.  mode "auto": the shorter of the inter (0xA8) and the intra (0xA7) stream, intra on a tie -- never
+    longer than without a reference; "inter": the inter stream (an empty cloud still travels as intra); "intra", or no
+    reference: today's stream byte for byte."""
+    if mode not in ("auto", "inter", "intra"):
+        raise L.PccError(f"encode_geometry: mode {mode!r} is not one of auto, inter, intra")
     cs = _input_set(x)
+    if reference is None or mode == "intra" or cs.n == 0:
+        return _encode_intra(cs, segment_nodes, timings)
+    rs = reference_set(reference)
+    inter = _encode_inter(cs, rs, segment_nodes, timings)
+    if mode == "inter":
+        return inter
+    intra = _encode_intra(cs, segment_nodes, None)
+    if timings is not None:
+        timings["inter_bytes"], timings["intra_bytes"] = len(inter), len(intra)
+    return inter if len(inter) < len(intra) else intra
+
+
+def _ref_args(rs):
+    """Kernel arguments (keys, n, bits, rank, h) of a reference set; None: the empty reference."""
+    if rs is None:
+        return None, 0, None, None, None
+    return (L.ptr(rs.keys), rs.n, *S.grid_args(rs.grid() if S.USE_GRID else None))
+
+
+class _Phases:
+    """Device time between named marks (tools/geometry_inter_timing.py); inert when the caller asked for no timings."""
+
+    def __init__(self, on):
+        self.marks = [] if on else None
+
+    def mark(self, name):
+        if self.marks is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            self.marks.append((name, ev))
+
+    def report(self):
+        out = {}
+        for (_, a), (name, b) in zip(self.marks[:-1], self.marks[1:]):
+            out[name] = out.get(name, 0.0) + a.elapsed_time(b)
+        return out
+
+
+def motion_vectors(cs, rs, origin, depth, sets=None, counts=False):
+    """(blocks set, block_log2 of this cloud, current pyramid, int32 vector index per block[, int32 match counts [blocks, K]]) of
+    the canonical set `cs` against the reference `rs`: `pcc_geom_inter_block_bits` on the frame itself, `pcc_geom_inter_motion`."""
+    lib = L.load()
+    dev = cs.device
+    sets = level_sets(cs, origin, depth) if sets is None else sets
+    first = max(0, depth - BLOCK_LOG2)
+    bl = depth - first
+    blocks, voxels = sets[first], sets[depth]
+    pw = lib.pcc_geom_inter_pyramid_words()
+    cur = torch.empty(blocks.n * pw, dtype=torch.int64, device=dev)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    vec = torch.empty(blocks.n, dtype=torch.int32, device=dev)
+    cnt = torch.empty((blocks.n, (2 * SEARCH + 1) ** 3), dtype=torch.int32, device=dev) if counts else None
+    L.call("pcc_geom_inter_block_bits", L.ptr(blocks.keys), blocks.n, bl, L.ptr(voxels.keys), voxels.n,
+           *S.grid_args(voxels.grid() if S.USE_GRID else None), 0, 0, 0, None, SEARCH, L.ptr(cur), L.ptr(bad), L.stream())
+    L.call("pcc_geom_inter_motion", L.ptr(blocks.keys), blocks.n, bl, L.ptr(cur), *_ref_args(rs), *origin, SEARCH, L.ptr(cnt), L.ptr(vec),
+           L.stream())
+    return (blocks, bl, cur, vec, cnt) if counts else (blocks, bl, cur, vec)
+
+
+def _encode_inter(cs, rs, segment_nodes, timings):
+    """The inter stream (0xA8) of the canonical non-empty set `cs` against the reference set `rs` (None: empty).  Device->host
+    reads: those of the intra encoder -- the vectors travel with the raw levels' bytes."""
+    n = cs.n
+    origin = tuple(cs.bounds.lo)
+    depth = max(1, max(cs.bounds.hi[i] - origin[i] for i in range(3)).bit_length())
+    first = max(0, depth - BLOCK_LOG2)
+    k_vec = (2 * SEARCH + 1) ** 3
+    dev = cs.device
+    lib = L.load()
+    ph = _Phases(timings is not None)
+    with torch.cuda.device(dev):
+        ph.mark("start")
+        sets = level_sets(cs, origin, depth)
+        ph.mark("level_sets_ms")
+        blocks, bl, _, vec = motion_vectors(cs, rs, origin, depth, sets)
+        ph.mark("motion_search_ms")
+        nb = blocks.n
+        bgrid = blocks.grid() if (first and S.USE_GRID) else None
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        pred = torch.empty(nb * lib.pcc_geom_inter_pyramid_words(), dtype=torch.int64, device=dev)
+        L.call("pcc_geom_inter_block_bits", L.ptr(blocks.keys), nb, bl, *_ref_args(rs), *origin, L.ptr(vec), SEARCH, L.ptr(pred), L.ptr(bad),
+               L.stream())
+        ph.mark("compensation_ms")
+        hw, hwi = lib.pcc_geom_hist_words(), lib.pcc_geom_inter_hist_words()
+        nodes = [s.n for s in sets[:depth]]
+        at = np.concatenate([[0], np.cumsum(nodes)]).tolist()
+        sym = torch.empty(at[-1], dtype=torch.int32, device=dev)        # what the rANS coder sees
+        idx = torch.empty(at[-1], dtype=torch.int32, device=dev)        # its table row: context + 64 * present
+        byte = torch.empty(at[-1], dtype=torch.int32, device=dev)       # the occupancy bytes of the inter levels (raw levels travel as these)
+        hist = torch.zeros(first * hw + (depth - first) * hwi, dtype=torch.int32, device=dev)
+        h_at = [l * hw if l < first else first * hw + (l - first) * hwi for l in range(depth)]
+        for l in range(depth):
+            node, child = sets[l], sets[l + 1]
+            sp, ip, hp = sym.data_ptr() + 4 * at[l], idx.data_ptr() + 4 * at[l], hist.data_ptr() + 4 * h_at[l]
+            ngrid = S.grid_args(node.grid() if (l and S.USE_GRID) else None)
+            cgrid = S.grid_args(child.grid() if S.USE_GRID else None)
+            if l < first:
+                L.call("pcc_geom_occ_ctx", L.ptr(node.keys), node.n, node.ts, *ngrid, L.ptr(child.keys), child.n, *cgrid, sp, ip, L.stream())
+                L.call("pcc_geom_hist", sp, ip, node.n, hp, L.ptr(bad), L.stream())
+            else:
+                L.call("pcc_geom_inter_occ_ctx", L.ptr(node.keys), node.n, node.ts, *ngrid, L.ptr(child.keys), child.n, *cgrid,
+                       L.ptr(blocks.keys), nb, *S.grid_args(bgrid), bl, L.ptr(pred), byte.data_ptr() + 4 * at[l], sp, None, ip, L.stream())
+                L.call("pcc_geom_inter_hist", sp, ip, node.n, hp, L.ptr(bad), L.stream())
+        ph.mark("symbols_hist_ms")
+        h_hist = hist.cpu().numpy().astype(np.int64)                       # one read: every level's histograms
+        raw_lv = [l for l in range(depth) if nodes[l] < RAW_NODES]
+        parts = [(sym if l < first else byte)[at[l]:at[l + 1]] for l in raw_lv] + [vec]
+        got = torch.cat(parts).to(torch.uint8).cpu().numpy()               # one read: the raw levels' bytes and the vectors
+        raw_bytes, p = {}, 0
+        for l in raw_lv:
+            raw_bytes[l] = got[p:p + nodes[l]].tobytes()
+            p += nodes[l]
+        h_vec = got[p:p + nb]
+        # containers: the vector list (when it is coded) and the coded levels, one rANS launch each into a shared blob
+        state = np.zeros((N_ROWS, 256), dtype=np.int64)
+        coded = [l for l in range(depth) if nodes[l] >= RAW_NODES]
+        code_vec = k_vec > 1 and nb >= RAW_NODES
+        jobs = (["vec"] if code_vec else []) + coded
+        plans = {l: R.Plan(nodes[l], 1, 1, segments_for(nodes[l], segment_nodes)) for l in coded}
+        if code_vec:
+            plans["vec"] = R.Plan(nb, 1, 1, segments_for(nb, segment_nodes))
+        caps = {j: R.align8(plans[j].capacity) for j in jobs}
+        head = 8 * max(len(jobs), 1)
+        blob = torch.zeros(head + sum(caps.values()), dtype=torch.uint8, device=dev)
+        begin, keep, where = head, [], {}
+
+        def run(job, tabs, sp, ip):
+            nonlocal begin
+            keep.append(tabs)
+            R.encode(tabs, plans[job], sp, ip, blob.data_ptr() + begin, blob.data_ptr() + 8 * jobs.index(job))
+            where[job] = (begin, caps[job])
+            begin += caps[job]
+
+        if code_vec:
+            v_hist = np.bincount(h_vec, minlength=k_vec)
+            v_idx = torch.zeros(nb, dtype=torch.int32, device=dev)
+            keep.append(v_idx)
+            run("vec", R.fresh_cdf_tables(f"geometry_vectors{k_vec}", dev, vector_table(v_hist), np.array([k_vec + 2], dtype=np.int32),
+                                          np.zeros(1, dtype=np.int32)), L.ptr(vec), L.ptr(v_idx))
+        for l in range(depth):
+            h = h_hist[h_at[l]:h_at[l] + (hw if l < first else hwi)]
+            sp, ip = sym.data_ptr() + 4 * at[l], idx.data_ptr() + 4 * at[l]
+            if l < first:
+                if l in plans:
+                    run(l, R.fresh_cdf_tables("geometry", dev, derive_tables(state[:N_CTX], h[N_CTX * 256:]), TABLE_SIZES, TABLE_OFFSETS), sp, ip)
+                state = state >> 1
+                state[:N_CTX] += h[:N_CTX * 256].reshape(N_CTX, 256)
+            else:
+                if l in plans:
+                    cdf = derive_tables_inter(state, h[N_ROWS * 256:N_ROWS * 256 + 8], h[N_ROWS * 256 + 8:])
+                    run(l, R.fresh_cdf_tables("geometry_inter", dev, cdf, INTER_SIZES, INTER_OFFSETS), sp, ip)
+                state = (state >> 1) + h[:N_ROWS * 256].reshape(N_ROWS, 256)
+        ph.mark("tables_rans_ms")
+        host = blob.cpu().numpy()                                          # one read: sizes + containers
+        sizes = host[:head].view(np.int64)
+        ph.mark("payload_read_ms")
+
+    def container(job):
+        b0, cap = where[job]
+        nb_ = int(sizes[jobs.index(job)])
+        if not 0 < nb_ <= cap:
+            raise L.PccError(f"encode_geometry: container {job} produced {nb_} bytes for a capacity of {cap}")
+        return host[b0:b0 + nb_].tobytes()
+
+    out = bytearray(HEADER_INTER.pack(MAGIC_INTER, n, depth, *origin, BLOCK_LOG2, SEARCH))
+    for l in range(depth):
+        if l == first and k_vec > 1:
+            if code_vec:
+                occ = np.flatnonzero(v_hist)
+                body = container("vec")
+                out += struct.pack("<B", len(occ)) + b"".join(struct.pack("<BI", int(i), int(v_hist[i])) for i in occ)
+                out += struct.pack("<I", len(body)) + body
+            else:
+                out += h_vec.tobytes()
+        if l in raw_bytes:
+            out += raw_bytes[l]
+            continue
+        h = h_hist[h_at[l]:h_at[l] + (hw if l < first else hwi)]
+        body = container(l)
+        if l < first:
+            out += SIDE.pack(*[int(v) for v in h[N_CTX * 256:]], len(body))
+        else:
+            pop, dist = [int(v) for v in h[N_ROWS * 256:N_ROWS * 256 + 8]], [int(v) for v in h[N_ROWS * 256 + 8:]]
+            # (the distance classes do not give the child total, so it travels: the next level's node count)
+            out += SIDE_INTER.pack(*pop, *dist, nodes[l + 1] if l + 1 < depth else n, len(body))
+        out += body
+    if timings is not None:
+        torch.cuda.synchronize(dev)
+        timings["inter"] = ph.report()
+        timings["blocks"] = nb
+        timings["zero_vectors"] = int((h_vec == 0).sum())
+        timings["host_reads_by_construction"] = 3 + 1 + 1                  # bounds, level sizes, histograms | bytes + vectors | payload
+    return bytes(out)
+
+
+def _encode_intra(cs, segment_nodes, timings):
+    """The intra stream (0xA7) of the canonical set `cs`."""
     n = cs.n
     origin = tuple(cs.bounds.lo)
     if n == 0:
@@ -356,21 +724,162 @@ def _payloads(data, levels):
     return buf, dict(zip(coded, offsets)), np.asarray(raw if raw else [1], dtype=np.int32), raw_at
 
 
+def _decode_inter(hdr, data, dev, rs, as_set, timings):
+    """The decoder of an inter stream (0xA8).  The levels above the blocks run as in `decode_geometry`; once the blocks are
+    known the vectors are decoded (or uploaded), the predicted pyramids are built from the reference, and every level from
+    there on draws `present` and the prediction byte from them.  Sizes come from the header alone (the pyramids from the block
+    level's node count), so there is still ONE device->host read, at the end; it also carries the vector list's rANS status and
+    range check and both class histograms of every inter level.  A wrong reference or a damaged payload can only give wrong
+    keys inside the cube until that read."""
+    n, depth, origin, first, search = hdr["n"], hdr["depth"], hdr["origin"], hdr["first"], hdr["search"]
+    bl = depth - first
+    k_vec = (2 * search + 1) ** 3
+    lib = L.load()
+    hw, hwi = lib.pcc_geom_hist_words(), lib.pcc_geom_inter_hist_words()
+    levels, vh = hdr["levels"], hdr["vectors"]
+    ph = _Phases(timings is not None)
+    with torch.cuda.device(dev):
+        ph.mark("start")
+        coded = [l for l, lv in enumerate(levels) if not lv["raw"]]
+        spans = [levels[l]["payload"] for l in coded] + ([] if vh["raw"] else [vh["payload"]])
+        h_buf, offsets = R.stage(data, spans)
+        where = dict(zip(coded + ["vec"], offsets))
+        raw_at, raw = {}, []
+        for l, lv in enumerate(levels):
+            if lv["raw"]:
+                raw_at[l] = len(raw)
+                raw.extend(data[lv["payload"][0]:lv["payload"][1]])
+        raw_at["vec"] = len(raw)
+        raw.extend(data[vh["payload"][0]:vh["payload"][1]] if vh["raw"] and k_vec > 1 else [0] * (levels[first]["nodes"] if vh["raw"] else 1))
+        d_buf, d_raw = torch.from_numpy(h_buf).to(dev), torch.from_numpy(np.asarray(raw, dtype=np.int32)).to(dev)
+        const = R.fixed_tables("geometry", dev, None, TABLE_SIZES, TABLE_OFFSETS)
+        consti = R.fixed_tables("geometry_inter", dev, None, INTER_SIZES, INTER_OFFSETS)
+        state = torch.zeros(N_ROWS * 256, dtype=torch.int64, device=dev)
+        hist = torch.zeros(first * hw + (depth - first) * hwi, dtype=torch.int32, device=dev)
+        h_at = [l * hw if l < first else first * hw + (l - first) * hwi for l in range(depth)]
+        # per level: status | bad byte | child total (i64) | distinct, off-lattice (i64 x 2); row `depth`: the vector list's status | bad index
+        flags = torch.zeros((depth + 1, 8), dtype=torch.int32, device=dev)
+        tabs = R.Tables(torch.empty((N_CTX, N_SYM + 2), dtype=torch.int32, device=dev), const.sizes, const.offsets,
+                        dec=torch.zeros(lib.pcc_geom_dec_table_bytes(), dtype=torch.uint8, device=dev))
+        tabsi = R.Tables(torch.empty((N_ROWS, INTER_STRIDE), dtype=torch.int32, device=dev), consti.sizes, consti.offsets,
+                         dec=torch.zeros(lib.pcc_geom_inter_dec_table_bytes(), dtype=torch.uint8, device=dev))
+        keys = torch.tensor([_key_of(0, 0, 0)], dtype=torch.int64, device=dev)
+        grid, by_grid = None, []
+        bkeys = bgrid = pred = None
+        nb = levels[first]["nodes"]
+        for l, lv in enumerate(levels):
+            m, pitch, total = lv["nodes"], 1 << (depth - l), lv["children"]
+            fp, hp = flags.data_ptr() + 32 * l, hist.data_ptr() + 4 * h_at[l]
+            if l == first:
+                vp = flags.data_ptr() + 32 * depth
+                if vh["raw"]:
+                    vec = d_raw[raw_at["vec"]:raw_at["vec"] + nb]
+                else:
+                    v_cdf, v_sizes = vector_table(vh["hist"]), np.array([k_vec + 2], dtype=np.int32)
+                    v_const = R.fixed_tables(f"geometry_vectors{k_vec}", dev, None, v_sizes, np.zeros(1, dtype=np.int32))
+                    vt = R.Tables(torch.from_numpy(v_cdf).to(dev), v_const.sizes, v_const.offsets,     # (the header's histogram: host work)
+                                  dec=torch.from_numpy(R._dec_blob(v_cdf, v_sizes)).to(dev))
+                    vec = torch.empty(nb, dtype=torch.int32, device=dev)
+                    R.decode(vt, d_buf.data_ptr() + where["vec"], vh["payload"][1] - vh["payload"][0], torch.zeros(nb, dtype=torch.int32, device=dev),
+                             nb, 1, 1, vh["streams"], vec, vp)
+                bkeys, bgrid = keys, grid
+                pred = torch.empty(nb * lib.pcc_geom_inter_pyramid_words(), dtype=torch.int64, device=dev)
+                L.call("pcc_geom_inter_block_bits", L.ptr(bkeys), nb, bl, *_ref_args(rs), *origin, L.ptr(vec), search, L.ptr(pred), vp + 4,
+                       L.stream())
+                ph.mark("vectors_compensation_ms")
+            if l < first:
+                ctx = torch.empty(m, dtype=torch.int32, device=dev)
+                L.call("pcc_geom_occ_ctx", L.ptr(keys), m, pitch, *S.grid_args(grid), None, 0, None, None, None, None, L.ptr(ctx), L.stream())
+                if lv["raw"]:
+                    sym = d_raw[raw_at[l]:raw_at[l] + m]
+                else:
+                    L.call("pcc_geom_tables", L.ptr(state), (C.c_uint32 * 8)(*lv["pop"]), L.ptr(tabs.cdf), L.ptr(tabs.dec), L.stream())
+                    sym = torch.empty(m, dtype=torch.int32, device=dev)
+                    R.decode(tabs, d_buf.data_ptr() + where[l], lv["payload"][1] - lv["payload"][0], ctx, m, 1, 1, lv["streams"], sym, fp)
+                L.call("pcc_geom_hist", L.ptr(sym), L.ptr(ctx), m, hp, fp + 4, L.stream())
+                L.call("pcc_geom_state_update", L.ptr(state), hp, L.stream())
+                byte = sym
+            else:
+                idx = torch.empty(m, dtype=torch.int32, device=dev)
+                r = torch.empty(m, dtype=torch.int32, device=dev)
+                L.call("pcc_geom_inter_occ_ctx", L.ptr(keys), m, pitch, *S.grid_args(grid), None, 0, None, None, None, L.ptr(bkeys), nb,
+                       *S.grid_args(bgrid), bl, L.ptr(pred), None, None, L.ptr(r), L.ptr(idx), L.stream())
+                if lv["raw"]:
+                    byte = d_raw[raw_at[l]:raw_at[l] + m]
+                    sym = torch.empty(m, dtype=torch.int32, device=dev)
+                    L.call("pcc_geom_inter_map", L.ptr(byte), L.ptr(idx), L.ptr(r), m, 0, L.ptr(sym), fp + 4, L.stream())
+                else:
+                    L.call("pcc_geom_inter_tables", L.ptr(state), (C.c_uint32 * 8)(*lv["pop"]), (C.c_uint32 * 9)(*lv["dist"]), L.ptr(tabsi.cdf),
+                           L.ptr(tabsi.dec), L.stream())
+                    sym = torch.empty(m, dtype=torch.int32, device=dev)
+                    R.decode(tabsi, d_buf.data_ptr() + where[l], lv["payload"][1] - lv["payload"][0], idx, m, 1, 1, lv["streams"], sym, fp)
+                    byte = torch.empty(m, dtype=torch.int32, device=dev)
+                    L.call("pcc_geom_inter_map", L.ptr(sym), L.ptr(idx), L.ptr(r), m, 1, L.ptr(byte), fp + 4, L.stream())
+                L.call("pcc_geom_inter_hist", L.ptr(sym), L.ptr(idx), m, hp, fp + 4, L.stream())
+                L.call("pcc_geom_state_update", L.ptr(state), hp, L.stream())
+                L.call("pcc_geom_state_update", state.data_ptr() + 8 * N_CTX * 256, hp + 4 * N_CTX * 256, L.stream())
+            ph.mark("symbols_ms")
+            off = torch.empty(m + 1, dtype=torch.int32, device=dev)
+            ws = L.workspace(lib.pcc_geom_offsets_ws_bytes(m), dev)
+            L.call("pcc_geom_child_offsets", L.ptr(byte), m, L.ptr(off), fp + 8, fp + 4, L.ptr(ws), ws.numel(), L.stream())
+            child = torch.full((total,), _key_of(0, 0, 0), dtype=torch.int64, device=dev)
+            L.call("pcc_geom_expand", L.ptr(keys), L.ptr(byte), L.ptr(off), m, pitch >> 1, L.ptr(child), total, L.stream())
+            keys, grid = _canonical_children(child, total, pitch >> 1, l + 1, dev, fp + 16)
+            by_grid.append(grid is not None)
+            ph.mark("expand_canonical_ms")
+        xyz = torch.empty((n, 3), dtype=torch.int32, device=dev)
+        akeys = torch.empty(n, dtype=torch.int64, device=dev) if as_set else None
+        L.call("pcc_geom_finish", L.ptr(keys), n, origin[0], origin[1], origin[2], L.ptr(akeys), L.ptr(xyz), L.stream())
+        cls = [hist[h_at[l] + (N_CTX * 256 if l < first else N_ROWS * 256):h_at[l] + (hw if l < first else hwi)] for l in range(depth)]
+        parts = [flags.reshape(-1)] + cls
+        if as_set:
+            parts += [xyz.amin(dim=0), xyz.amax(dim=0)]
+        back = torch.cat(parts).cpu().numpy()                                  # the decode's one device->host read
+        ph.mark("finish_read_ms")
+        fl = back[:8 * (depth + 1)].reshape(depth + 1, 8)
+        p = 8 * (depth + 1)
+        if fl[depth, 0] != 0 or fl[depth, 1] != 0:
+            raise L.PccError(f"geometry stream: malformed vector list (status {int(fl[depth, 0])}, index out of range {int(fl[depth, 1])})")
+        for l, lv in enumerate(levels):
+            width = 8 if l < first else 17
+            got, p = [int(v) for v in back[p:p + width]], p + width
+            total, distinct, off_lattice = (int(v) for v in fl[l, 2:8].view(np.int64))
+            if fl[l, 0] != 0:
+                raise L.PccError(f"geometry stream: malformed rANS container in level {l} (status {int(fl[l, 0])})")
+            if fl[l, 1] != 0 or total != lv["children"]:
+                raise L.PccError(f"geometry stream: level {l} decodes to {total} children, the header gives {lv['children']}")
+            if not lv["raw"] and got != [int(v) for v in lv["pop"]] + [int(v) for v in lv.get("dist", [])]:
+                raise L.PccError(f"geometry stream: level {l} does not decode to its class histograms")
+            if by_grid[l] and (off_lattice or distinct != lv["children"]):
+                raise L.PccError(f"geometry stream: level {l} expands to {distinct} distinct cells, the header gives {lv['children']}")
+        if timings is not None:
+            torch.cuda.synchronize(dev)
+            timings["inter"] = ph.report()
+            timings["host_reads_by_construction"] = 1
+        if not as_set:
+            return xyz
+        lo_hi = back[p:].reshape(2, 3).tolist()
+        return S.CoordSet(akeys, n, 1, S.Bounds(0, lo_hi[0], lo_hi[1]), on_lattice=True)
+
+
 @torch.no_grad()
-def decode_geometry(data, device, as_set=False, timings=None):
+def decode_geometry(data, device, as_set=False, reference=None, timings=None):
     """bytes -> int32 [n, 3] rows (x, y, z) in canonical order on `device`; as_set=True: the canonical pitch-1 CoordSet
     instead (no caller re-sorts).  Raises PccError on a malformed stream; never returns anything but exactly the header's n
-    rows.
+    rows.  reference: the cloud an inter stream (0xA8) was coded against (same kinds of input as `encode_geometry` takes);
+    an intra stream ignores it, an inter stream without one is refused.
 
     Every buffer and launch is sized by what `parse_header` derived on the host (each level's nodes <= children <= n); the
     tables are derived on the device from the histograms the kernels leave there (`pcc_geom_tables`), so no level waits for
     the host.  What the payload decodes to -- rANS status, bytes outside 1..255, every level's child total and popcount
     histogram, the canonicalisation's row count -- is compared with the header's figures in ONE read at the end; until then
     a damaged payload can only produce wrong keys inside the level's cube, never a write past a buffer."""
-    hdr = parse_header(data)
+    hdr = parse_header(data, have_reference=reference is not None)
     dev = torch.device(device)
     if dev.type != "cuda":
         raise L.PccError("decode_geometry runs on a GPU (no CPU fallback)")
+    if hdr.get("inter"):
+        return _decode_inter(hdr, data, dev, reference_set(reference, "decode_geometry"), as_set, timings)
     n, depth, origin = hdr["n"], hdr["depth"], hdr["origin"]
     if n == 0:
         empty = torch.empty((0, 3), dtype=torch.int32, device=dev)
@@ -452,3 +961,29 @@ def decode_geometry(data, device, as_set=False, timings=None):
             return xyz
         lo_hi = back[16 * depth:].reshape(2, 3).tolist()
         return S.CoordSet(akeys, n, 1, S.Bounds(0, lo_hi[0], lo_hi[1]), on_lattice=True)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# sequences: frame i against frame i - 1
+# ------------------------------------------------------------------------------------------------------------------------
+def encode_sequence(frames, intra_period=32, mode="auto", segment_nodes=SEGMENT_NODES):
+    """One stream per frame: frame i is coded against frame i - 1, every `intra_period`-th frame (0, intra_period, ...) without a
+    reference.  The coder is lossless, so the decoder's previous frame is the encoder's.  mode as in `encode_geometry`."""
+    if int(intra_period) < 1:
+        raise L.PccError(f"encode_sequence: intra_period {intra_period} must be at least 1")
+    out, prev = [], None
+    for i, frame in enumerate(frames):
+        cs = _input_set(frame)
+        ref = None if i % int(intra_period) == 0 else prev
+        out.append(encode_geometry(cs, segment_nodes=segment_nodes, reference=ref, mode=mode))
+        prev = cs
+    return out
+
+
+def decode_sequence(streams, device, as_set=False):
+    """The frames of `encode_sequence`, in order: int32 [n, 3] tensors, or canonical CoordSets with as_set=True."""
+    out, prev = [], None
+    for data in streams:
+        prev = decode_geometry(data, device, as_set=True, reference=prev)
+        out.append(prev if as_set else prev.coords()[:, 1:].contiguous())
+    return out

@@ -157,6 +157,17 @@ SIGNATURES = {
     "pcc_geom_dec_table_bytes": (_i64, []),
     "pcc_geom_tables": (C.c_int, [_p, C.POINTER(C.c_uint32), _p, _p, _p]),
     "pcc_geom_state_update": (C.c_int, [_p, _p, _p]),
+    "pcc_geom_inter_pyramid_words": (_i32, []),
+    "pcc_geom_inter_candidates": (_i32, [_i32, _p]),
+    "pcc_geom_inter_block_bits": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _p, _p, _i32, _i32, _i32, _p, _i32, _p, _p, _p]),
+    "pcc_geom_inter_motion": (C.c_int, [_p, _i64, _i32, _p, _p, _i64, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p]),
+    "pcc_geom_inter_occ_ctx": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _i64, _p, _p, _p, _i32, _p, _p, _p, _p, _p,
+                                         _p]),
+    "pcc_geom_inter_map": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p]),
+    "pcc_geom_inter_hist_words": (_i32, []),
+    "pcc_geom_inter_hist": (C.c_int, [_p, _p, _i64, _p, _p, _p]),
+    "pcc_geom_inter_dec_table_bytes": (_i64, []),
+    "pcc_geom_inter_tables": (C.c_int, [_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _p, _p, _p]),
     "pcc_raht_isqrt": (_u64, [_u64]),
     "pcc_raht_butterfly": (C.c_int, [C.c_uint32, C.c_uint32, _i64, _i64, C.POINTER(_i64)]),
     "pcc_raht_prepare": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p]),

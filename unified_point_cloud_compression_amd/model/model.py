@@ -376,31 +376,37 @@ class UnifiedModel(CompressionModel):
 
     # ---- lossless geometry, lossy colour: the voxels travel in a geometry stream of their own ---------
     @torch.no_grad()
-    def compress_lossless_geometry(self, pointcloud, q, block_size=1024):
+    def compress_lossless_geometry(self, pointcloud, q, block_size=1024, reference=None):
         """-> (strings, shapes, geometry, q_vals), one entry per block of `partition`: the latents' strings as `compress` codes
         them and `geometry[i]` = `encode_geometry` of the block's input set.  Neither k nor the latent coordinates are
-        returned: `decompress_lossless_geometry` derives both from the decoded voxels."""
-        from ..geometry import encode_geometry
+        returned: `decompress_lossless_geometry` derives both from the decoded voxels.  reference: a voxel cloud the decoder
+        holds too (the previous frame); every block's geometry is coded against the whole of it where that is shorter."""
+        from ..geometry import encode_geometry, reference_set
         if not pointcloud.is_cuda:
             raise L.PccError("compress_lossless_geometry expects the point cloud on the GPU")
+        if reference is not None:                      # canonical once, not once per block
+            reference = reference_set(reference, "compress_lossless_geometry") or reference
         strings, shapes, geometry, q_vals = [], [], [], []
         for x_block in self.blocks_of(pointcloud, block_size):
             sets = []
             symbols, shape, _, _ = self.compress_block(x_block, q, sets=sets)
             strings.append(symbols)
             shapes.append(shape)
-            geometry.append(encode_geometry(sets[-1]))
+            geometry.append(encode_geometry(sets[-1], reference=reference))
             q_vals.append(q)
         return strings, shapes, geometry, q_vals
 
     @torch.no_grad()
-    def decompress_lossless_geometry(self, strings, shape, geometry, q_vals):
-        """-> [N, 6]: per block its unique input voxels in canonical order with the decoded colours.  The voxel set is
+    def decompress_lossless_geometry(self, strings, shape, geometry, q_vals, reference=None):
+        """-> [N, 6]: per block its unique input voxels in canonical order with the decoded colours (reference: the cloud
+        `compress_lossless_geometry` was given).  The voxel set is
         decoded, its stride-2, -4, -8 (y's) and -32 (z's) sets are taken from it, the entropy model runs exactly as in
         `decompress`, and the synthesis runs at the given geometry (`SparseSynthesisTransform.forward_at`) under the same
         range guard: when it trips, g_s alone is evaluated again in the six-term form."""
-        from ..geometry import decode_geometry, parse_header
+        from ..geometry import decode_geometry, parse_header, reference_set
         device = self.g_s.down_conv.kernel.device
+        if reference is not None:
+            reference = reference_set(reference, "decompress_lossless_geometry") or reference
         status, blocks, latents = [], [], []
         for i, (block_symbols, block_shape, geom) in enumerate(zip(strings, shape, geometry)):
             # (the stride-32 set cannot have more rows than there are voxels: a shape that says otherwise is refused before
@@ -409,7 +415,7 @@ class UnifiedModel(CompressionModel):
             if not 0 <= int(block_shape[0]) <= n_vox:
                 raise L.PccError(f"bitstream says {int(block_shape[0])} hyper-latent rows for {n_vox} voxels")
             pre = self.entropy_model.predecode(block_symbols, block_shape, device, check=status)
-            x_cset = decode_geometry(geom, device, as_set=True)
+            x_cset = decode_geometry(geom, device, as_set=True, reference=reference)
             chain = x_cset.stride_chain_begin((2, 4, 8, 32))
             if chain is not None:
                 S.resolve(chain)
