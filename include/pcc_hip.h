@@ -794,6 +794,56 @@ int pcc_lift_finish(const int32_t* values, int64_t n, int32_t channels, int32_t 
                     void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 8f-3e inter frames of the lossless attribute coder (DESIGN.md section 7i "Inter frames", stream 0xB6): the LAST level (nodes
+ *       at pitch 2, children = the voxels) may predict a child from its match in a reference cloud instead of from the level.
+ *       Blocks: the nodes of level max(0, depth - 4) of the current cloud (block_keys origin-relative, block_log2 = depth - that
+ *       level, 1..4; block_bits / block_rank / h_block their grid index at pitch 2^block_log2, or NULLs: binary search), vec the
+ *       vector index per block as pcc_geom_inter_motion gives it.  The reference: canonical pitch-1 keys in ABSOLUTE
+ *       coordinates (n_ref == 0: empty) with its grid index or NULLs, and ref_values int32 [n_ref, channels] from
+ *       pcc_lift_prepare.  d_flag: device int32 zeroed by the caller; bit 0 is set by a block row, a vector index, a mode or a
+ *       match outside its range (counted as vector 0 / mode 0 / unmatched) and by the clamps of pcc_lift_inverse.
+ * pcc_lift_inter_match     match[i] of voxel i (voxel_keys origin-relative, origin ox, oy, oz): with its block's vector d the
+ *                          reference row at p - d, else at the first occupied of the 26 cells around it ordered by
+ *                          (|o|^2, 9 (ox + 1) + 3 (oy + 1) + (oz + 1)), else -1.
+ * pcc_lift_inter_residual  after pcc_lift_forward: rows of the level -= Hp of the spatial prediction (what pcc_lift_residual
+ *                          does) and coef_t [rows_total - row_base, channels] = H - Hp of the temporal prediction (a matched
+ *                          child: ref_values of its match; an unmatched one: the spatial prediction); sums [n_blocks, 2] int32
+ *                          (cleared here) += sum |symbol| of the spatial / temporal rows of the block's nodes.  A level without
+ *                          rows (rows_total == row_base: every voxel alone in its cell) is legal here and in
+ *                          pcc_lift_inter_select: nothing is written but the zero sums, coef_t may be NULL.
+ * pcc_lift_inter_select    sums != NULL: mode[b] = sums[b, 1] < sums[b, 0] first.  Then idx of the level's rows: group
+ *                          (level + mode) * 6 + 3 * (channel > 0) + stage, or side[group] & 63; coef / coef_t given (together):
+ *                          the rows of mode-1 blocks are copied from coef_t into coef.  mask / off as for pcc_raht_index.
+ * pcc_lift_inter_inverse   pcc_lift_inverse with predict != 0 for this level, the children of a mode-1 block's nodes predicted as
+ *                          in pcc_lift_inter_residual.
+ * ---------------------------------------------------------------------------------------- */
+int pcc_lift_inter_match(const int64_t* voxel_keys, int64_t n, const int64_t* block_keys, int64_t n_blocks,
+                         const uint64_t* block_bits, const int32_t* block_rank, const int32_t* h_block, int32_t block_log2,
+                         const int32_t* vec, int32_t search, const int64_t* ref_keys, int64_t n_ref, const uint64_t* ref_bits,
+                         const int32_t* ref_rank, const int32_t* h_ref, int32_t ox, int32_t oy, int32_t oz, int32_t* match,
+                         int32_t* d_flag, void* stream);
+int pcc_lift_inter_residual(const int64_t* keys, int64_t n, int32_t pitch, const uint64_t* bits, const int32_t* rank,
+                            const int32_t* h_grid, const int64_t* child_keys, int64_t n_child, const uint64_t* child_bits,
+                            const int32_t* child_rank, const int32_t* h_child, const int64_t* block_keys, int64_t n_blocks,
+                            const uint64_t* block_bits, const int32_t* block_rank, const int32_t* h_block, int32_t block_log2,
+                            const int32_t* off, const int32_t* v, int32_t channels, const int32_t* match,
+                            const int32_t* ref_values /*nullable when n_ref == 0*/, int64_t n_ref, int32_t* coef, int32_t* coef_t,
+                            int64_t row_base, int64_t rows_total, int32_t* sums, int32_t* d_flag, void* stream);
+int pcc_lift_inter_select(const int64_t* keys, const int32_t* mask, const int32_t* off, int64_t n, int32_t level,
+                          int32_t channels, const int64_t* block_keys, int64_t n_blocks, const uint64_t* block_bits,
+                          const int32_t* block_rank, const int32_t* h_block, int32_t block_log2, const int32_t* sums /*nullable*/,
+                          int32_t* mode, const int32_t* side /*nullable*/, int32_t* idx, int32_t* coef /*nullable*/,
+                          const int32_t* coef_t /*nullable*/, int64_t row_base, int64_t rows_total, int32_t* d_flag, void* stream);
+int pcc_lift_inter_inverse(const int64_t* keys, int64_t n, int32_t pitch, const uint64_t* bits, const int32_t* rank,
+                           const int32_t* h_grid, const int64_t* child_keys, int64_t n_child, const uint64_t* child_bits,
+                           const int32_t* child_rank, const int32_t* h_child, const int64_t* block_keys, int64_t n_blocks,
+                           const uint64_t* block_bits, const int32_t* block_rank, const int32_t* h_block, int32_t block_log2,
+                           const int32_t* mode, const int32_t* off, const int32_t* v, int32_t channels, int32_t colour,
+                           const int32_t* match, const int32_t* ref_values /*nullable when n_ref == 0*/, int64_t n_ref,
+                           const int32_t* coef, int64_t row_base, int64_t rows_total, int32_t* child_v, int32_t* d_flag,
+                           void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * 8f-4  nearest-neighbour association of the distortion report (replaces the two Open3D KD-trees and the per-point
  *       Python loop of PointCloudMetric.__init__, metrics/metric.py:36-43).  Exact, integer coordinates.
  *       a_xyz [n_a,3] int32 queries (any order; canonical order is fastest); b_xyz [n_b,3] int32 SORTED BY x ascending

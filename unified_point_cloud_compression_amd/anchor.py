@@ -13,6 +13,9 @@ their mean colour (`voxelize.voxel_grid`); the lossless octree (`geometry.encode
 lossless colour coder (`attributes.encode_attributes_lossless`), no scaling and no merging.
 
     container = u8 0xC2 | u32 len_geometry | geometry stream | attribute stream
+
+Both parts may be coded against a reference cloud the decoder holds (the previous frame): `compress_lossless(reference=,
+attributes=)`, and `compress_lossless_sequence` / `decompress_lossless_sequence` chain whole frames that way.
 """
 import math
 import struct
@@ -21,7 +24,7 @@ import torch
 
 from . import lib as L
 from . import sparse as S
-from .attributes import decode_attributes, decode_attributes_lossless, encode_attributes, encode_attributes_lossless
+from .attributes import INTER_MAGIC, decode_attributes, decode_attributes_lossless, encode_attributes, encode_attributes_lossless
 from .geometry import decode_geometry, encode_geometry
 from .voxelize import voxel_grid
 
@@ -109,13 +112,23 @@ def parse_lossless_container(data):
     return bytes(data[LOSSLESS_HEADER.size:LOSSLESS_HEADER.size + len_g]), bytes(data[LOSSLESS_HEADER.size + len_g:])
 
 
+def _has_colours(reference):
+    return torch.is_tensor(reference) and reference.dim() == 2 and reference.shape[1] == 6
+
+
 @torch.no_grad()
-def compress_lossless(cloud, reference=None):
+def compress_lossless(cloud, reference=None, attributes="intra"):
     """[N, 6] GPU cloud of distinct voxels (integer xyz, rgb in [0, 1]: colours become round(255 c)) -> bytes from which
     `decompress_lossless` returns the same voxels with the same levels.  Non-integer coordinates and repeated voxels raise
     PccError: voxelise first (`voxelize.voxel_grid`).  reference: a voxel cloud (its first three columns) the decoder holds
-    too, e.g. the previous frame: the geometry is coded against it where that is shorter; colour stays intra."""
+    too, e.g. the previous frame: the geometry is coded against it where that is shorter.  attributes: "intra" -- the colours
+    ignore the reference; "auto" / "inter" -- the mode of `attributes.encode_attributes_lossless`, which then needs an [M, 6]
+    reference of distinct voxels and codes the colours against its colours."""
     what = "compress_lossless"
+    if attributes not in ("auto", "inter", "intra"):
+        raise L.PccError(f"{what}: attributes {attributes!r} is not one of auto, inter, intra")
+    if attributes != "intra" and not _has_colours(reference):
+        raise L.PccError(f"{what}: attributes={attributes!r} needs an [M, 6] reference cloud (xyz, rgb in [0, 1])")
     if not torch.is_tensor(cloud) or cloud.dim() != 2 or cloud.shape[1] != 6 or cloud.shape[0] == 0:
         raise L.PccError(f"{what}: a non-empty [N, 6] cloud (xyz, rgb in [0, 1]) is required")
     if not cloud.is_cuda:
@@ -130,16 +143,50 @@ def compress_lossless(cloud, reference=None):
     levels = torch.round(cloud[:, 3:6].to(torch.float64) * 255.0).clamp_(0, 255).to(torch.uint8)
     levels = (levels if perm is None else levels[perm]).contiguous()
     geometry = encode_geometry(cs, reference=reference)
-    attributes = encode_attributes_lossless(cs, attrs=levels)
-    return LOSSLESS_HEADER.pack(LOSSLESS_MAGIC, len(geometry)) + geometry + attributes
+    if attributes == "intra":
+        colours = encode_attributes_lossless(cs, attrs=levels)
+    else:
+        colours = encode_attributes_lossless(cs, attrs=levels, reference=reference, mode=attributes)
+    return LOSSLESS_HEADER.pack(LOSSLESS_MAGIC, len(geometry)) + geometry + colours
 
 
 @torch.no_grad()
 def decompress_lossless(data, device, reference=None):
     """bytes -> [n, 6] float32 on `device` in canonical order: the exact coordinates, colours level / 255 (round(255 c) of
-    them gives the levels back).  reference: the cloud `compress_lossless` was given."""
+    them gives the levels back).  reference: the cloud `compress_lossless` was given; a stream whose colours are coded against
+    it (magic byte 0xB6 of the attribute part) raises PccError when the reference has no colours."""
     geometry, attributes = parse_lossless_container(data)
+    inter = len(attributes) > 0 and attributes[0] == INTER_MAGIC
+    if inter and not _has_colours(reference):
+        raise L.PccError("decompress_lossless: the colours are coded against a reference; an [M, 6] reference cloud is required")
     cs = decode_geometry(geometry, device, as_set=True, reference=reference)
-    levels = decode_attributes_lossless(attributes, cs)
+    levels = decode_attributes_lossless(attributes, cs, reference=reference if inter else None)
     rgb = levels.to(torch.float64) / torch.tensor(255.0, dtype=torch.float64, device=cs.device)
     return torch.cat([cs.coords()[:cs.n, 1:].to(torch.float64), rgb], dim=1).to(torch.float32)
+
+
+@torch.no_grad()
+def compress_lossless_sequence(frames, intra_period=32):
+    """Frames ([N, 6] clouds as for `compress_lossless`) -> one stream per frame: frame i is coded on its own when
+    i % intra_period == 0, else against frame i - 1 with geometry and colour both "auto" (lossless: the decoder holds the same
+    frame).  Every stream decodes with `decompress_lossless(stream, device, reference=previous frame)`."""
+    if int(intra_period) < 1:
+        raise L.PccError(f"compress_lossless_sequence: intra_period {intra_period} is not positive")
+    out, prev = [], None
+    for i, frame in enumerate(frames):
+        if i % int(intra_period) == 0:
+            out.append(compress_lossless(frame))
+        else:
+            out.append(compress_lossless(frame, reference=prev, attributes="auto"))
+        prev = frame
+    return out
+
+
+@torch.no_grad()
+def decompress_lossless_sequence(streams, device):
+    """The streams of `compress_lossless_sequence` -> the frames, each [n, 6] float32 in canonical order."""
+    out, prev = [], None
+    for data in streams:
+        prev = decompress_lossless(data, device, reference=prev)
+        out.append(prev)
+    return out

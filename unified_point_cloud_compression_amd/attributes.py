@@ -27,6 +27,9 @@ over the same levels, rows, groups, family and container with a reversible arith
     stream = u8 0xB5 | u32 n | u8 depth | u8 C | u8 flags (bit 0: YCoCg-R, bit 1: prediction, bit 2: stored)
              | C zig-zag varints (root values) | depth x 6 side bytes | u32 length | rANS container
     stored:  u8 0xB5 | u32 n | u8 depth | u8 C | u8 4 | n x C raw levels in canonical order
+    inter:   u8 0xB6 | u32 n | u8 depth | u8 C | u8 flags (bit 1, and bit 0 for YCoCg-R) | u8 block_log2 | u8 search | u32 blocks
+             | C zig-zag varints | (depth + 1) x 6 side bytes | ceil(blocks / 8) mode bytes (block b: bit b & 7 of byte b >> 3)
+             | u32 length | rANS container            (coded against a reference cloud the decoder holds; no vector travels)
 """
 import ctypes as C
 import struct
@@ -436,6 +439,9 @@ LOSSLESS_MAGIC = 0xB5      # format version 1
 LOSSLESS_HEADER = struct.Struct("<BIBBB")
 F_COLOUR, F_PREDICT, F_STORED = 1, 2, 4
 SYMBOL_LIMIT = 1023        # the decoder's clamp on a symbol; a valid one is within +-1020
+INTER_MAGIC = 0xB6         # inter frames, format version 1: the last level may be predicted from a reference cloud
+INTER_HEADER = struct.Struct("<BIBBBBBI")
+INTER_MAX_DEPTH = 14       # (depth + 1) * 6 groups within the 90 of pcc_raht_hist
 
 
 def channel_ranges(channels, colour):
@@ -443,12 +449,80 @@ def channel_ranges(channels, colour):
     return [(0, 255)] + [(-255, 255) if colour else (0, 255)] * (channels - 1)
 
 
-def parse_lossless_header(data):
+def _root_values(data, at, n, channels, colour, name):
+    """(root value per channel, the offset behind them) of the zig-zag varints at `at`, each inside its channel's range."""
+    root = []
+    for c, (lo, hi) in enumerate(channel_ranges(channels, colour)):
+        u, sh = 0, 0
+        while True:
+            if at >= len(data) or sh > 14:
+                raise L.PccError(f"{name} truncated inside the root values")
+            b = data[at]
+            at += 1
+            u |= (b & 0x7F) << sh
+            sh += 7
+            if not b & 0x80:
+                break
+        q = (u >> 1) if not u & 1 else -((u + 1) >> 1)
+        if not lo <= q <= hi or (n == 0 and q):
+            raise L.PccError(f"{name}: root value {q} of channel {c} outside {lo}..{hi}")
+        root.append(q)
+    return root, at
+
+
+def _parse_inter_header(data, have_reference):
+    """The 0xB6 half of `parse_lossless_header`."""
+    name = "inter lossless attribute stream"
+    if not have_reference:
+        raise L.PccError(f"{name}: the stream is coded against a reference cloud and none was given")
+    if len(data) < INTER_HEADER.size:
+        raise L.PccError(f"{name} truncated inside the header")
+    _, n, depth, ch, flags, block_log2, search, blocks = INTER_HEADER.unpack_from(data, 0)
+    if not 1 <= ch <= MAX_C:
+        raise L.PccError(f"{name}: {ch} channels outside 1..{MAX_C}")
+    if flags not in (F_PREDICT, F_PREDICT | F_COLOUR) or (flags & F_COLOUR and ch != 3):
+        raise L.PccError(f"{name}: flags {flags:#x} with {ch} channels")
+    if block_log2 != G.BLOCK_LOG2 or search != G.SEARCH:
+        raise L.PccError(f"{name}: block_log2 {block_log2}, search {search}; this build reads {G.BLOCK_LOG2} and {G.SEARCH}")
+    if not 2 <= n < MAX_POINTS:
+        raise L.PccError(f"{name}: header claims {n} points, an inter stream codes 2 .. 2^26 - 1")
+    if not 1 <= depth <= INTER_MAX_DEPTH or n > 8 ** min(depth, 10):
+        raise L.PccError(f"{name}: header claims {n} points at depth {depth} (inter streams exist up to depth {INTER_MAX_DEPTH})")
+    if not 1 <= blocks <= n:
+        raise L.PccError(f"{name}: header claims {blocks} blocks for {n} points")
+    colour = bool(flags & F_COLOUR)
+    root, at = _root_values(data, INTER_HEADER.size, n, ch, colour, name)
+    groups = (depth + 1) * 6
+    if at + groups > len(data):
+        raise L.PccError(f"{name} truncated inside the side bytes")
+    side = list(data[at:at + groups])
+    at += groups
+    if max(side) >= N_TABLES:
+        raise L.PccError(f"{name}: side byte {max(side)} names no table (64 members)")
+    mbytes = (blocks + 7) // 8
+    if at + mbytes > len(data):
+        raise L.PccError(f"{name} truncated inside the mode bytes")
+    if blocks % 8 and data[at + mbytes - 1] >> (blocks % 8):
+        raise L.PccError(f"{name}: padding bits of the mode bytes are set")
+    hdr = {"n": n, "depth": depth, "channels": ch, "colour": colour, "predict": True, "stored": False, "root": root, "side": side,
+           "payload": None, "streams": 0, "raw": None, "inter": True, "block_log2": block_log2, "search": search, "blocks": blocks,
+           "modes": (at, at + mbytes)}
+    hdr["payload"], hdr["streams"] = _container_span(data, at + mbytes, (n - 1) * ch, name)
+    if hdr["payload"][1] != len(data):
+        raise L.PccError(f"{name}: trailing bytes")
+    return hdr
+
+
+def parse_lossless_header(data, have_reference=True):
     """{n, depth, channels, colour, predict, stored, root (per channel), side (depth * 6 members), payload=(begin, end) or None,
-    streams, raw=(begin, end) or None}.  Raises PccError on a bad magic byte, an unknown flag, the colour flag without three
-    channels, channels, n or depth out of range, a root outside its channel's range, a side byte that names no table,
+    streams, raw=(begin, end) or None, inter}.  Raises PccError on a bad magic byte, an unknown flag, the colour flag without
+    three channels, channels, n or depth out of range, a root outside its channel's range, a side byte that names no table,
     truncation, trailing bytes, a container length that disagrees with the data and a stored body of the wrong size --
-    before any GPU work."""
+    before any GPU work.  An inter stream (0xB6) has inter=True, (depth + 1) * 6 side bytes and block_log2, search, blocks,
+    modes=(begin, end) besides; refused for it as well: a block size or search range other than this build's, depth > 14,
+    n < 2, a block count of 0 or above n, set padding bits of the mode bytes, and have_reference=False."""
+    if len(data) and data[0] == INTER_MAGIC:
+        return _parse_inter_header(data, have_reference)
     if len(data) < LOSSLESS_HEADER.size:
         raise L.PccError("lossless attribute stream truncated inside the header")
     magic, n, depth, ch, flags = LOSSLESS_HEADER.unpack_from(data, 0)
@@ -464,28 +538,14 @@ def parse_lossless_header(data):
         raise L.PccError(f"lossless attribute stream: header claims {n} points at depth {depth}")
     colour = bool(flags & F_COLOUR)
     hdr = {"n": n, "depth": depth, "channels": ch, "colour": colour, "predict": bool(flags & F_PREDICT), "stored": bool(flags & F_STORED),
-           "root": [], "side": [], "payload": None, "streams": 0, "raw": None}
+           "root": [], "side": [], "payload": None, "streams": 0, "raw": None, "inter": False}
     at = LOSSLESS_HEADER.size
     if hdr["stored"]:
         if len(data) != at + n * ch:
             raise L.PccError(f"lossless attribute stream: a stored body of {len(data) - at} bytes for {n} x {ch} levels")
         hdr["raw"] = (at, at + n * ch)
         return hdr
-    for c, (lo, hi) in enumerate(channel_ranges(ch, colour)):
-        u, sh = 0, 0
-        while True:
-            if at >= len(data) or sh > 14:
-                raise L.PccError("lossless attribute stream truncated inside the root values")
-            b = data[at]
-            at += 1
-            u |= (b & 0x7F) << sh
-            sh += 7
-            if not b & 0x80:
-                break
-        q = (u >> 1) if not u & 1 else -((u + 1) >> 1)
-        if not lo <= q <= hi or (n == 0 and q):
-            raise L.PccError(f"lossless attribute stream: root value {q} of channel {c} outside {lo}..{hi}")
-        hdr["root"].append(q)
+    hdr["root"], at = _root_values(data, at, n, ch, colour, "lossless attribute stream")
     if at + depth * 6 > len(data):
         raise L.PccError("lossless attribute stream truncated inside the side bytes")
     hdr["side"] = list(data[at:at + depth * 6])
@@ -508,15 +568,84 @@ def _node_level_args(node, child, root):
             *S.grid_args(child.grid() if S.USE_GRID else None))
 
 
+def _reference_rows(reference, reference_attrs, channels, predict, what):
+    """(set or None for an empty reference, its uint8 [M, C] levels, the permutation that brings them into the set's order or
+    None) of the reference cloud of an inter stream: an [M, 6] cloud, or a pitch-1 set / [M, >= 3] rows with `reference_attrs`.
+    Refused: the input forms `encode_attributes` refuses, rows that repeat a voxel (their colours would be ambiguous), another
+    channel count than the stream's, and a stream without prediction."""
+    who = f"{what} (reference)"
+    if not predict:
+        raise L.PccError(f"{what}: a reference needs the prediction (predict=True)")
+    cloud, levels = _attribute_rows(reference, reference_attrs, who)
+    if levels.shape[1] != channels:
+        raise L.PccError(f"{who}: {levels.shape[1]} channels, the cloud has {channels}")
+    if (cloud.n if isinstance(cloud, S.CoordSet) else cloud.shape[0]) == 0:
+        return None, None, None
+    rs, perm, keep = G.canonical_rows(cloud, who)
+    if keep is not None:
+        raise L.PccError(f"{who}: {levels.shape[0] - rs.n} rows repeat a voxel; merge them first (voxelize.voxel_grid)")
+    if levels.device != rs.device:
+        raise L.PccError(f"{who}: points and attrs are on different devices")
+    return rs, levels, perm
+
+
+def _inter_state(cs, sets, origin, depth, ref, channels, colour, d_flag):
+    """What both sides of an inter stream recompute from the geometry and the reference: (the block arguments of the
+    pcc_lift_inter_* entry points, the block count, int32 match row per voxel, int32 [M, C] prepared reference values or None,
+    M).  `geometry.motion_vectors` gives the vectors; the tensors the arguments point into live in `sets` and the result."""
+    rs, levels, perm = ref
+    dev = cs.device
+    blocks, bl, _, vec = G.motion_vectors(cs, rs, origin, depth, sets)
+    grid = blocks.grid() if (depth > bl and S.USE_GRID) else None         # the root's single node is searched
+    bargs = (L.ptr(blocks.keys), blocks.n, *S.grid_args(grid), bl)
+    match = torch.empty(cs.n, dtype=torch.int32, device=dev)
+    L.call("pcc_lift_inter_match", L.ptr(sets[depth].keys), cs.n, *bargs, L.ptr(vec), G.SEARCH, *G._ref_args(rs), *origin, L.ptr(match),
+           d_flag, L.stream())
+    if rs is None:
+        return bargs, blocks.n, match, None, 0, (vec, grid)
+    if levels.device != dev:
+        raise L.PccError("the reference is on another device than the cloud")
+    tv = torch.empty((rs.n, channels), dtype=torch.int32, device=dev)
+    L.call("pcc_lift_prepare", L.ptr(levels), L.ptr(perm), rs.n, channels, int(colour), L.ptr(tv), L.stream())
+    return bargs, blocks.n, match, tv, rs.n, (vec, grid)
+
+
+def _rans_body(coef, idx, symbols, segment_symbols, dev, what, done=None):
+    """`u32 length | rANS container` of the symbol vector; one device->host read (size + container).  done: an event recorded
+    behind the coder's launches."""
+    plan = R.Plan(symbols, 1, 1, segments_for(symbols, segment_symbols))
+    cap = R.align8(plan.capacity)
+    blob = torch.zeros(8 + cap, dtype=torch.uint8, device=dev)
+    R.encode(_tables(dev), plan, coef, idx, blob.data_ptr() + 8, blob.data_ptr())
+    if done is not None:
+        done.record()
+    host = blob.cpu().numpy()
+    nb = int(host[:8].view(np.int64)[0])
+    if not 0 < nb <= cap:
+        raise L.PccError(f"{what}: the coder produced {nb} bytes for a capacity of {cap}")
+    return struct.pack("<I", nb) + host[8:8 + nb].tobytes()
+
+
 @torch.no_grad()
-def encode_attributes_lossless(cloud, colour=True, attrs=None, predict=True, segment_symbols=SEGMENT_SYMBOLS, timings=None):
+def encode_attributes_lossless(cloud, colour=True, attrs=None, predict=True, segment_symbols=SEGMENT_SYMBOLS, timings=None,
+                               reference=None, reference_attrs=None, mode="auto"):
     """The input forms and refusals of `encode_attributes` -> bytes that `decode_attributes_lossless` turns back into the very
     uint8 levels (colours of an [N, 6] cloud become round(255 c) first).  colour: YCoCg-R in front of the lifting (three
     channels only).  predict: code every butterfly against its prediction from the parent level.  When the coded stream would
     be longer than header + n * C bytes, the raw levels are stored instead.  timings: a dict that receives per-stage device
-    events (tools/lossless_timing.py)."""
+    events (tools/lossless_timing.py, tools/lossless_inter_timing.py).
+    reference: a cloud the decoder holds too -- [M, 6], or a pitch-1 set / [M, >= 3] rows with `reference_attrs` uint8 [M, C]
+    in its row order; distinct voxels, the cloud's channel count, predict=True.  mode "auto": the shorter of the inter (0xB6)
+    and the intra (0xB5) stream, intra on a tie and at depth 15 -- never longer than without a reference; "inter": the inter
+    stream (fewer than two voxels still travel as intra; depth 15 raises); "intra", or no reference: today's stream byte for
+    byte."""
     what = "encode_attributes_lossless"
+    if mode not in ("auto", "inter", "intra"):
+        raise L.PccError(f"{what}: mode {mode!r} is not one of auto, inter, intra")
     cloud, levels = _attribute_rows(cloud, attrs, what)
+    ref = None
+    if reference is not None and mode != "intra":                         # "intra" never looks at the reference
+        ref = _reference_rows(reference, reference_attrs, levels.shape[1], bool(predict), what)
     cs, perm, keep = G.canonical_rows(cloud, what)
     if keep is not None:
         raise L.PccError(f"{what}: {levels.shape[0] - cs.n} rows repeat a voxel; merge them first (voxelize.voxel_grid)")
@@ -531,9 +660,20 @@ def encode_attributes_lossless(cloud, colour=True, attrs=None, predict=True, seg
         raise L.PccError(f"{what}: points and attrs are on different devices")
     origin, depth = tuple(cs.bounds.lo), _depth_of(cs)
     rows = n - 1
+    inter = ref is not None and mode != "intra" and n >= 2
+    if inter and depth > INTER_MAX_DEPTH:
+        if mode == "inter":
+            raise L.PccError(f"{what}: inter streams exist up to depth {INTER_MAX_DEPTH}, the cloud has depth {depth}")
+        inter = False
     with torch.cuda.device(dev):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)] if timings is not None else None
+        ph = G._Phases(timings is not None and inter)
         sets = G.level_sets(cs, origin, depth)
+        if inter:
+            ph.mark("start")
+            d_flag = torch.zeros(1, dtype=torch.int32, device=dev)
+            bargs, nb, match, tv, nr, _keep = _inter_state(cs, sets, origin, depth, ref, ch, colour, L.ptr(d_flag))
+            ph.mark("motion_match_ms")
         if ev:
             ev[0].record()
         values = torch.empty((n, ch), dtype=torch.int32, device=dev)
@@ -550,67 +690,110 @@ def encode_attributes_lossless(cloud, colour=True, attrs=None, predict=True, seg
                    L.ptr(v[l]), L.ptr(coef), sets[l].n - 1, rows, L.stream())
         if ev:
             ev[2].record()
+        last = depth - 1
         if predict and rows:
-            for l in range(depth):
+            for l in range(last if inter else depth):
                 L.call("pcc_lift_residual", *_node_level_args(sets[l], sets[l + 1], l == 0), L.ptr(offs[l]), L.ptr(w[l + 1]), L.ptr(v[l]), ch,
                        L.ptr(coef), sets[l].n - 1, rows, L.stream())
+        if inter:                                                          # the last level: both residual sets, coef as the intra coder's
+            coef_t = torch.empty((rows - (sets[last].n - 1), ch), dtype=torch.int32, device=dev)
+            sums = torch.empty((nb, 2), dtype=torch.int32, device=dev)
+            L.call("pcc_lift_inter_residual", *_node_level_args(sets[last], sets[depth], last == 0), *bargs, L.ptr(offs[last]), L.ptr(v[last]),
+                   ch, L.ptr(match), L.ptr(tv), nr, L.ptr(coef), L.ptr(coef_t), sets[last].n - 1, rows, L.ptr(sums), L.ptr(d_flag), L.stream())
         if ev:
             ev[3].record()
-        parts = [v[0].reshape(-1), checks.reshape(-1)]
-        if rows:
-            idx = torch.empty(rows * ch, dtype=torch.int32, device=dev)
-            hist = torch.empty(depth * 6 * N_SLOTS, dtype=torch.int32, device=dev)
-            _fill_index(masks, offs, sets, depth, ch, None, idx, rows)
-            L.call("pcc_raht_hist", L.ptr(coef), L.ptr(idx), rows * ch, depth * 6, L.ptr(hist), L.stream())
-            parts.append(hist)
-        back = torch.cat(parts).cpu().numpy()                              # one read: root values, the plan's checks, the histograms
-        _check_plan(back[ch:ch + 4 * depth], sets, what)
-        root = [int(back[c]) for c in range(ch)]
-        side = choose_members(back[ch + 4 * depth:]) if rows else [0] * (depth * 6)
-        if ev:
-            ev[4].record()
-        body = b""
-        if rows:
-            d_side = torch.tensor(side, dtype=torch.int32, device=dev)
-            _fill_index(masks, offs, sets, depth, ch, d_side, idx, rows)
-            tabs = _tables(dev)
-            plan = R.Plan(rows * ch, 1, 1, segments_for(rows * ch, segment_symbols))
-            cap = R.align8(plan.capacity)
-            blob = torch.zeros(8 + cap, dtype=torch.uint8, device=dev)
-            R.encode(tabs, plan, coef, idx, blob.data_ptr() + 8, blob.data_ptr())
+        out, stored = None, False
+        if not inter or mode == "auto":
+            parts = [v[0].reshape(-1), checks.reshape(-1)]
+            if rows:
+                idx = torch.empty(rows * ch, dtype=torch.int32, device=dev)
+                hist = torch.empty(depth * 6 * N_SLOTS, dtype=torch.int32, device=dev)
+                _fill_index(masks, offs, sets, depth, ch, None, idx, rows)
+                L.call("pcc_raht_hist", L.ptr(coef), L.ptr(idx), rows * ch, depth * 6, L.ptr(hist), L.stream())
+                parts.append(hist)
+            back = torch.cat(parts).cpu().numpy()                          # one read: root values, the plan's checks, the histograms
+            _check_plan(back[ch:ch + 4 * depth], sets, what)
+            root = [int(back[c]) for c in range(ch)]
+            side = choose_members(back[ch + 4 * depth:]) if rows else [0] * (depth * 6)
             if ev:
-                ev[5].record()
-            host = blob.cpu().numpy()                                      # one read: size + container
-            nb = int(host[:8].view(np.int64)[0])
-            if not 0 < nb <= cap:
-                raise L.PccError(f"{what}: the coder produced {nb} bytes for a capacity of {cap}")
-            body = struct.pack("<I", nb) + host[8:8 + nb].tobytes()
-        out = bytearray(LOSSLESS_HEADER.pack(LOSSLESS_MAGIC, n, depth, ch, (F_COLOUR if colour else 0) | (F_PREDICT if predict else 0)))
-        for q in root:
-            out += _zigzag(q)
-        out += bytes(side) + body
-        stored = len(out) > LOSSLESS_HEADER.size + n * ch
-        if stored:                                                         # a third read, of the raw levels, in this case alone
-            raw = levels if perm is None else levels[perm]
-            out = LOSSLESS_HEADER.pack(LOSSLESS_MAGIC, n, depth, ch, F_STORED) + raw.cpu().numpy().tobytes()
+                ev[4].record()
+            body = b""
+            if rows:
+                d_side = torch.tensor(side, dtype=torch.int32, device=dev)
+                _fill_index(masks, offs, sets, depth, ch, d_side, idx, rows)
+                body = _rans_body(coef, idx, rows * ch, segment_symbols, dev, what, ev[5] if ev else None)    # one read: size + container
+            out = bytearray(LOSSLESS_HEADER.pack(LOSSLESS_MAGIC, n, depth, ch, (F_COLOUR if colour else 0) | (F_PREDICT if predict else 0)))
+            for q in root:
+                out += _zigzag(q)
+            out += bytes(side) + body
+            stored = len(out) > LOSSLESS_HEADER.size + n * ch
+            if stored:                                                     # a third read, of the raw levels, in this case alone
+                raw = levels if perm is None else levels[perm]
+                out = LOSSLESS_HEADER.pack(LOSSLESS_MAGIC, n, depth, ch, F_STORED) + raw.cpu().numpy().tobytes()
+        if inter:
+            # the select pass: modes from the block sums, the temporal rows of mode-1 blocks into coef, their rows into the groups
+            # of level `depth`; then the members, the member index and the container as above
+            ph.mark("before_select")
+            groups = (depth + 1) * 6
+            node = sets[last]
+            d_mode = torch.empty(nb, dtype=torch.int32, device=dev)
+            idx = torch.empty(rows * ch, dtype=torch.int32, device=dev)
+            hist = torch.empty(groups * N_SLOTS, dtype=torch.int32, device=dev)
+            sel = (L.ptr(node.keys), L.ptr(masks[last]), L.ptr(offs[last]), node.n, last, ch, *bargs)
+            _fill_index(masks, offs, sets, last, ch, None, idx, rows)
+            L.call("pcc_lift_inter_select", *sel, L.ptr(sums), L.ptr(d_mode), None, L.ptr(idx), L.ptr(coef), L.ptr(coef_t), node.n - 1, rows,
+                   L.ptr(d_flag), L.stream())
+            L.call("pcc_raht_hist", L.ptr(coef), L.ptr(idx), rows * ch, groups, L.ptr(hist), L.stream())
+            back = torch.cat([v[0].reshape(-1), checks.reshape(-1), d_flag, d_mode, hist]).cpu().numpy()      # one read
+            _check_plan(back[ch:ch + 4 * depth], sets, what)
+            at = ch + 4 * depth
+            if back[at] != 0:
+                raise L.PccError(f"{what}: the blocks, vectors or matches of the cloud are inconsistent")
+            modes = np.packbits(back[at + 1:at + 1 + nb].astype(bool), bitorder="little").tobytes()
+            side = choose_members(back[at + 1 + nb:])
+            ph.mark("select_hist_choose_ms")
+            d_side = torch.tensor(side, dtype=torch.int32, device=dev)
+            _fill_index(masks, offs, sets, last, ch, d_side, idx, rows)
+            L.call("pcc_lift_inter_select", *sel, None, L.ptr(d_mode), L.ptr(d_side), L.ptr(idx), None, None, node.n - 1, rows, L.ptr(d_flag),
+                   L.stream())
+            body = _rans_body(coef, idx, rows * ch, segment_symbols, dev, what)          # one read: size + container
+            ph.mark("inter_index_rans_ms")
+            coded = bytearray(INTER_HEADER.pack(INTER_MAGIC, n, depth, ch, F_PREDICT | (F_COLOUR if colour else 0), G.BLOCK_LOG2, G.SEARCH, nb))
+            for c in range(ch):
+                coded += _zigzag(int(back[c]))
+            coded += bytes(side) + modes + body
+            if timings is not None:
+                timings["inter_bytes"], timings["intra_bytes"] = len(coded), (len(out) if out is not None else None)
+                timings["mode1_blocks"], timings["blocks"] = int(back[at + 1:at + 1 + nb].sum()), nb
+            if out is None or len(coded) < len(out):
+                out = coded
         if timings is not None:
             torch.cuda.synchronize(dev)
             timings["stages_ms"] = {"prepare_plan": ev[0].elapsed_time(ev[1]), "forward": ev[1].elapsed_time(ev[2]),
-                                    "residual": ev[2].elapsed_time(ev[3]), "index_hist_choose": ev[3].elapsed_time(ev[4]),
-                                    "index_rans": ev[4].elapsed_time(ev[5]) if rows else 0.0}
-            timings["host_reads_by_construction"] = (2 if rows else 1) + int(stored)       # beyond those of building the level sets
-            timings["stored"] = stored
+                                    "residual": ev[2].elapsed_time(ev[3])}
+            if not inter or mode == "auto":
+                timings["stages_ms"].update({"index_hist_choose": ev[3].elapsed_time(ev[4]), "index_rans": ev[4].elapsed_time(ev[5]) if rows else 0.0})
+                timings["host_reads_by_construction"] = (2 if rows else 1) + int(stored)   # beyond those of building the level sets
+                timings["stored"] = stored
+            if inter:
+                timings["inter_stages_ms"] = {k: val for k, val in ph.report().items() if k != "before_select"}
     return bytes(out)
 
 
 @torch.no_grad()
-def decode_attributes_lossless(data, geometry, device=None):
+def decode_attributes_lossless(data, geometry, device=None, reference=None, reference_attrs=None, timings=None):
     """bytes + the block's geometry (the pitch-1 CoordSet `decode_geometry(..., as_set=True)` returns, or [n, >= 3] rows) ->
     uint8 [n, C] in the canonical order `decode_geometry` returns: the levels the encoder was given.  device=None: the
-    geometry's.  Raises PccError on a malformed stream, on a stream whose n or depth differ from the geometry's, and on a
-    payload that does not decode to legal values; never returns anything but exactly [n, C]."""
+    geometry's.  reference, reference_attrs: the reference cloud `encode_attributes_lossless` was given; an inter stream (0xB6)
+    needs it with its colours, an intra stream ignores it.  The decoder re-runs the motion search and the matching on the
+    geometry, compares the header's block count with the geometry's and sizes every buffer from the geometry.  Raises PccError
+    on a malformed stream, on a stream whose n, depth or block count differ from the geometry's, and on a payload that does not
+    decode to legal values; never returns anything but exactly [n, C].  timings: a dict that receives per-stage device events
+    (tools/lossless_inter_timing.py); asking for them adds a synchronisation at the end."""
     what = "decode_attributes_lossless"
-    hdr = parse_lossless_header(data)
+    hdr = parse_lossless_header(data, have_reference=reference is not None)
+    inter = hdr["inter"]
+    ref = _reference_rows(reference, reference_attrs, hdr["channels"], True, what) if inter else None
     if torch.is_tensor(geometry) and device is not None:
         geometry = geometry.to(device)
     cs = G.canonical_rows(geometry, what)[0]
@@ -628,7 +811,10 @@ def decode_attributes_lossless(data, geometry, device=None):
         return torch.from_numpy(np.frombuffer(data, np.uint8, b1 - b0, b0).reshape(n, ch).copy()).to(dev)
     rows = n - 1
     with torch.cuda.device(dev):
+        ph = G._Phases(timings is not None)
+        ph.mark("start")
         sets = G.level_sets(cs, tuple(cs.bounds.lo), depth)
+        ph.mark("level_sets_ms")
         masks, offs, checks = _plan(sets, depth, dev)
         weights = [None] * (depth + 1)                                      # the voxels weigh 1: no array
         for l in range(depth - 1, -1, -1):
@@ -636,22 +822,45 @@ def decode_attributes_lossless(data, geometry, device=None):
             L.call("pcc_raht_weights", *_level_args(sets[l], sets[l + 1]), L.ptr(weights[l + 1]), L.ptr(weights[l]), L.stream())
         status = torch.zeros(2, dtype=torch.int32, device=dev)             # rANS status | clamp flag
         coef = torch.zeros(max(rows, 1) * ch, dtype=torch.int32, device=dev)
+        last = depth - 1
+        ph.mark("plan_weights_ms")
+        if inter:
+            if hdr["blocks"] != sets[max(0, depth - G.BLOCK_LOG2)].n:
+                raise L.PccError(f"{what}: the stream codes {hdr['blocks']} blocks, the geometry has {sets[max(0, depth - G.BLOCK_LOG2)].n}")
+            bargs, nb, match, tv, nr, _keep = _inter_state(cs, sets, tuple(cs.bounds.lo), depth, ref, ch, colour, status.data_ptr() + 4)
+            m0, m1 = hdr["modes"]
+            bits = np.unpackbits(np.frombuffer(data, np.uint8, m1 - m0, m0), bitorder="little")[:nb]
+            d_mode = torch.from_numpy(bits.astype(np.int32)).to(dev)
+            ph.mark("motion_match_ms")
         if rows:
             b0, b1 = hdr["payload"]
             d_buf = torch.from_numpy(R.stage(data, [(b0, b1)])[0]).to(dev)
             d_side = torch.tensor(hdr["side"], dtype=torch.int32, device=dev)
             idx = torch.empty(rows * ch, dtype=torch.int32, device=dev)
-            _fill_index(masks, offs, sets, depth, ch, d_side, idx, rows)
+            _fill_index(masks, offs, sets, last if inter else depth, ch, d_side, idx, rows)
+            if inter:
+                L.call("pcc_lift_inter_select", L.ptr(sets[last].keys), L.ptr(masks[last]), L.ptr(offs[last]), sets[last].n, last, ch, *bargs,
+                       None, L.ptr(d_mode), L.ptr(d_side), L.ptr(idx), None, None, sets[last].n - 1, rows, status.data_ptr() + 4, L.stream())
             R.decode(_tables(dev), d_buf, b1 - b0, idx, rows * ch, 1, 1, hdr["streams"], coef, status.data_ptr())
+        ph.mark("index_rans_ms")
         v = torch.tensor([hdr["root"]], dtype=torch.int32, device=dev)
         for l in range(depth):
             cv = torch.zeros((sets[l + 1].n, ch), dtype=torch.int32, device=dev)
-            L.call("pcc_lift_inverse", *_node_level_args(sets[l], sets[l + 1], l == 0), L.ptr(offs[l]), L.ptr(weights[l + 1]), L.ptr(v), ch,
-                   int(colour), int(predict), L.ptr(coef), sets[l].n - 1, rows, L.ptr(cv), status.data_ptr() + 4, L.stream())
+            if inter and l == last:
+                L.call("pcc_lift_inter_inverse", *_node_level_args(sets[l], sets[l + 1], l == 0), *bargs, L.ptr(d_mode), L.ptr(offs[l]), L.ptr(v),
+                       ch, int(colour), L.ptr(match), L.ptr(tv), nr, L.ptr(coef), sets[l].n - 1, rows, L.ptr(cv), status.data_ptr() + 4,
+                       L.stream())
+            else:
+                L.call("pcc_lift_inverse", *_node_level_args(sets[l], sets[l + 1], l == 0), L.ptr(offs[l]), L.ptr(weights[l + 1]), L.ptr(v),
+                       ch, int(colour), int(predict), L.ptr(coef), sets[l].n - 1, rows, L.ptr(cv), status.data_ptr() + 4, L.stream())
             v = cv
         out = torch.empty((n, ch), dtype=torch.uint8, device=dev)
         L.call("pcc_lift_finish", L.ptr(v), n, ch, int(colour), L.ptr(out), status.data_ptr() + 4, L.stream())
+        ph.mark("inverse_finish_ms")
         back = torch.cat([status, checks.reshape(-1)]).cpu().numpy()         # the decode's one device->host read
+        if timings is not None:
+            torch.cuda.synchronize(dev)
+            timings["stages_ms"] = ph.report()
     _check_plan(back[2:], sets, what)
     if back[0] != 0:
         raise L.PccError(f"lossless attribute stream: malformed rANS container (status {int(back[0])})")

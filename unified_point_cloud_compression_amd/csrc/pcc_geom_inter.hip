@@ -13,18 +13,15 @@
 // The prediction is never a key list: a block's pyramid is addressed by the block's row in its level, so every size follows from
 // the node count of that level, which the stream header gives.  The reference is probed in absolute coordinates through its
 // grid index or, without one, by binary search over its keys.  Integers only; every sum is order independent.
-#include "pcc_common.h"
-#include "pcc_conv.h"
+#include "pcc_geom_inter.h"
 
 static constexpr int INTER_ROWS = 128;
 static constexpr int INTER_HIST = INTER_ROWS * 256;      // [row][symbol], then 8 popcount classes (absent), 9 distance classes (present)
 static constexpr int INTER_CLASSES = 17;
 static constexpr int INTER_PYR = 75;                     // words per block: tier 4 at 0 (64), tier 3 at 64 (8), tiers 2, 1, 0 at 72, 73, 74
-static constexpr int INTER_MAX_CAND = 125;
 static constexpr int INTER_CDF_STRIDE = 258;
 static constexpr int INTER_CDF_TOTAL = 64 * 257 + 64 * 258;
 
-struct InterCands { int n; int v[INTER_MAX_CAND]; };     // (dx + 8) | (dy + 8) << 4 | (dz + 8) << 8, by |v|^2 then lexicographically
 struct InterRho { unsigned char rho[256], inv[256]; };   // rho: symbol -> t = s ^ r by (popcount(t), t); inv: t -> symbol
 
 static constexpr InterRho inter_make_rho() {
@@ -47,22 +44,10 @@ __device__ __forceinline__ int inter_bit(const unsigned long long* w, int e, int
   return (int)((w[inter_tier(e) + (c >> 6)] >> (c & 63)) & 1ull);
 }
 
-// a voxel of a set given in ABSOLUTE coordinates (any sign inside the key range)
-__device__ inline bool inter_has(const PccGrid& g, const int64_t* __restrict__ keys, int n, int x, int y, int z) {
-  const int B = (int)PCC_BIAS;
-  if (x < -B || y < -B || z < -B || x >= B || y >= B || z >= B) return false;
-  return pcc_lookup(g, keys, n, pcc_key_pack(0, x, y, z)) >= 0;
-}
-
 // a node of a level of the coder (origin-relative cells, never negative)
 __device__ inline bool inter_node(const PccGrid& g, const int64_t* __restrict__ keys, int n, int x, int y, int z) {
   if ((x | y | z) < 0 || x >= (int)PCC_BIAS || y >= (int)PCC_BIAS || z >= (int)PCC_BIAS) return false;
   return pcc_lookup(g, keys, n, pcc_key_pack(0, x, y, z)) >= 0;
-}
-
-__device__ __forceinline__ void inter_cand(const InterCands& c, int j, int& dx, int& dy, int& dz) {
-  const int p = c.v[j];
-  dx = (p & 15) - 8; dy = ((p >> 4) & 15) - 8; dz = ((p >> 8) & 15) - 8;
 }
 
 __global__ void __launch_bounds__(64) k_inter_block_bits(const int64_t* __restrict__ bkeys, int bl, const int64_t* __restrict__ skeys, int ns,
@@ -368,34 +353,6 @@ __global__ void __launch_bounds__(256) k_inter_tables(const unsigned long long* 
 }
 
 // ---- host entry points --------------------------------------------------------------------------------------------------
-static int inter_cands(int search, const char* who, InterCands* out) {
-  PCC_REQUIRE(search >= 0 && search <= 2, "%s: search range %d outside 0..2", who, search);
-  int n = 0, v[INTER_MAX_CAND][3];
-  for (int dx = -search; dx <= search; ++dx)
-    for (int dy = -search; dy <= search; ++dy)
-      for (int dz = -search; dz <= search; ++dz) { v[n][0] = dx; v[n][1] = dy; v[n][2] = dz; ++n; }
-  // by |v|^2, then lexicographically: the enumeration above is lexicographic, and an insertion sort on the norm is stable
-  for (int i = 1; i < n; ++i) {
-    int t[3] = {v[i][0], v[i][1], v[i][2]};
-    const int nt = t[0] * t[0] + t[1] * t[1] + t[2] * t[2];
-    int j = i - 1;
-    while (j >= 0 && v[j][0] * v[j][0] + v[j][1] * v[j][1] + v[j][2] * v[j][2] > nt) {
-      v[j + 1][0] = v[j][0]; v[j + 1][1] = v[j][1]; v[j + 1][2] = v[j][2];
-      --j;
-    }
-    v[j + 1][0] = t[0]; v[j + 1][1] = t[1]; v[j + 1][2] = t[2];
-  }
-  memset(out, 0, sizeof(*out));
-  out->n = n;
-  for (int i = 0; i < n; ++i) out->v[i] = (v[i][0] + 8) | ((v[i][1] + 8) << 4) | ((v[i][2] + 8) << 8);
-  return PCC_OK;
-}
-
-static bool inter_origin_ok(int ox, int oy, int oz) {
-  const int B = 1 << 15;
-  return ox >= -B && oy >= -B && oz >= -B && ox < B && oy < B && oz < B;
-}
-
 extern "C" int32_t pcc_geom_inter_pyramid_words(void) { return INTER_PYR; }
 
 extern "C" int32_t pcc_geom_inter_candidates(int32_t search, int32_t* h_out /*[n, 3]*/) {

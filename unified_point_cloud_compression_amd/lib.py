@@ -186,6 +186,12 @@ SIGNATURES = {
     "pcc_lift_inverse": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _i64, _p, _p,
                                    _p]),
     "pcc_lift_finish": (C.c_int, [_p, _i64, _i32, _i32, _p, _p, _p]),
+    "pcc_lift_inter_match": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _p, _i32, _p, _i32, _p, _i64, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p]),
+    "pcc_lift_inter_residual": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _i64, _p, _p, _p, _i32, _p, _p, _i32, _p, _p,
+                                          _i64, _p, _p, _i64, _i64, _p, _p, _p]),
+    "pcc_lift_inter_select": (C.c_int, [_p, _p, _p, _i64, _i32, _i32, _p, _i64, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p]),
+    "pcc_lift_inter_inverse": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _i64, _p, _p, _p, _i32, _p, _p, _p, _i32, _i32,
+                                         _p, _p, _i64, _p, _i64, _i64, _p, _p, _p]),
     "pcc_conv_pairs_supported": (C.c_int, [_i32, _i32, _i32]),
     "pcc_pair_plan_ws_bytes": (_sz, [_i64, _i32]),
     "pcc_pair_plan_rank": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _sz, _p]),
