@@ -751,6 +751,61 @@ int pcc_raht_hist(const int32_t* sym, const int32_t* grp, int64_t n_sym, int32_t
 int pcc_raht_finish(const int32_t* values, int64_t n, int32_t channels, int32_t colour, uint8_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 8f-3c' inter frames of the RAHT colour coder (DESIGN.md section 7f "Inter frames", stream 0xB4): a prediction signal P (Q8
+ *       int32 [n, channels]) over the CURRENT voxels goes through the same integer forward transform as the source, over the
+ *       same geometry and weights, and a row travels as quantise(H - Hp); the decoder forms Hp the same way and adds it to
+ *       q * step.  Blocks, block grid and block_log2 as in 8f-3e (the nodes of level max(0, depth - 4)); match from
+ *       pcc_lift_inter_match; ref_values int32 [n_ref, channels] from pcc_raht_prepare over the reference's levels.  Levels are
+ *       given as in 8f-3c.  d_flag: device int32 zeroed by the caller; bit 0 is set by a block row, a mode or a match outside
+ *       its range (counted as mode 0 / unmatched) and by the clamps of the inverse.
+ * pcc_raht_inter_fill     sums [n_blocks, channels + 1] int32 (cleared here): per channel the sum of ref_values over the block's
+ *                         matched voxels, then their count.  pred[i] = ref_values[match[i]], or for an unmatched voxel
+ *                         floor(sum / count) of its block; zero in a block without a match and, with mode != NULL (decoder),
+ *                         in a block of mode 0.
+ * pcc_raht_inter_forward  pcc_raht_forward over child_v and child_p in one pass: w, v and p (the prediction's DC) of the node,
+ *                         coef = quantise(H) and coef_p = quantise(H - Hp) at the node's rows.  sums != NULL (a level inside the
+ *                         blocks, pitch <= 2^block_log2): sums [n_blocks, 2] int32 (zeroed by the caller, accumulated over the
+ *                         levels) += sum |coef|, sum |coef_p| of the node's rows over all channels.  sums == NULL (a level above
+ *                         the blocks): the block arguments are ignored.
+ * pcc_raht_inter_modes    mode[b] = sums[b, 1] < sums[b, 0] and fill_sums[b, channels] > 0; block_p [n_blocks, channels] (the p
+ *                         of the block level) is zeroed for a mode-0 block, so the levels above see the decision.
+ * pcc_raht_inter_select   a level >= depth - block_log2: idx of its rows: group (mode ? depth : level) * 6 + 3 * (channel > 0) +
+ *                         stage, or side[group] & 63; coef != NULL (encoder): rows of mode-0 blocks are copied from coef into
+ *                         coef_p.  mask / off as for pcc_raht_index.
+ * pcc_raht_inter_predict  decoder: p (DC) of the node and the unquantised Hp of its rows into hp [rows_total, channels].
+ * pcc_raht_inter_inverse  pcc_raht_inverse with H = hp + q * step (both terms and the sum clamped to +-2^30) and, dc_p != NULL
+ *                         (the root), DC = v + dc_p.
+ * ---------------------------------------------------------------------------------------- */
+int pcc_raht_inter_fill(const int64_t* voxel_keys, int64_t n, const int64_t* block_keys, int64_t n_blocks,
+                        const uint64_t* block_bits, const int32_t* block_rank, const int32_t* h_block, int32_t block_log2,
+                        const int32_t* match, const int32_t* ref_values /*nullable when n_ref == 0*/, int64_t n_ref,
+                        int32_t channels, const int32_t* mode /*nullable*/, int32_t* sums, int32_t* pred, int32_t* d_flag,
+                        void* stream);
+int pcc_raht_inter_forward(const int64_t* keys, int64_t n, int32_t pitch, const int64_t* child_keys, int64_t n_child,
+                           const uint64_t* child_bits, const int32_t* child_rank, const int32_t* h_child,
+                           const int64_t* block_keys, int64_t n_blocks, const uint64_t* block_bits, const int32_t* block_rank,
+                           const int32_t* h_block, int32_t block_log2, const int32_t* off, const int32_t* child_w /*nullable*/,
+                           const int32_t* child_v, const int32_t* child_p, int32_t channels, const int32_t* h_steps, int32_t* w,
+                           int32_t* v, int32_t* p, int32_t* coef, int32_t* coef_p, int64_t row_base, int64_t rows_total,
+                           int32_t* sums /*nullable*/, int32_t* d_flag /*nullable without sums*/, void* stream);
+int pcc_raht_inter_modes(const int32_t* sums, const int32_t* fill_sums, int64_t n_blocks, int32_t channels, int32_t* mode,
+                         int32_t* block_p, void* stream);
+int pcc_raht_inter_select(const int64_t* keys, const int32_t* mask, const int32_t* off, int64_t n, int32_t level, int32_t depth,
+                          int32_t channels, const int64_t* block_keys, int64_t n_blocks, const uint64_t* block_bits,
+                          const int32_t* block_rank, const int32_t* h_block, int32_t block_log2, const int32_t* mode,
+                          const int32_t* side /*nullable*/, int32_t* idx, int32_t* coef_p /*nullable*/,
+                          const int32_t* coef /*nullable*/, int64_t row_base, int64_t rows_total, int32_t* d_flag, void* stream);
+int pcc_raht_inter_predict(const int64_t* keys, int64_t n, int32_t pitch, const int64_t* child_keys, int64_t n_child,
+                           const uint64_t* child_bits, const int32_t* child_rank, const int32_t* h_child, const int32_t* off,
+                           const int32_t* child_w /*nullable*/, const int32_t* child_p, int32_t channels, int32_t* p, int32_t* hp,
+                           int64_t row_base, int64_t rows_total, void* stream);
+int pcc_raht_inter_inverse(const int64_t* keys, int64_t n, int32_t pitch, const int64_t* child_keys, int64_t n_child,
+                           const uint64_t* child_bits, const int32_t* child_rank, const int32_t* h_child, const int32_t* off,
+                           const int32_t* child_w /*nullable*/, const int32_t* v, const int32_t* dc_p /*nullable*/,
+                           int32_t channels, const int32_t* h_steps, const int32_t* coef, const int32_t* hp, int64_t row_base,
+                           int64_t rows_total, int32_t* child_v, int32_t* d_flag, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * 8f-3d lossless attribute coder over the same level sets: the levels, stages, slot pairs, rows and
  *       groups of 8f-3c (pcc_raht_mask / pcc_raht_weights / pcc_raht_index / pcc_raht_hist and pcc_geom_child_offsets serve both)
  *       with a reversible arithmetic.  Values are plain int32 levels [rows, channels], 1 <= channels <= 8: 0..255, and with

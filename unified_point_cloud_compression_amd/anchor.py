@@ -9,6 +9,9 @@ their mean colour (`voxelize.voxel_grid`); the lossless octree (`geometry.encode
 
     container = u8 0xC1 | f64 position_scale | u32 len_geometry | geometry stream | attribute stream
 
+Both parts may be coded against the previous frame as decoded (`compress_anchor(reference=, attributes=)`);
+`compress_anchor_sequence` / `decompress_anchor_sequence` chain whole frames that way in a closed loop.
+
 `compress_lossless` / `decompress_lossless` return a voxel cloud bit for bit: the same octree with the
 lossless colour coder (`attributes.encode_attributes_lossless`), no scaling and no merging.
 
@@ -24,7 +27,8 @@ import torch
 
 from . import lib as L
 from . import sparse as S
-from .attributes import INTER_MAGIC, decode_attributes, decode_attributes_lossless, encode_attributes, encode_attributes_lossless
+from .attributes import (INTER_LOSSY_MAGIC, INTER_MAGIC, decode_attributes, decode_attributes_lossless, encode_attributes,
+                         encode_attributes_lossless)
 from .geometry import decode_geometry, encode_geometry
 from .voxelize import voxel_grid
 
@@ -60,12 +64,19 @@ def scaled_voxels(cloud, position_scale):
 
 
 @torch.no_grad()
-def compress_anchor(cloud, qp, position_scale=1.0, chroma_qp_offset=-2, reference=None):
+def compress_anchor(cloud, qp, position_scale=1.0, chroma_qp_offset=-2, reference=None, attributes="intra"):
     """[N, 6] GPU cloud (xyz, rgb in [0, 1]) -> bytes.  position_scale in (0, 1]: below 1 the points are scaled first; points
     that then share a cell are merged with their mean colour.  qp, chroma_qp_offset: `attributes.encode_attributes`.
     reference: voxels IN THE SCALED DOMAIN that `decompress_anchor` will be given too (the previous frame's decoded geometry,
-    say): the geometry is then coded against them where that is shorter (`geometry.encode_geometry`); colour stays intra."""
+    say): the geometry is then coded against them where that is shorter (`geometry.encode_geometry`).  attributes: "intra" --
+    colour ignores the reference; "auto" / "inter" -- the mode of `attributes.encode_attributes`, which then needs an [M, 6]
+    reference of distinct scaled-domain integer voxels with rgb in [0, 1]: the previous frame AS DECODED
+    (`compress_anchor_sequence` keeps that loop closed)."""
     what = "compress_anchor"
+    if attributes not in ("auto", "inter", "intra"):
+        raise L.PccError(f"{what}: attributes {attributes!r} is not one of auto, inter, intra")
+    if attributes != "intra" and not _has_colours(reference):
+        raise L.PccError(f"{what}: attributes={attributes!r} needs an [M, 6] reference cloud (scaled-domain xyz, rgb in [0, 1])")
     if not torch.is_tensor(cloud) or cloud.dim() != 2 or cloud.shape[1] != 6 or cloud.shape[0] == 0:
         raise L.PccError(f"{what}: a non-empty [N, 6] cloud (xyz, rgb in [0, 1]) is required")
     if not cloud.is_cuda:
@@ -78,21 +89,70 @@ def compress_anchor(cloud, qp, position_scale=1.0, chroma_qp_offset=-2, referenc
     cs = S.coordset_from_coords(c4, 1)[0]                    # the grid's rows are ascending: canonical as they are
     levels = torch.round(g.attrs.to(torch.float64) * 255.0).clamp_(0, 255).to(torch.uint8)
     geometry = encode_geometry(cs, reference=reference)
-    attributes = encode_attributes(cs, qp, chroma_qp_offset, attrs=levels)
-    return HEADER.pack(MAGIC, scale, len(geometry)) + geometry + attributes
+    if attributes == "intra":
+        colours = encode_attributes(cs, qp, chroma_qp_offset, attrs=levels)
+    else:
+        colours = encode_attributes(cs, qp, chroma_qp_offset, attrs=levels, reference=reference, mode=attributes)
+    return HEADER.pack(MAGIC, scale, len(geometry)) + geometry + colours
+
+
+def _decode_anchor(data, device, reference):
+    """(position scale, the decoded voxel set in the scaled domain, its uint8 levels): what `decompress_anchor` returns and what
+    the next frame of a sequence is coded against both come from here."""
+    scale, geometry, attributes = parse_container(data)
+    inter = len(attributes) > 0 and attributes[0] == INTER_LOSSY_MAGIC
+    if inter and not _has_colours(reference):
+        raise L.PccError("decompress_anchor: the colours are coded against a reference; an [M, 6] reference cloud is required")
+    cs = decode_geometry(geometry, device, as_set=True, reference=reference)
+    return scale, cs, decode_attributes(attributes, cs, reference=reference if inter else None)
+
+
+def _decoded_cloud(scale, cs, levels):
+    """[n, 6] float32: the set's voxels divided by the scale (1.0: the scaled domain itself) and levels / 255 (round(255 c) gives
+    them back)."""
+    dev = cs.device
+    xyz = cs.coords()[:cs.n, 1:].to(torch.float64) / torch.tensor(scale, dtype=torch.float64, device=dev)
+    rgb = levels.to(torch.float64) / torch.tensor(255.0, dtype=torch.float64, device=dev)
+    return torch.cat([xyz, rgb], dim=1).to(torch.float32)
 
 
 @torch.no_grad()
 def decompress_anchor(data, device, reference=None):
     """bytes -> [n, 6] float32 on `device`: positions divided by the scale, colours / 255, in canonical order.  reference:
-    the scaled-domain voxels `compress_anchor` was given."""
-    scale, geometry, attributes = parse_container(data)
-    cs = decode_geometry(geometry, device, as_set=True, reference=reference)
-    levels = decode_attributes(attributes, cs)
-    dev = cs.device
-    xyz = cs.coords()[:cs.n, 1:].to(torch.float64) / torch.tensor(scale, dtype=torch.float64, device=dev)
-    rgb = levels.to(torch.float64) / torch.tensor(255.0, dtype=torch.float64, device=dev)
-    return torch.cat([xyz, rgb], dim=1).to(torch.float32)
+    the scaled-domain cloud `compress_anchor` was given; a stream whose colours are coded against it (magic byte 0xB4 of the
+    attribute part) raises PccError when the reference has no colours."""
+    return _decoded_cloud(*_decode_anchor(data, device, reference))
+
+
+@torch.no_grad()
+def compress_anchor_sequence(frames, qp, position_scale=1.0, chroma_qp_offset=-2, intra_period=32):
+    """Frames ([N, 6] clouds as for `compress_anchor`) -> one stream per frame, closed loop: frame i is coded on its own when
+    i % intra_period == 0, else against frame i - 1 AS DECODED -- its voxels in the scaled domain and its decoded colours --
+    with geometry and colour both "auto".  The encoder decodes every stream it wrote to hold what the decoder will hold.
+    `decompress_anchor_sequence` returns the frames."""
+    if int(intra_period) < 1:
+        raise L.PccError(f"compress_anchor_sequence: intra_period {intra_period} is not positive")
+    out, prev = [], None
+    for i, frame in enumerate(frames):
+        if i % int(intra_period) == 0:
+            out.append(compress_anchor(frame, qp, position_scale, chroma_qp_offset))
+            prev = None
+        else:
+            out.append(compress_anchor(frame, qp, position_scale, chroma_qp_offset, reference=prev, attributes="auto"))
+        _, cs, levels = _decode_anchor(out[-1], frame.device, prev)
+        prev = _decoded_cloud(1.0, cs, levels)
+    return out
+
+
+@torch.no_grad()
+def decompress_anchor_sequence(streams, device):
+    """The streams of `compress_anchor_sequence` -> the frames, each [n, 6] float32 as `decompress_anchor` returns them."""
+    out, prev = [], None
+    for data in streams:
+        scale, cs, levels = _decode_anchor(data, device, prev)
+        prev = _decoded_cloud(1.0, cs, levels)                 # the reference stays in the scaled domain
+        out.append(_decoded_cloud(scale, cs, levels))
+    return out
 
 
 # ---- the lossless codec --------------------------------------------------------------------------------------------------

@@ -6,6 +6,10 @@ this project's own stream: no G-PCC syntax and no bit-compatibility claim, the s
     stream = u8 0xB3 | u32 n | u8 depth | u8 C | u8 flags (bit 0: colour transform) | u8 qp | i8 chroma_qp_offset
              | C zig-zag LEB128 varints (the quantised root DC) | depth x 6 side bytes | u32 length | rANS container
     (no length and no container when n <= 1)
+    inter:   u8 0xB4 | u32 n | u8 depth | u8 C | u8 flags | u8 qp | i8 chroma_qp_offset | u8 block_log2 | u8 search | u32 blocks
+             | C zig-zag varints (the quantised root DC residual) | (depth + 1) x 6 side bytes
+             | ceil(blocks / 8) mode bytes (block b: bit b & 7 of byte b >> 3) | u32 length | rANS container
+             (coded against a reference cloud the decoder holds, in the coefficient domain; no vector travels; "Inter frames" in 7f)
 
 The geometry is not in the stream: the decoder is handed it and refuses a stream whose n or depth differ from the set's.
 Level l of the transform is level l of the octree (`geometry.level_sets`); inside a node three stages of weighted Haar
@@ -50,6 +54,8 @@ MAX_POINTS = 1 << 26       # a DC value stays below 2^29 and every product below
 LIMIT = 1 << 30            # the decoder's clamp on q * step and on every butterfly output
 QP_MIN, QP_MAX = 4, 51
 HEADER = struct.Struct("<BIBBBBb")
+INTER_LOSSY_MAGIC = 0xB4   # inter frames, format version 1: coefficients predicted from a reference cloud
+INTER_LOSSY_HEADER = struct.Struct("<BIBBBBbBBI")
 STEP_TABLE = (256, 287, 323, 362, 406, 456)                 # Q8: 2^(k / 6), k = 0..5
 THETA = (55109, 46341, 38968, 32768)                        # Q16: 2^(-k / 4), k = 1..4
 N_TABLES, N_SLOTS, ESCAPE, MAX_ABS = 64, 128, 127, 63       # slots 0..126: the values -63..63; slot 127: the escape
@@ -166,16 +172,23 @@ def _container_span(data, at, symbols, name):
     return (at, at + nbytes), streams
 
 
-def parse_header(data):
+def parse_header(data, have_reference=True):
     """{n, depth, channels, colour, qp, chroma_qp_offset, steps, dc (quantised root DC per channel), side (depth * 6 members),
-    payload=(begin, end) or None, streams}.  Raises PccError on a bad magic byte, on channels, qp or depth out of range, on a
-    root DC or side byte out of range, on truncation, on trailing bytes and on a length that disagrees with the data --
-    before any GPU work."""
-    if len(data) < HEADER.size:
-        raise L.PccError("attribute stream truncated inside the header")
+    payload=(begin, end) or None, streams, inter}.  Raises PccError on a bad magic byte, on channels, qp or depth out of range,
+    on a root DC or side byte out of range, on truncation, on trailing bytes and on a length that disagrees with the data --
+    before any GPU work.  An inter stream (0xB4) has inter=True, dc = the quantised root DC residual, (depth + 1) * 6 side bytes
+    and block_log2, search, blocks, modes=(begin, end) besides; refused for it as well: a block size or search range other than
+    this build's, depth > 14, n < 2, a block count of 0 or above n, set padding bits of the mode bytes, and have_reference=False."""
+    inter = len(data) > 0 and data[0] == INTER_LOSSY_MAGIC
+    name = "inter attribute stream" if inter else "attribute stream"
+    head = INTER_LOSSY_HEADER if inter else HEADER
+    if inter and not have_reference:
+        raise L.PccError(f"{name}: the stream is coded against a reference cloud and none was given")
+    if len(data) < head.size:
+        raise L.PccError(f"{name} truncated inside the header")
     magic, n, depth, ch, flags, qp, cqo = HEADER.unpack_from(data, 0)
-    if magic != MAGIC:
-        raise L.PccError(f"attribute stream: magic byte {magic:#x}, this build reads {MAGIC:#x}")
+    if magic not in (MAGIC, INTER_LOSSY_MAGIC):
+        raise L.PccError(f"attribute stream: magic byte {magic:#x}, this build reads {MAGIC:#x} and {INTER_LOSSY_MAGIC:#x}")
     if not 1 <= ch <= MAX_C:
         raise L.PccError(f"attribute stream: {ch} channels outside 1..{MAX_C}")
     if flags & ~1 or (flags & 1 and ch != 3):
@@ -186,8 +199,21 @@ def parse_header(data):
         raise L.PccError(f"attribute stream: header claims {n} points, the limit is 2^26 - 1")
     if (n == 0 and depth != 0) or (n > 0 and not 1 <= depth <= G.MAX_DEPTH) or n > 8 ** min(depth, 10):
         raise L.PccError(f"attribute stream: header claims {n} points at depth {depth}")
+    hdr = {"inter": inter}
+    if inter:
+        block_log2, search, blocks = INTER_LOSSY_HEADER.unpack_from(data, 0)[7:]
+        if block_log2 != G.BLOCK_LOG2 or search != G.SEARCH:
+            raise L.PccError(f"{name}: block_log2 {block_log2}, search {search}; this build reads {G.BLOCK_LOG2} and {G.SEARCH}")
+        if n < 2:
+            raise L.PccError(f"{name}: header claims {n} points, an inter stream codes 2 .. 2^26 - 1")
+        if depth > INTER_MAX_DEPTH:
+            raise L.PccError(f"{name}: header claims depth {depth} (inter streams exist up to depth {INTER_MAX_DEPTH})")
+        if not 1 <= blocks <= n:
+            raise L.PccError(f"{name}: header claims {blocks} blocks for {n} points")
+        hdr.update(block_log2=block_log2, search=search, blocks=blocks)
+    groups = (depth + 1) * 6 if inter else depth * 6
     steps = steps_for(qp, cqo, ch)
-    at, dc = HEADER.size, []
+    at, dc = head.size, []
     for c in range(ch):
         u, sh = 0, 0
         while True:
@@ -203,19 +229,27 @@ def parse_header(data):
         if abs(q) * steps[c] > LIMIT:
             raise L.PccError(f"attribute stream: root DC {q} of channel {c} is out of range")
         dc.append(q)
-    if at + depth * 6 > len(data):
-        raise L.PccError("attribute stream truncated inside the side bytes")
-    side = list(data[at:at + depth * 6])
-    at += depth * 6
+    if at + groups > len(data):
+        raise L.PccError(f"{name} truncated inside the side bytes")
+    side = list(data[at:at + groups])
+    at += groups
     if side and max(side) >= N_TABLES:
-        raise L.PccError(f"attribute stream: side byte {max(side)} names no table (64 members)")
-    hdr = {"n": n, "depth": depth, "channels": ch, "colour": bool(flags & 1), "qp": qp, "chroma_qp_offset": cqo, "steps": steps,
-           "dc": dc, "side": side, "payload": None, "streams": 0}
+        raise L.PccError(f"{name}: side byte {max(side)} names no table (64 members)")
+    if inter:
+        mbytes = (hdr["blocks"] + 7) // 8
+        if at + mbytes > len(data):
+            raise L.PccError(f"{name} truncated inside the mode bytes")
+        if hdr["blocks"] % 8 and data[at + mbytes - 1] >> (hdr["blocks"] % 8):
+            raise L.PccError(f"{name}: padding bits of the mode bytes are set")
+        hdr["modes"] = (at, at + mbytes)
+        at += mbytes
+    hdr.update({"n": n, "depth": depth, "channels": ch, "colour": bool(flags & 1), "qp": qp, "chroma_qp_offset": cqo, "steps": steps,
+                "dc": dc, "side": side, "payload": None, "streams": 0})
     if n > 1:
-        hdr["payload"], hdr["streams"] = _container_span(data, at, (n - 1) * ch, "attribute stream")
+        hdr["payload"], hdr["streams"] = _container_span(data, at, (n - 1) * ch, name)
         at = hdr["payload"][1]
     if at != len(data):
-        raise L.PccError("attribute stream: trailing bytes")
+        raise L.PccError(f"{name}: trailing bytes")
     return hdr
 
 
@@ -287,18 +321,54 @@ def _attribute_rows(cloud, attrs, what):
     return cloud, attrs.contiguous()
 
 
+def _intra_tail(what, sets, masks, offs, checks, coef, v_root, steps, depth, ch, rows, segment_symbols, dev, ev):
+    """(quantised root DC, side bytes, `u32 length | rANS container`) of the 0xB3 stream from the quantised rows and the root's
+    DC: the groups, their histograms, the member choice (one read), the member index and the coder (one read)."""
+    parts = [v_root.reshape(-1), checks.reshape(-1)]
+    if rows:
+        idx = torch.empty(rows * ch, dtype=torch.int32, device=dev)
+        hist = torch.empty(depth * 6 * N_SLOTS, dtype=torch.int32, device=dev)
+        _fill_index(masks, offs, sets, depth, ch, None, idx, rows)
+        L.call("pcc_raht_hist", L.ptr(coef), L.ptr(idx), rows * ch, depth * 6, L.ptr(hist), L.stream())
+        parts.append(hist)
+    back = torch.cat(parts).cpu().numpy()                              # one read: root DC, the plan's checks, the histograms
+    _check_plan(back[ch:ch + 4 * depth], sets, what)
+    dc = [quantise(int(back[c]), steps[c]) for c in range(ch)]
+    side = choose_members(back[ch + 4 * depth:]) if rows else [0] * (depth * 6)
+    if ev:
+        ev[3].record()
+    body = b""
+    if rows:
+        d_side = torch.tensor(side, dtype=torch.int32, device=dev)
+        _fill_index(masks, offs, sets, depth, ch, d_side, idx, rows)
+        body = _rans_body(coef, idx, rows * ch, segment_symbols, dev, what, ev[4] if ev else None)    # one read: size + container
+    return dc, side, body
+
+
 @torch.no_grad()
-def encode_attributes(cloud, qp, chroma_qp_offset=-2, colour=True, attrs=None, segment_symbols=SEGMENT_SYMBOLS, timings=None):
+def encode_attributes(cloud, qp, chroma_qp_offset=-2, colour=True, attrs=None, segment_symbols=SEGMENT_SYMBOLS, timings=None,
+                      reference=None, reference_attrs=None, mode="auto"):
     """[N, 6] GPU tensor (xyz, then rgb in [0, 1]: colours become round(255 c)), or a pitch-1 CoordSet / [N, >= 3] rows with
     `attrs` uint8 [N, C], 1 <= C <= 8 -> bytes.  Any row order (attributes follow their rows into canonical order; a set's
     attributes are in the set's order).  Duplicate voxels, CPU tensors and batched input raise PccError.  colour: the integer
     BT.709 transform in front of the RAHT (three channels only).  segment_symbols: symbols per rANS stream (tests lower it).
-    timings: a dict that receives per-stage device events (tools/anchor_rd.py)."""
+    timings: a dict that receives per-stage device events (tools/anchor_rd.py, tools/anchor_inter_timing.py).
+    reference: a cloud the decoder holds too, with the levels the DECODER holds (the previous frame as decoded) -- [M, 6], or a
+    pitch-1 set / [M, >= 3] rows with `reference_attrs` uint8 [M, C] in its row order; distinct voxels, the cloud's channel
+    count.  mode "auto": the shorter of the inter (0xB4) and the intra (0xB3) stream, intra on a tie and at depth 15 -- by
+    stream length alone: against an unrelated reference the shorter stream may decode to a lower PSNR than the intra one
+    (DESIGN.md 7f); "inter": the inter stream (fewer than two voxels still travel as intra; depth 15 raises); "intra", or no
+    reference: today's stream byte for byte."""
     what = "encode_attributes"
+    if mode not in ("auto", "inter", "intra"):
+        raise L.PccError(f"{what}: mode {mode!r} is not one of auto, inter, intra")
     cloud, levels = _attribute_rows(cloud, attrs, what)
     if not -128 <= int(chroma_qp_offset) <= 127:
         raise L.PccError(f"{what}: chroma_qp_offset {chroma_qp_offset} does not fit the header's signed byte")
     qp, cqo = min(max(int(qp), QP_MIN), QP_MAX), int(chroma_qp_offset)
+    ref = None
+    if reference is not None and mode != "intra":                         # "intra" never looks at the reference
+        ref = _reference_rows(reference, reference_attrs, levels.shape[1], True, what)
     cs, perm, keep = G.canonical_rows(cloud, what)
     if keep is not None:
         raise L.PccError(f"{what}: {levels.shape[0] - cs.n} rows repeat a voxel; merge them first (voxelize.voxel_grid)")
@@ -315,6 +385,11 @@ def encode_attributes(cloud, qp, chroma_qp_offset=-2, colour=True, attrs=None, s
     h_steps = (C.c_int32 * ch)(*steps)
     origin, depth = tuple(cs.bounds.lo), _depth_of(cs)
     rows = n - 1
+    if ref is not None and n >= 2:
+        if depth <= INTER_MAX_DEPTH:
+            return _encode_inter_lossy(what, cs, levels, perm, ref, qp, cqo, colour, mode, segment_symbols, timings)
+        if mode == "inter":
+            raise L.PccError(f"{what}: inter streams exist up to depth {INTER_MAX_DEPTH}, the cloud has depth {depth}")
     with torch.cuda.device(dev):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if timings is not None else None
         sets = G.level_sets(cs, origin, depth)
@@ -335,35 +410,7 @@ def encode_attributes(cloud, qp, chroma_qp_offset=-2, colour=True, attrs=None, s
             w_child, v_child = w, v
         if ev:
             ev[2].record()
-        parts = [v_child.reshape(-1), checks.reshape(-1)]
-        if rows:
-            idx = torch.empty(rows * ch, dtype=torch.int32, device=dev)
-            hist = torch.empty(depth * 6 * N_SLOTS, dtype=torch.int32, device=dev)
-            _fill_index(masks, offs, sets, depth, ch, None, idx, rows)
-            L.call("pcc_raht_hist", L.ptr(coef), L.ptr(idx), rows * ch, depth * 6, L.ptr(hist), L.stream())
-            parts.append(hist)
-        back = torch.cat(parts).cpu().numpy()                              # one read: root DC, the plan's checks, the histograms
-        _check_plan(back[ch:ch + 4 * depth], sets, what)
-        dc = [quantise(int(back[c]), steps[c]) for c in range(ch)]
-        side = choose_members(back[ch + 4 * depth:]) if rows else [0] * (depth * 6)
-        if ev:
-            ev[3].record()
-        body = b""
-        if rows:
-            d_side = torch.tensor(side, dtype=torch.int32, device=dev)
-            _fill_index(masks, offs, sets, depth, ch, d_side, idx, rows)
-            tabs = _tables(dev)
-            plan = R.Plan(rows * ch, 1, 1, segments_for(rows * ch, segment_symbols))
-            cap = R.align8(plan.capacity)
-            blob = torch.zeros(8 + cap, dtype=torch.uint8, device=dev)
-            R.encode(tabs, plan, coef, idx, blob.data_ptr() + 8, blob.data_ptr())
-            if ev:
-                ev[4].record()
-            host = blob.cpu().numpy()                                      # one read: size + container
-            nb = int(host[:8].view(np.int64)[0])
-            if not 0 < nb <= cap:
-                raise L.PccError(f"{what}: the coder produced {nb} bytes for a capacity of {cap}")
-            body = struct.pack("<I", nb) + host[8:8 + nb].tobytes()
+        dc, side, body = _intra_tail(what, sets, masks, offs, checks, coef, v_child, steps, depth, ch, rows, segment_symbols, dev, ev)
         if timings is not None:
             torch.cuda.synchronize(dev)
             timings["stages_ms"] = {"prepare_plan": ev[0].elapsed_time(ev[1]), "forward": ev[1].elapsed_time(ev[2]),
@@ -378,13 +425,19 @@ def encode_attributes(cloud, qp, chroma_qp_offset=-2, colour=True, attrs=None, s
 
 
 @torch.no_grad()
-def decode_attributes(data, geometry, device=None):
+def decode_attributes(data, geometry, device=None, reference=None, reference_attrs=None, timings=None):
     """bytes + the block's geometry (the pitch-1 CoordSet `decode_geometry(..., as_set=True)` returns, or [n, >= 3] rows) ->
-    uint8 [n, C] in the canonical order `decode_geometry` returns.  device=None: the geometry's.  Raises PccError on a
-    malformed stream, on a stream whose n or depth differ from the geometry's, and on a payload that does not decode; never
-    returns anything but exactly [n, C]."""
+    uint8 [n, C] in the canonical order `decode_geometry` returns.  device=None: the geometry's.  reference, reference_attrs:
+    the reference cloud `encode_attributes` was given; an inter stream (0xB4) needs it with its levels, an intra stream ignores
+    it.  The decoder re-runs the motion search and the matching, forms the prediction's transform from the reference it was
+    handed, compares the header's block count with the geometry's and sizes every buffer from the geometry.  Raises PccError on
+    a malformed stream, on a stream whose n, depth or block count differ from the geometry's, and on a payload that does not
+    decode; never returns anything but exactly [n, C].  timings: a dict that receives per-stage device events
+    (tools/anchor_inter_timing.py); asking for them adds a synchronisation at the end."""
     what = "decode_attributes"
-    hdr = parse_header(data)
+    hdr = parse_header(data, have_reference=reference is not None)
+    inter = hdr["inter"]
+    ref = _reference_rows(reference, reference_attrs, hdr["channels"], True, what) if inter else None
     if torch.is_tensor(geometry) and device is not None:
         geometry = geometry.to(device)
     cs = G.canonical_rows(geometry, what)[0]
@@ -400,7 +453,10 @@ def decode_attributes(data, geometry, device=None):
     h_steps = (C.c_int32 * ch)(*steps)
     rows = n - 1
     with torch.cuda.device(dev):
+        ph = G._Phases(timings is not None)
+        ph.mark("start")
         sets = G.level_sets(cs, tuple(cs.bounds.lo), depth)
+        ph.mark("level_sets_ms")
         masks, offs, checks = _plan(sets, depth, dev)
         weights = [None] * (depth + 1)                                      # the voxels weigh 1: no array
         for l in range(depth - 1, -1, -1):
@@ -408,22 +464,61 @@ def decode_attributes(data, geometry, device=None):
             L.call("pcc_raht_weights", *_level_args(sets[l], sets[l + 1]), L.ptr(weights[l + 1]), L.ptr(weights[l]), L.stream())
         status = torch.zeros(2, dtype=torch.int32, device=dev)             # rANS status | clamp flag
         coef = torch.zeros(max(rows, 1) * ch, dtype=torch.int32, device=dev)
+        ph.mark("plan_weights_ms")
+        first, hp, p_root = depth, None, None
+        if inter:
+            first = max(0, depth - G.BLOCK_LOG2)
+            if hdr["blocks"] != sets[first].n:
+                raise L.PccError(f"{what}: the stream codes {hdr['blocks']} blocks, the geometry has {sets[first].n}")
+            flag = status.data_ptr() + 4
+            bargs, nb, match, tv, nr, _keep = _inter_state(cs, sets, tuple(cs.bounds.lo), depth, ref, ch, hdr["colour"], flag,
+                                                           "pcc_raht_prepare")
+            m0, m1 = hdr["modes"]
+            bits = np.unpackbits(np.frombuffer(data, np.uint8, m1 - m0, m0), bitorder="little")[:nb]
+            d_mode = torch.from_numpy(bits.astype(np.int32)).to(dev)
+            ph.mark("motion_match_ms")
+            # the prediction's transform: P with the mode-0 blocks zeroed, then the same forward pass, rows left unquantised
+            fill_sums = torch.empty((nb, ch + 1), dtype=torch.int32, device=dev)
+            p_child = torch.empty((n, ch), dtype=torch.int32, device=dev)
+            L.call("pcc_raht_inter_fill", L.ptr(sets[depth].keys), n, *bargs, L.ptr(match), L.ptr(tv), nr, ch, L.ptr(d_mode), L.ptr(fill_sums),
+                   L.ptr(p_child), flag, L.stream())
+            hp = torch.zeros(rows * ch, dtype=torch.int32, device=dev)
+            for l in range(depth - 1, -1, -1):
+                p = torch.empty((sets[l].n, ch), dtype=torch.int32, device=dev)
+                L.call("pcc_raht_inter_predict", *_level_args(sets[l], sets[l + 1]), L.ptr(offs[l]), L.ptr(weights[l + 1]), L.ptr(p_child), ch,
+                       L.ptr(p), L.ptr(hp), sets[l].n - 1, rows, L.stream())
+                p_child = p
+            p_root = p_child
+            ph.mark("fill_predict_ms")
         if rows:
             b0, b1 = hdr["payload"]
             d_buf = torch.from_numpy(R.stage(data, [(b0, b1)])[0]).to(dev)
             d_side = torch.tensor(hdr["side"], dtype=torch.int32, device=dev)
             idx = torch.empty(rows * ch, dtype=torch.int32, device=dev)
-            _fill_index(masks, offs, sets, depth, ch, d_side, idx, rows)
+            if inter:
+                _inter_index(masks, offs, sets, depth, first, ch, bargs, d_mode, d_side, idx, None, None, rows, status.data_ptr() + 4)
+            else:
+                _fill_index(masks, offs, sets, depth, ch, d_side, idx, rows)
             R.decode(_tables(dev), d_buf, b1 - b0, idx, rows * ch, 1, 1, hdr["streams"], coef, status.data_ptr())
+        ph.mark("index_rans_ms")
         v = torch.tensor([[q * s for q, s in zip(hdr["dc"], steps)]], dtype=torch.int32, device=dev)
         for l in range(depth):
             cv = torch.zeros((sets[l + 1].n, ch), dtype=torch.int32, device=dev)
-            L.call("pcc_raht_inverse", *_level_args(sets[l], sets[l + 1]), L.ptr(offs[l]), L.ptr(weights[l + 1]), L.ptr(v), ch, h_steps,
-                   L.ptr(coef), sets[l].n - 1, rows, L.ptr(cv), status.data_ptr() + 4, L.stream())
+            if inter:
+                L.call("pcc_raht_inter_inverse", *_level_args(sets[l], sets[l + 1]), L.ptr(offs[l]), L.ptr(weights[l + 1]), L.ptr(v),
+                       L.ptr(p_root) if l == 0 else None, ch, h_steps, L.ptr(coef), L.ptr(hp), sets[l].n - 1, rows, L.ptr(cv),
+                       status.data_ptr() + 4, L.stream())
+            else:
+                L.call("pcc_raht_inverse", *_level_args(sets[l], sets[l + 1]), L.ptr(offs[l]), L.ptr(weights[l + 1]), L.ptr(v), ch, h_steps,
+                       L.ptr(coef), sets[l].n - 1, rows, L.ptr(cv), status.data_ptr() + 4, L.stream())
             v = cv
         out = torch.empty((n, ch), dtype=torch.uint8, device=dev)
         L.call("pcc_raht_finish", L.ptr(v), n, ch, int(hdr["colour"]), L.ptr(out), L.stream())
+        ph.mark("inverse_finish_ms")
         back = torch.cat([status, checks.reshape(-1)]).cpu().numpy()         # the decode's one device->host read
+        if timings is not None:
+            torch.cuda.synchronize(dev)
+            timings["stages_ms"] = ph.report()
     _check_plan(back[2:], sets, what)
     if back[0] != 0:
         raise L.PccError(f"attribute stream: malformed rANS container (status {int(back[0])})")
@@ -589,10 +684,12 @@ def _reference_rows(reference, reference_attrs, channels, predict, what):
     return rs, levels, perm
 
 
-def _inter_state(cs, sets, origin, depth, ref, channels, colour, d_flag):
-    """What both sides of an inter stream recompute from the geometry and the reference: (the block arguments of the
-    pcc_lift_inter_* entry points, the block count, int32 match row per voxel, int32 [M, C] prepared reference values or None,
-    M).  `geometry.motion_vectors` gives the vectors; the tensors the arguments point into live in `sets` and the result."""
+def _inter_state(cs, sets, origin, depth, ref, channels, colour, d_flag, prepare="pcc_lift_prepare"):
+    """What both sides of an inter stream (0xB6 and 0xB4) recompute from the geometry and the reference: (the block arguments of
+    the pcc_lift_inter_* / pcc_raht_inter_* entry points, the block count, int32 match row per voxel, int32 [M, C] prepared
+    reference values or None, M).  `geometry.motion_vectors` gives the vectors; the tensors the arguments point into live in
+    `sets` and the result.  prepare: the entry point that turns the reference's levels into the coder's values (plain or
+    YCoCg-R levels for the lossless coder, Q8 with BT.709 for the RAHT coder: "pcc_raht_prepare")."""
     rs, levels, perm = ref
     dev = cs.device
     blocks, bl, _, vec = G.motion_vectors(cs, rs, origin, depth, sets)
@@ -606,7 +703,7 @@ def _inter_state(cs, sets, origin, depth, ref, channels, colour, d_flag):
     if levels.device != dev:
         raise L.PccError("the reference is on another device than the cloud")
     tv = torch.empty((rs.n, channels), dtype=torch.int32, device=dev)
-    L.call("pcc_lift_prepare", L.ptr(levels), L.ptr(perm), rs.n, channels, int(colour), L.ptr(tv), L.stream())
+    L.call(prepare, L.ptr(levels), L.ptr(perm), rs.n, channels, int(colour), L.ptr(tv), L.stream())
     return bargs, blocks.n, match, tv, rs.n, (vec, grid)
 
 
@@ -624,6 +721,95 @@ def _rans_body(coef, idx, symbols, segment_symbols, dev, what, done=None):
     if not 0 < nb <= cap:
         raise L.PccError(f"{what}: the coder produced {nb} bytes for a capacity of {cap}")
     return struct.pack("<I", nb) + host[8:8 + nb].tobytes()
+
+
+def _inter_index(masks, offs, sets, depth, first, ch, bargs, d_mode, d_side, idx, coef_p, coef, rows, d_flag):
+    """idx of all rows of an inter RAHT stream: the levels above the blocks as in the intra stream, the levels inside them by
+    their block's mode.  d_side None: groups; coef given (encoder): the intra symbols of mode-0 blocks are copied into coef_p."""
+    _fill_index(masks, offs, sets, first, ch, d_side, idx, rows)
+    for l in range(first, depth):
+        L.call("pcc_raht_inter_select", L.ptr(sets[l].keys), L.ptr(masks[l]), L.ptr(offs[l]), sets[l].n, l, depth, ch, *bargs, L.ptr(d_mode),
+               L.ptr(d_side), L.ptr(idx), L.ptr(coef_p), L.ptr(coef), sets[l].n - 1, rows, d_flag, L.stream())
+
+
+def _encode_inter_lossy(what, cs, levels, perm, ref, qp, cqo, colour, mode, segment_symbols, timings):
+    """The inter half of `encode_attributes` (n >= 2, depth <= 14): the 0xB4 stream and, for mode "auto", the 0xB3 stream from
+    the same forward pass; the shorter is returned, intra on a tie.  Device->host reads beyond the level sets: 2 for the inter
+    stream (modes, root DCs and histograms; the container), 2 more for the intra stream of "auto"."""
+    n, ch, dev = cs.n, levels.shape[1], cs.device
+    steps = steps_for(qp, cqo, ch)
+    h_steps = (C.c_int32 * ch)(*steps)
+    origin, depth = tuple(cs.bounds.lo), _depth_of(cs)
+    rows = n - 1
+    with torch.cuda.device(dev):
+        ph = G._Phases(timings is not None)
+        sets = G.level_sets(cs, origin, depth)
+        ph.mark("start")
+        d_flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        bargs, nb, match, tv, nr, _keep = _inter_state(cs, sets, origin, depth, ref, ch, colour, L.ptr(d_flag), "pcc_raht_prepare")
+        first = depth - bargs[-1]
+        ph.mark("motion_match_ms")
+        values = torch.empty((n, ch), dtype=torch.int32, device=dev)
+        L.call("pcc_raht_prepare", L.ptr(levels), L.ptr(perm), n, ch, int(colour), L.ptr(values), L.stream())
+        masks, offs, checks = _plan(sets, depth, dev)
+        fill_sums = torch.empty((nb, ch + 1), dtype=torch.int32, device=dev)
+        pred = torch.empty((n, ch), dtype=torch.int32, device=dev)
+        L.call("pcc_raht_inter_fill", L.ptr(sets[depth].keys), n, *bargs, L.ptr(match), L.ptr(tv), nr, ch, None, L.ptr(fill_sums), L.ptr(pred),
+               L.ptr(d_flag), L.stream())
+        ph.mark("prepare_plan_fill_ms")
+        coef = torch.zeros((rows, ch), dtype=torch.int32, device=dev)      # the intra symbols of every row
+        coef_p = torch.zeros((rows, ch), dtype=torch.int32, device=dev)    # the inter stream's symbols
+        sums = torch.zeros((nb, 2), dtype=torch.int32, device=dev)
+        d_mode = torch.empty(nb, dtype=torch.int32, device=dev)
+        w_child, v_child, p_child = None, values, pred
+        for l in range(depth - 1, -1, -1):                                  # the levels above the blocks come after the decision
+            w = torch.empty(sets[l].n, dtype=torch.int32, device=dev)
+            v = torch.empty((sets[l].n, ch), dtype=torch.int32, device=dev)
+            p = torch.empty((sets[l].n, ch), dtype=torch.int32, device=dev)
+            L.call("pcc_raht_inter_forward", *_level_args(sets[l], sets[l + 1]), *bargs, L.ptr(offs[l]), L.ptr(w_child), L.ptr(v_child),
+                   L.ptr(p_child), ch, h_steps, L.ptr(w), L.ptr(v), L.ptr(p), L.ptr(coef), L.ptr(coef_p), sets[l].n - 1, rows,
+                   L.ptr(sums) if l >= first else None, L.ptr(d_flag), L.stream())
+            if l == first:
+                L.call("pcc_raht_inter_modes", L.ptr(sums), L.ptr(fill_sums), nb, ch, L.ptr(d_mode), L.ptr(p), L.stream())
+            w_child, v_child, p_child = w, v, p
+        ph.mark("forward_modes_ms")
+        groups = (depth + 1) * 6
+        idx = torch.empty(rows * ch, dtype=torch.int32, device=dev)
+        hist = torch.empty(groups * N_SLOTS, dtype=torch.int32, device=dev)
+        _inter_index(masks, offs, sets, depth, first, ch, bargs, d_mode, None, idx, coef_p, coef, rows, L.ptr(d_flag))
+        L.call("pcc_raht_hist", L.ptr(coef_p), L.ptr(idx), rows * ch, groups, L.ptr(hist), L.stream())
+        back = torch.cat([v_child.reshape(-1), p_child.reshape(-1), checks.reshape(-1), d_flag, d_mode, hist]).cpu().numpy()      # one read
+        at = 2 * ch + 4 * depth
+        _check_plan(back[2 * ch:at], sets, what)
+        if back[at] != 0:
+            raise L.PccError(f"{what}: the blocks, vectors or matches of the cloud are inconsistent")
+        root = [quantise(int(back[c]) - int(back[ch + c]), steps[c]) for c in range(ch)]
+        modes = back[at + 1:at + 1 + nb]
+        side = choose_members(back[at + 1 + nb:])
+        ph.mark("select_hist_choose_ms")
+        d_side = torch.tensor(side, dtype=torch.int32, device=dev)
+        _inter_index(masks, offs, sets, depth, first, ch, bargs, d_mode, d_side, idx, None, None, rows, L.ptr(d_flag))
+        body = _rans_body(coef_p, idx, rows * ch, segment_symbols, dev, what)          # one read: size + container
+        ph.mark("index_rans_ms")
+        out = bytearray(INTER_LOSSY_HEADER.pack(INTER_LOSSY_MAGIC, n, depth, ch, int(colour), qp, cqo, G.BLOCK_LOG2, G.SEARCH, nb))
+        for q in root:
+            out += _zigzag(q)
+        out += bytes(side) + np.packbits(modes.astype(bool), bitorder="little").tobytes() + body
+        intra = None
+        if mode == "auto":
+            dc, side0, body0 = _intra_tail(what, sets, masks, offs, checks, coef, v_child, steps, depth, ch, rows, segment_symbols, dev, None)
+            intra = bytearray(HEADER.pack(MAGIC, n, depth, ch, int(colour), qp, cqo))
+            for q in dc:
+                intra += _zigzag(q)
+            intra += bytes(side0) + body0
+            ph.mark("intra_stream_ms")
+        if timings is not None:
+            torch.cuda.synchronize(dev)
+            timings["inter_stages_ms"] = ph.report()
+            timings["inter_bytes"], timings["intra_bytes"] = len(out), (len(intra) if intra is not None else None)
+            timings["mode1_blocks"], timings["blocks"] = int(modes.sum()), nb
+            timings["host_reads_by_construction"] = 4 if mode == "auto" else 2   # beyond those of building the level sets
+    return bytes(out if intra is None or len(out) < len(intra) else intra)
 
 
 @torch.no_grad()
