@@ -704,6 +704,53 @@ int pcc_geom_inter_tables(const uint64_t* state, const uint32_t* h_pop, const ui
                           void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 8f-3b'' global motion of the inter coders (DESIGN.md section 7e "Global motion"; motion.py): one rigid transform per frame,
+ *       applied to the reference before the block motion of 8f-3b'.
+ *       The transform is 12 int32 on the HOST: M[3][3] row-major in Q24, then t[3] in Q8 voxels; |M_ij| <= PCC_MOTION_MAX_M,
+ *       |t_i| < PCC_MOTION_MAX_T, else PCC_EINVAL before any launch.
+ * pcc_motion_warp       out_keys[i] = the key of q, q_k = (sum_j M_kj p_j + (t_k << 16) + 2^23) >> 24 in int64 (the shift
+ *                       floors), p the voxel of keys[i] (a pitch-1 key array in any order, duplicates allowed; the batch index is
+ *                       carried); PCC_MOTION_DROPPED when a coordinate of q is outside [-2^15 + 64, 2^15 - 64), the range a
+ *                       coordinate set holds -- nothing else is written for such a row.  d_info (device int32 [8], the caller sets
+ *                       {INT32_MAX x3, INT32_MIN x3, 0, 0}): min q | max q over the kept rows | number of dropped rows | unused;
+ *                       integer atomics, so the values do not depend on arrival order.
+ *                       The warped cloud is the set of distinct kept keys: pcc_sort_keys (stable, with its permutation) and
+ *                       pcc_unique_sorted over out_keys; PCC_MOTION_DROPPED sorts behind every key.  Over a canonical input the
+ *                       first row of a run is the source of LOWEST CANONICAL RANK: the winner whose attributes the cell carries.
+ * pcc_motion_gather     out[u, :] = attrs[perm[first[u]], :] for u < n_out: the uint8 [n_src, c] rows (1 <= c <=
+ *                       PCC_MOTION_MAX_ATTRS) of the winners, perm / first as those two entry points left them (indices are clamped
+ *                       into [0, n_src): nothing is read outside the arrays).
+ * pcc_motion_icp_terms  the normal-equation terms of one point-to-plane ICP iteration for the transform h_rt = R[3][3] row-major,
+ *                       t[3] (HOST, fp64).  Per reference voxel p, in the order of ref_keys (one thread each): x = R p + t;
+ *                       candidates are the voxels c of the CURRENT frame (cur_keys: canonical, pitch 1; grid_* its pcc_grid_build
+ *                       index or NULL bits: binary search, same bits out) with |c_k - floor(x_k + 0.5)| <= ceil(radius) on every
+ *                       axis and |c - x|^2 < radius^2; the match is the candidate of least |c - x|^2, the lowest canonical rank on a
+ *                       tie; no candidate: the voxel adds nothing.  With n the normal at c (normals fp32 [n_cur, 3], those of
+ *                       pcc_normals_grid) and g = h_centre[3]: a = [(x - g) x n, n], b = (c - x) . n, and
+ *                       out[PCC_MOTION_ICP_SUMS] (device fp64) = the 21 entries a_i a_j, i <= j, row by row | the 6 entries a_i b |
+ *                       the number of matches | sum |c - x|^2.  Every product and sum is a separate fp64 rounding in the order
+ *                       written in csrc/pcc_motion.hip; a wave's terms meet in an xor butterfly, the waves and then the workgroups'
+ *                       partials (ws: pcc_motion_icp_ws_bytes(n_ref), a short buffer returns PCC_EWS) are added in index order: no
+ *                       floating-point atomics, two calls give the same bits.  match (nullable int32 [n_ref]): the matched rank
+ *                       or -1.  0 < radius <= 4.
+ * ---------------------------------------------------------------------------------------- */
+#define PCC_MOTION_MAX_M (1 << 25)
+#define PCC_MOTION_MAX_T (1 << 24)
+#define PCC_MOTION_MAX_ATTRS 8
+#define PCC_MOTION_ICP_SUMS 29
+#define PCC_MOTION_DROPPED 0x7FFFFFFFFFFFFFFFll
+int pcc_motion_warp(const int64_t* keys, int64_t n, const int32_t* h_transform /*[12]*/, int64_t* out_keys /*[n]*/,
+                    int32_t* d_info /*[8]*/, void* stream);
+int pcc_motion_gather(const uint8_t* attrs, int32_t c, int64_t n_src, const int32_t* perm, const int32_t* first, int64_t n_out,
+                      uint8_t* out /*[n_out,c]*/, void* stream);
+size_t pcc_motion_icp_ws_bytes(int64_t n_ref);
+int pcc_motion_icp_terms(const int64_t* ref_keys, int64_t n_ref, const int64_t* cur_keys, int64_t n_cur,
+                         const uint64_t* grid_bits /*nullable*/, const int32_t* grid_rank, const int32_t* h_grid,
+                         const float* normals /*[n_cur,3]*/, const double* h_rt /*[12]*/, const double* h_centre /*[3]*/,
+                         double radius, double* out /*[PCC_MOTION_ICP_SUMS]*/, int32_t* match /*nullable [n_ref]*/, void* ws,
+                         size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * 8f-3c RAHT colour coder over the level sets of 8f-3b: the anchor the reference compares against is
  *       `tmc3 --transformType=0` (`utils.py:505-529`); this is the same transform family in our own stream, no G-PCC syntax.
  *       A level is given as its canonical node keys at `pitch` plus the canonical child set at pitch / 2 with that set's grid

@@ -18,7 +18,10 @@ lossless colour coder (`attributes.encode_attributes_lossless`), no scaling and 
     container = u8 0xC2 | u32 len_geometry | geometry stream | attribute stream
 
 Both parts may be coded against a reference cloud the decoder holds (the previous frame): `compress_lossless(reference=,
-attributes=)`, and `compress_lossless_sequence` / `decompress_lossless_sequence` chain whole frames that way.
+attributes=)`, and `compress_lossless_sequence` / `decompress_lossless_sequence` chain whole frames that way.  With
+`global_motion=` the geometry may come out as a global-motion stream (0xA9, DESIGN.md section 7e "Global motion"); the colour
+coder is then given the same warped reference, its colours carried (`motion.warp_cloud`), and the decoder reads the transform
+back from the geometry stream.
 """
 import math
 import struct
@@ -29,7 +32,8 @@ from . import lib as L
 from . import sparse as S
 from .attributes import (INTER_LOSSY_MAGIC, INTER_MAGIC, decode_attributes, decode_attributes_lossless, encode_attributes,
                          encode_attributes_lossless)
-from .geometry import decode_geometry, encode_geometry
+from .geometry import canonical_rows, decode_geometry, encode_geometry, stream_transform
+from .motion import warp_cloud
 from .voxelize import voxel_grid
 
 MAGIC = 0xC1
@@ -177,13 +181,30 @@ def _has_colours(reference):
 
 
 @torch.no_grad()
-def compress_lossless(cloud, reference=None, attributes="intra"):
+def _colour_reference(reference, geometry):
+    """The reference the colour coder sees: the one given, or -- behind a global-motion geometry stream -- that reference
+    warped by the stream's transform with its colours carried, the cloud the geometry's block search ran against."""
+    T = stream_transform(geometry)
+    if T is None:
+        return reference
+    # the colour coder refuses a reference whose rows repeat a voxel; the warp would merge them silently, so it is refused here
+    # as well: what a malformed reference does must not depend on whether the geometry came out wrapped
+    rs, _, keep = canonical_rows(reference, "lossless codec (reference)")
+    if keep is not None:
+        raise L.PccError(f"lossless codec (reference): {reference.shape[0] - rs.n} rows repeat a voxel; merge them first (voxelize.voxel_grid)")
+    return warp_cloud(reference, T)
+
+
+@torch.no_grad()
+def compress_lossless(cloud, reference=None, attributes="intra", global_motion=None):
     """[N, 6] GPU cloud of distinct voxels (integer xyz, rgb in [0, 1]: colours become round(255 c)) -> bytes from which
     `decompress_lossless` returns the same voxels with the same levels.  Non-integer coordinates and repeated voxels raise
     PccError: voxelise first (`voxelize.voxel_grid`).  reference: a voxel cloud (its first three columns) the decoder holds
     too, e.g. the previous frame: the geometry is coded against it where that is shorter.  attributes: "intra" -- the colours
     ignore the reference; "auto" / "inter" -- the mode of `attributes.encode_attributes_lossless`, which then needs an [M, 6]
-    reference of distinct voxels and codes the colours against its colours."""
+    reference of distinct voxels and codes the colours against its colours.  global_motion: as in
+    `geometry.encode_geometry` (None, "auto" or a RigidTransform); when the geometry comes out wrapped, the colours are coded
+    against the warped reference."""
     what = "compress_lossless"
     if attributes not in ("auto", "inter", "intra"):
         raise L.PccError(f"{what}: attributes {attributes!r} is not one of auto, inter, intra")
@@ -202,11 +223,11 @@ def compress_lossless(cloud, reference=None, attributes="intra"):
         raise L.PccError(f"{what}: {cloud.shape[0] - cs.n} rows repeat a voxel; merge them first (voxelize.voxel_grid)")
     levels = torch.round(cloud[:, 3:6].to(torch.float64) * 255.0).clamp_(0, 255).to(torch.uint8)
     levels = (levels if perm is None else levels[perm]).contiguous()
-    geometry = encode_geometry(cs, reference=reference)
+    geometry = encode_geometry(cs, reference=reference, global_motion=global_motion)
     if attributes == "intra":
         colours = encode_attributes_lossless(cs, attrs=levels)
     else:
-        colours = encode_attributes_lossless(cs, attrs=levels, reference=reference, mode=attributes)
+        colours = encode_attributes_lossless(cs, attrs=levels, reference=_colour_reference(reference, geometry), mode=attributes)
     return LOSSLESS_HEADER.pack(LOSSLESS_MAGIC, len(geometry)) + geometry + colours
 
 
@@ -220,16 +241,17 @@ def decompress_lossless(data, device, reference=None):
     if inter and not _has_colours(reference):
         raise L.PccError("decompress_lossless: the colours are coded against a reference; an [M, 6] reference cloud is required")
     cs = decode_geometry(geometry, device, as_set=True, reference=reference)
-    levels = decode_attributes_lossless(attributes, cs, reference=reference if inter else None)
+    levels = decode_attributes_lossless(attributes, cs, reference=_colour_reference(reference, geometry) if inter else None)
     rgb = levels.to(torch.float64) / torch.tensor(255.0, dtype=torch.float64, device=cs.device)
     return torch.cat([cs.coords()[:cs.n, 1:].to(torch.float64), rgb], dim=1).to(torch.float32)
 
 
 @torch.no_grad()
-def compress_lossless_sequence(frames, intra_period=32):
+def compress_lossless_sequence(frames, intra_period=32, global_motion=None):
     """Frames ([N, 6] clouds as for `compress_lossless`) -> one stream per frame: frame i is coded on its own when
     i % intra_period == 0, else against frame i - 1 with geometry and colour both "auto" (lossless: the decoder holds the same
-    frame).  Every stream decodes with `decompress_lossless(stream, device, reference=previous frame)`."""
+    frame) and `global_motion` as given.  Every stream decodes with `decompress_lossless(stream, device, reference=previous
+    frame)`."""
     if int(intra_period) < 1:
         raise L.PccError(f"compress_lossless_sequence: intra_period {intra_period} is not positive")
     out, prev = [], None
@@ -237,7 +259,7 @@ def compress_lossless_sequence(frames, intra_period=32):
         if i % int(intra_period) == 0:
             out.append(compress_lossless(frame))
         else:
-            out.append(compress_lossless(frame, reference=prev, attributes="auto"))
+            out.append(compress_lossless(frame, reference=prev, attributes="auto", global_motion=global_motion))
         prev = frame
     return out
 

@@ -39,6 +39,16 @@ The prediction is the reference displaced per block by the block's vector and cl
 rho^-1(byte XOR predicted byte), rho = 0..255 by (popcount, value), with table rows, adaptive counts and class correction of its
 own (`derive_tables_inter`).  The kernels are those of csrc/pcc_geom_inter.hip; the encoder's vectors ride in the read that
 fetches the raw levels' bytes, the decoder still reads ONCE, at the end.  `encode_sequence` / `decode_sequence` chain frames.
+
+Global motion (`encode_geometry(x, reference=r, global_motion=...)`, DESIGN.md section 7e "Global motion"): one rigid transform
+moves the whole reference before the blocks look at it.
+
+    stream  = u8 0xA9 | 9 x i32 M (Q24, row by row) | 3 x i32 t (Q8 voxels) | an 0xA7 or 0xA8 stream as above        (49 bytes + it)
+
+The stream behind the transform is coded against `motion.warp_cloud(reference, T)`, an integer warp both sides repeat
+(`pcc_motion_warp`).  `parse_header` checks the transform's ranges on the host; the decoder warps the reference rows as they
+come (no canonicalisation first: the set of warped cells does not depend on their order), which costs the one read the
+canonicalisation of the reference would have cost, and decodes the inner stream as before.
 """
 import ctypes as C
 import struct
@@ -47,6 +57,7 @@ import numpy as np
 import torch
 
 from . import lib as L
+from . import motion as M
 from . import rans as R
 from . import sparse as S
 
@@ -120,6 +131,8 @@ TABLE_OFFSETS = np.ones(N_CTX, dtype=np.int32)
 
 # ---- the inter stream, format 0xA8 (module docstring; DESIGN.md section 7e "Inter frames") -----------------------------------
 MAGIC_INTER = 0xA8
+MAGIC_GLOBAL = 0xA9       # wrapper: u8 0xA9 | 12 x i32 transform | an 0xA7 or 0xA8 stream coded against the warped reference
+GLOBAL_HEADER = 1 + M.PACKED.size
 BLOCK_LOG2 = 4            # blocks are the nodes at pitch 16: one motion vector each
 SEARCH = 2                # vectors in [-2, 2]^3: 125 candidates, an index fits a byte
 MAX_SEARCH = 2
@@ -231,12 +244,25 @@ def parse_header(data, have_reference=True):
     pop).  An inter stream (0xA8) adds inter=True, block_log2, search, first (the level of the blocks) and vectors = dict(raw,
     payload, hist, streams); its levels carry `inter` (coded against the prediction) and, coded ones of those, `dist`.  Raises PccError on a bad magic byte, depth, n, block size or search
     range, on an inter stream when the caller has no reference, on truncated or inconsistent side information and on trailing
-    bytes -- before any GPU work."""
+    bytes -- before any GPU work.  A global-motion wrapper (0xA9) is refused without a reference too; its transform's ranges are
+    checked here, the stream behind it is parsed as above (and must not be a wrapper again) and its dictionary is returned with
+    `transform` (a RigidTransform) and `inner` = 49, the byte the payload spans count from."""
+    if len(data) >= 1 and data[0] == MAGIC_GLOBAL:
+        if not have_reference:
+            raise L.PccError("geometry stream: a global-motion stream (0xa9) decodes against a reference cloud, none was given")
+        if len(data) < GLOBAL_HEADER:
+            raise L.PccError("geometry stream truncated inside the global-motion transform")
+        transform = M.RigidTransform.unpack(data[1:GLOBAL_HEADER])          # (refuses entries outside the ranges)
+        if len(data) > GLOBAL_HEADER and data[GLOBAL_HEADER] == MAGIC_GLOBAL:
+            raise L.PccError("geometry stream: a global-motion stream wraps an intra or an inter stream, not another wrapper")
+        hdr = parse_header(bytes(data[GLOBAL_HEADER:]), have_reference)
+        hdr.update(transform=transform, inner=GLOBAL_HEADER)
+        return hdr
     if len(data) < HEADER.size:
         raise L.PccError("geometry stream truncated inside the header")
     magic, n, depth, ox, oy, oz = HEADER.unpack_from(data, 0)
     if magic not in (MAGIC, MAGIC_INTER):
-        raise L.PccError(f"geometry stream: magic byte {magic:#x}, this build reads {MAGIC:#x} and {MAGIC_INTER:#x}")
+        raise L.PccError(f"geometry stream: magic byte {magic:#x}, this build reads {MAGIC:#x}, {MAGIC_INTER:#x} and {MAGIC_GLOBAL:#x}")
     inter = magic == MAGIC_INTER
     at, first, k, block_log2, search = HEADER.size, depth, 1, 0, 0
     if inter:
@@ -391,20 +417,59 @@ def reference_set(reference, what="encode_geometry"):
 
 
 @torch.no_grad()
-def encode_geometry(x, segment_nodes=SEGMENT_NODES, timings=None, reference=None, mode="auto"):
+def encode_geometry(x, segment_nodes=SEGMENT_NODES, timings=None, reference=None, mode="auto", global_motion=None):
     """[N, >= 3] GPU tensor (any row order, duplicates allowed, floats floored) or pitch-1 CoordSet -> bytes.
     segment_nodes: nodes per rANS stream (tests lower it to cut small levels into several streams; the decoder reads the
     stream count from each container).  timings: a dict that receives per-level device events (tools/geometry_timing.py).
     reference: a voxel cloud the decoder holds too (same kinds of input as x), against which the levels at and below the block
     pitch are predicted.  mode "auto": the shorter of the inter (0xA8) and the intra (0xA7) stream, intra on a tie -- never
     longer than without a reference; "inter": the inter stream (an empty cloud still travels as intra); "intra", or no
-    reference: today's stream byte for byte."""
+    reference: today's stream byte for byte.
+    global_motion (DESIGN.md section 7e "Global motion"): None -- the streams above.  A `motion.RigidTransform` T -- the wrapper
+    stream u8 0xA9 | 12 x i32 T | the stream above coded against `motion.warp_cloud(reference, T)` under `mode` (a reference
+    is required).  "auto" -- T = `motion.estimate_rigid(x, reference)`; the wrapper and the plain stream are both coded and
+    the shorter one is returned, the plain one on a tie, when nothing matches or T is the identity: never longer than without
+    global motion."""
     if mode not in ("auto", "inter", "intra"):
         raise L.PccError(f"encode_geometry: mode {mode!r} is not one of auto, inter, intra")
+    if not (global_motion is None or isinstance(global_motion, M.RigidTransform) or (isinstance(global_motion, str) and global_motion == "auto")):
+        raise L.PccError(f"encode_geometry: global_motion {global_motion!r} is not None, \"auto\" or a RigidTransform")
     cs = _input_set(x)
+    if isinstance(global_motion, M.RigidTransform):
+        if reference is None:
+            raise L.PccError("encode_geometry: a global motion transform needs the reference it moves")
+        return _encode_global(cs, reference_set(reference), global_motion, mode, segment_nodes, timings)
     if reference is None or mode == "intra" or cs.n == 0:
         return _encode_intra(cs, segment_nodes, timings)
     rs = reference_set(reference)
+    plain = _encode_against(cs, rs, mode, segment_nodes, timings)
+    if global_motion is None or rs is None:
+        return plain
+    T = M.estimate_rigid(cs, rs)
+    if T is None or T.is_identity():
+        return plain
+    tw = {} if timings is not None else None
+    wrapped = _encode_global(cs, rs, T, mode, segment_nodes, tw)
+    take = len(wrapped) < len(plain)
+    if timings is not None:
+        if take:                                   # the events of the stream that is returned, not of the discarded one
+            timings.clear()
+            timings.update(tw)
+        timings["global_bytes"], timings["plain_bytes"] = len(wrapped), len(plain)
+    return wrapped if take else plain
+
+
+def _encode_global(cs, rs, T, mode, segment_nodes, timings):
+    """The wrapper stream (0xA9) of the canonical set `cs`: the transform, then `cs` against the warped reference set."""
+    ws = M.warp_set(rs, T) if rs is not None else None
+    if ws is not None and ws.n == 0:
+        ws = None
+    inner = _encode_intra(cs, segment_nodes, timings) if (mode == "intra" or cs.n == 0) else _encode_against(cs, ws, mode, segment_nodes, timings)
+    return bytes([MAGIC_GLOBAL]) + T.pack() + inner
+
+
+def _encode_against(cs, rs, mode, segment_nodes, timings):
+    """The stream of the canonical non-empty set `cs` against the reference set `rs` (None: empty) under mode "inter" / "auto"."""
     inter = _encode_inter(cs, rs, segment_nodes, timings)
     if mode == "inter":
         return inter
@@ -878,8 +943,19 @@ def decode_geometry(data, device, as_set=False, reference=None, timings=None):
     dev = torch.device(device)
     if dev.type != "cuda":
         raise L.PccError("decode_geometry runs on a GPU (no CPU fallback)")
+    transform = hdr.get("transform")
+    if transform is not None:
+        data = bytes(data[hdr["inner"]:])              # (the payload spans of the dictionary count from here)
     if hdr.get("inter"):
-        return _decode_inter(hdr, data, dev, reference_set(reference, "decode_geometry"), as_set, timings)
+        if transform is None:
+            rs = reference_set(reference, "decode_geometry")
+        else:
+            # the warp takes the reference rows as they are -- the set of warped cells does not depend on their order -- and
+            # its one read (row count and bounds of the warped set) stands where the canonicalisation of the reference stood;
+            # every launch of it is sized by the reference's row count
+            rs = M.warp_set(reference, transform)
+            rs = rs if rs.n else None
+        return _decode_inter(hdr, data, dev, rs, as_set, timings)
     n, depth, origin = hdr["n"], hdr["depth"], hdr["origin"]
     if n == 0:
         empty = torch.empty((0, 3), dtype=torch.int32, device=dev)
@@ -966,16 +1042,28 @@ def decode_geometry(data, device, as_set=False, reference=None, timings=None):
 # ------------------------------------------------------------------------------------------------------------------------
 # sequences: frame i against frame i - 1
 # ------------------------------------------------------------------------------------------------------------------------
-def encode_sequence(frames, intra_period=32, mode="auto", segment_nodes=SEGMENT_NODES):
+def stream_transform(data):
+    """The RigidTransform of a global-motion stream (0xA9), None for any other stream.  PccError when the 49 bytes are cut short
+    or an entry is out of range."""
+    if len(data) < 1 or data[0] != MAGIC_GLOBAL:
+        return None
+    if len(data) < GLOBAL_HEADER:
+        raise L.PccError("geometry stream truncated inside the global-motion transform")
+    return M.RigidTransform.unpack(data[1:GLOBAL_HEADER])
+
+
+def encode_sequence(frames, intra_period=32, mode="auto", segment_nodes=SEGMENT_NODES, global_motion=None):
     """One stream per frame: frame i is coded against frame i - 1, every `intra_period`-th frame (0, intra_period, ...) without a
-    reference.  The coder is lossless, so the decoder's previous frame is the encoder's.  mode as in `encode_geometry`."""
+    reference.  The coder is lossless, so the decoder's previous frame is the encoder's.  mode and global_motion as in
+    `encode_geometry` (global_motion applies to the frames that have a reference; `decode_sequence` reads it from the streams)."""
     if int(intra_period) < 1:
         raise L.PccError(f"encode_sequence: intra_period {intra_period} must be at least 1")
     out, prev = [], None
     for i, frame in enumerate(frames):
         cs = _input_set(frame)
         ref = None if i % int(intra_period) == 0 else prev
-        out.append(encode_geometry(cs, segment_nodes=segment_nodes, reference=ref, mode=mode))
+        out.append(encode_geometry(cs, segment_nodes=segment_nodes, reference=ref, mode=mode,
+                                   global_motion=global_motion if ref is not None else None))
         prev = cs
     return out
 
