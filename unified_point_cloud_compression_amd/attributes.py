@@ -321,9 +321,41 @@ def _attribute_rows(cloud, attrs, what):
     return cloud, attrs.contiguous()
 
 
-def _intra_tail(what, sets, masks, offs, checks, coef, v_root, steps, depth, ch, rows, segment_symbols, dev, ev):
-    """(quantised root DC, side bytes, `u32 length | rANS container`) of the 0xB3 stream from the quantised rows and the root's
-    DC: the groups, their histograms, the member choice (one read), the member index and the coder (one read)."""
+def _encoder_input(what, cloud, attrs, reference, reference_attrs, mode, predict, chroma_qp_offset=0):
+    """The opening of both encoders: (canonical set, uint8 levels, their permutation, reference rows or None, depth, whether an
+    inter stream is coded).  Refusals in this order, those that need no launch first: the mode, the cloud's rows, the chroma
+    offset, the reference's rows, rows that repeat a voxel, too many points, attrs on another device, "inter" beyond depth 14.
+    An empty cloud comes back with depth 0 before the device is looked at."""
+    if mode not in ("auto", "inter", "intra"):
+        raise L.PccError(f"{what}: mode {mode!r} is not one of auto, inter, intra")
+    cloud, levels = _attribute_rows(cloud, attrs, what)
+    if not -128 <= int(chroma_qp_offset) <= 127:
+        raise L.PccError(f"{what}: chroma_qp_offset {chroma_qp_offset} does not fit the header's signed byte")
+    ref = None
+    if reference is not None and mode != "intra":                         # "intra" never looks at the reference
+        ref = _reference_rows(reference, reference_attrs, levels.shape[1], predict, what)
+    cs, perm, keep = G.canonical_rows(cloud, what)
+    if keep is not None:
+        raise L.PccError(f"{what}: {levels.shape[0] - cs.n} rows repeat a voxel; merge them first (voxelize.voxel_grid)")
+    if cs.n >= MAX_POINTS:
+        raise L.PccError(f"{what}: {cs.n} points, the limit is 2^26 - 1")
+    if cs.n == 0:
+        return cs, levels, perm, None, 0, False
+    if levels.device != cs.device:
+        raise L.PccError(f"{what}: points and attrs are on different devices")
+    depth = _depth_of(cs)
+    inter = ref is not None and cs.n >= 2
+    if inter and depth > INTER_MAX_DEPTH:
+        if mode == "inter":
+            raise L.PccError(f"{what}: inter streams exist up to depth {INTER_MAX_DEPTH}, the cloud has depth {depth}")
+        inter = False
+    return cs, levels, perm, ref, depth, inter
+
+
+def _intra_tail(what, sets, masks, offs, checks, coef, v_root, depth, ch, rows, segment_symbols, dev, ph):
+    """(root values as they are, side bytes, `u32 length | rANS container`) of an intra stream (0xB3, 0xB5) from the coded rows
+    and the root's values: the groups, their histograms, the member choice (one read), the member index and the coder (one
+    read).  ph: the caller's `geometry.Phases`."""
     parts = [v_root.reshape(-1), checks.reshape(-1)]
     if rows:
         idx = torch.empty(rows * ch, dtype=torch.int32, device=dev)
@@ -333,16 +365,15 @@ def _intra_tail(what, sets, masks, offs, checks, coef, v_root, steps, depth, ch,
         parts.append(hist)
     back = torch.cat(parts).cpu().numpy()                              # one read: root DC, the plan's checks, the histograms
     _check_plan(back[ch:ch + 4 * depth], sets, what)
-    dc = [quantise(int(back[c]), steps[c]) for c in range(ch)]
+    root = [int(back[c]) for c in range(ch)]
     side = choose_members(back[ch + 4 * depth:]) if rows else [0] * (depth * 6)
-    if ev:
-        ev[3].record()
+    ph.mark("index_hist_choose")
     body = b""
     if rows:
         d_side = torch.tensor(side, dtype=torch.int32, device=dev)
         _fill_index(masks, offs, sets, depth, ch, d_side, idx, rows)
-        body = _rans_body(coef, idx, rows * ch, segment_symbols, dev, what, ev[4] if ev else None)    # one read: size + container
-    return dc, side, body
+        body = _rans_body(coef, idx, rows * ch, segment_symbols, dev, what, ph)    # one read: size + container
+    return root, side, body
 
 
 @torch.no_grad()
@@ -360,46 +391,25 @@ def encode_attributes(cloud, qp, chroma_qp_offset=-2, colour=True, attrs=None, s
     (DESIGN.md 7f); "inter": the inter stream (fewer than two voxels still travel as intra; depth 15 raises); "intra", or no
     reference: today's stream byte for byte."""
     what = "encode_attributes"
-    if mode not in ("auto", "inter", "intra"):
-        raise L.PccError(f"{what}: mode {mode!r} is not one of auto, inter, intra")
-    cloud, levels = _attribute_rows(cloud, attrs, what)
-    if not -128 <= int(chroma_qp_offset) <= 127:
-        raise L.PccError(f"{what}: chroma_qp_offset {chroma_qp_offset} does not fit the header's signed byte")
+    cs, levels, perm, ref, depth, inter = _encoder_input(what, cloud, attrs, reference, reference_attrs, mode, True, chroma_qp_offset)
     qp, cqo = min(max(int(qp), QP_MIN), QP_MAX), int(chroma_qp_offset)
-    ref = None
-    if reference is not None and mode != "intra":                         # "intra" never looks at the reference
-        ref = _reference_rows(reference, reference_attrs, levels.shape[1], True, what)
-    cs, perm, keep = G.canonical_rows(cloud, what)
-    if keep is not None:
-        raise L.PccError(f"{what}: {levels.shape[0] - cs.n} rows repeat a voxel; merge them first (voxelize.voxel_grid)")
-    n, ch = cs.n, levels.shape[1]
-    if n >= MAX_POINTS:
-        raise L.PccError(f"{what}: {n} points, the limit is 2^26 - 1")
+    n, ch, dev = cs.n, levels.shape[1], cs.device
     colour = bool(colour) and ch == 3
     if n == 0:
         return HEADER.pack(MAGIC, 0, 0, ch, int(colour), qp, cqo) + b"\x00" * ch
-    dev = cs.device
-    if levels.device != dev:
-        raise L.PccError(f"{what}: points and attrs are on different devices")
+    if inter:
+        return _encode_inter_lossy(what, cs, levels, perm, ref, qp, cqo, colour, mode, segment_symbols, timings)
     steps = steps_for(qp, cqo, ch)
     h_steps = (C.c_int32 * ch)(*steps)
-    origin, depth = tuple(cs.bounds.lo), _depth_of(cs)
     rows = n - 1
-    if ref is not None and n >= 2:
-        if depth <= INTER_MAX_DEPTH:
-            return _encode_inter_lossy(what, cs, levels, perm, ref, qp, cqo, colour, mode, segment_symbols, timings)
-        if mode == "inter":
-            raise L.PccError(f"{what}: inter streams exist up to depth {INTER_MAX_DEPTH}, the cloud has depth {depth}")
     with torch.cuda.device(dev):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if timings is not None else None
-        sets = G.level_sets(cs, origin, depth)
-        if ev:
-            ev[0].record()
+        ph = G.Phases(timings is not None)
+        sets = G.level_sets(cs, tuple(cs.bounds.lo), depth)
+        ph.mark()
         values = torch.empty((n, ch), dtype=torch.int32, device=dev)
         L.call("pcc_raht_prepare", L.ptr(levels), L.ptr(perm), n, ch, int(colour), L.ptr(values), L.stream())
         masks, offs, checks = _plan(sets, depth, dev)
-        if ev:
-            ev[1].record()
+        ph.mark("prepare_plan")
         coef = torch.zeros((max(rows, 1), ch), dtype=torch.int32, device=dev)
         w_child, v_child = None, values
         for l in range(depth - 1, -1, -1):
@@ -408,18 +418,16 @@ def encode_attributes(cloud, qp, chroma_qp_offset=-2, colour=True, attrs=None, s
             L.call("pcc_raht_forward", *_level_args(sets[l], sets[l + 1]), L.ptr(offs[l]), L.ptr(w_child), L.ptr(v_child), ch, h_steps,
                    L.ptr(w), L.ptr(v), L.ptr(coef), sets[l].n - 1, rows, L.stream())
             w_child, v_child = w, v
-        if ev:
-            ev[2].record()
-        dc, side, body = _intra_tail(what, sets, masks, offs, checks, coef, v_child, steps, depth, ch, rows, segment_symbols, dev, ev)
+        ph.mark("forward")
+        root, side, body = _intra_tail(what, sets, masks, offs, checks, coef, v_child, depth, ch, rows, segment_symbols, dev, ph)
         if timings is not None:
             torch.cuda.synchronize(dev)
-            timings["stages_ms"] = {"prepare_plan": ev[0].elapsed_time(ev[1]), "forward": ev[1].elapsed_time(ev[2]),
-                                    "index_hist_choose": ev[2].elapsed_time(ev[3]),
-                                    "index_rans": ev[3].elapsed_time(ev[4]) if rows else 0.0}
+            timings["stages_ms"] = ph.report()
+            timings["stages_ms"].setdefault("index_rans", 0.0)             # (a single voxel has no rows to code)
             timings["host_reads_by_construction"] = 2 if rows else 1       # beyond those of building the level sets
     out = bytearray(HEADER.pack(MAGIC, n, depth, ch, int(colour), qp, cqo))
-    for q in dc:
-        out += _zigzag(q)
+    for q, step in zip(root, steps):
+        out += _zigzag(quantise(q, step))
     out += bytes(side)
     return bytes(out + body)
 
@@ -437,34 +445,16 @@ def decode_attributes(data, geometry, device=None, reference=None, reference_att
     what = "decode_attributes"
     hdr = parse_header(data, have_reference=reference is not None)
     inter = hdr["inter"]
-    ref = _reference_rows(reference, reference_attrs, hdr["channels"], True, what) if inter else None
-    if torch.is_tensor(geometry) and device is not None:
-        geometry = geometry.to(device)
-    cs = G.canonical_rows(geometry, what)[0]
+    cs, ref = _decoder_input(what, hdr, geometry, device, reference, reference_attrs)
     dev = cs.device
-    if dev.type != "cuda" or (device is not None and torch.device(device).type != "cuda"):
-        raise L.PccError(f"{what} runs on a GPU (no CPU fallback)")
     n, depth, ch, steps = hdr["n"], hdr["depth"], hdr["channels"], hdr["steps"]
-    if cs.n != n or (n and _depth_of(cs) != depth):
-        raise L.PccError(f"{what}: the stream codes {n} points at depth {depth}, the geometry has {cs.n} at depth "
-                         f"{_depth_of(cs) if cs.n else 0}")
     if n == 0:
         return torch.empty((0, ch), dtype=torch.uint8, device=dev)
     h_steps = (C.c_int32 * ch)(*steps)
     rows = n - 1
     with torch.cuda.device(dev):
-        ph = G._Phases(timings is not None)
-        ph.mark("start")
-        sets = G.level_sets(cs, tuple(cs.bounds.lo), depth)
-        ph.mark("level_sets_ms")
-        masks, offs, checks = _plan(sets, depth, dev)
-        weights = [None] * (depth + 1)                                      # the voxels weigh 1: no array
-        for l in range(depth - 1, -1, -1):
-            weights[l] = torch.empty(sets[l].n, dtype=torch.int32, device=dev)
-            L.call("pcc_raht_weights", *_level_args(sets[l], sets[l + 1]), L.ptr(weights[l + 1]), L.ptr(weights[l]), L.stream())
-        status = torch.zeros(2, dtype=torch.int32, device=dev)             # rANS status | clamp flag
-        coef = torch.zeros(max(rows, 1) * ch, dtype=torch.int32, device=dev)
-        ph.mark("plan_weights_ms")
+        ph = G.Phases(timings is not None)
+        sets, masks, offs, checks, weights, status, coef = _decoder_plan(cs, depth, ch, ph)
         first, hp, p_root = depth, None, None
         if inter:
             first = max(0, depth - G.BLOCK_LOG2)
@@ -473,9 +463,7 @@ def decode_attributes(data, geometry, device=None, reference=None, reference_att
             flag = status.data_ptr() + 4
             bargs, nb, match, tv, nr, _keep = _inter_state(cs, sets, tuple(cs.bounds.lo), depth, ref, ch, hdr["colour"], flag,
                                                            "pcc_raht_prepare")
-            m0, m1 = hdr["modes"]
-            bits = np.unpackbits(np.frombuffer(data, np.uint8, m1 - m0, m0), bitorder="little")[:nb]
-            d_mode = torch.from_numpy(bits.astype(np.int32)).to(dev)
+            d_mode = _block_modes(data, hdr, nb, dev)
             ph.mark("motion_match_ms")
             # the prediction's transform: P with the mode-0 blocks zeroed, then the same forward pass, rows left unquantised
             fill_sums = torch.empty((nb, ch + 1), dtype=torch.int32, device=dev)
@@ -515,16 +503,64 @@ def decode_attributes(data, geometry, device=None, reference=None, reference_att
         out = torch.empty((n, ch), dtype=torch.uint8, device=dev)
         L.call("pcc_raht_finish", L.ptr(v), n, ch, int(hdr["colour"]), L.ptr(out), L.stream())
         ph.mark("inverse_finish_ms")
-        back = torch.cat([status, checks.reshape(-1)]).cpu().numpy()         # the decode's one device->host read
-        if timings is not None:
-            torch.cuda.synchronize(dev)
-            timings["stages_ms"] = ph.report()
+        _decoder_read(what, "attribute stream", "a coefficient or a reconstructed value left the +-2^30 range", status, checks, sets, ph,
+                      timings)
+    return out
+
+
+def _decoder_input(what, hdr, geometry, device, reference, reference_attrs):
+    """(canonical set of the geometry on the GPU, the reference rows of an inter stream or None) of both decoders; refuses a
+    reference an inter stream cannot use, a geometry off the GPU and one whose n or depth are not the header's."""
+    ref = _reference_rows(reference, reference_attrs, hdr["channels"], True, what) if hdr["inter"] else None
+    if torch.is_tensor(geometry) and device is not None:
+        geometry = geometry.to(device)
+    cs = G.canonical_rows(geometry, what)[0]
+    if cs.device.type != "cuda" or (device is not None and torch.device(device).type != "cuda"):
+        raise L.PccError(f"{what} runs on a GPU (no CPU fallback)")
+    n, depth = hdr["n"], hdr["depth"]
+    if cs.n != n or (n and _depth_of(cs) != depth):
+        raise L.PccError(f"{what}: the stream codes {n} points at depth {depth}, the geometry has {cs.n} at depth "
+                         f"{_depth_of(cs) if cs.n else 0}")
+    return cs, ref
+
+
+def _decoder_plan(cs, depth, ch, ph):
+    """What both decoders build from the geometry alone: (level sets, masks, offsets and checks of `_plan`, int32 weights per
+    level, the status words rANS status | clamp flag, the zeroed coefficient rows)."""
+    dev = cs.device
+    ph.mark("start")
+    sets = G.level_sets(cs, tuple(cs.bounds.lo), depth)
+    ph.mark("level_sets_ms")
+    masks, offs, checks = _plan(sets, depth, dev)
+    weights = [None] * (depth + 1)                                          # the voxels weigh 1: no array
+    for l in range(depth - 1, -1, -1):
+        weights[l] = torch.empty(sets[l].n, dtype=torch.int32, device=dev)
+        L.call("pcc_raht_weights", *_level_args(sets[l], sets[l + 1]), L.ptr(weights[l + 1]), L.ptr(weights[l]), L.stream())
+    status = torch.zeros(2, dtype=torch.int32, device=dev)
+    coef = torch.zeros(max(cs.n - 1, 1) * ch, dtype=torch.int32, device=dev)
+    ph.mark("plan_weights_ms")
+    return sets, masks, offs, checks, weights, status, coef
+
+
+def _block_modes(data, hdr, blocks, dev):
+    """int32 mode per block of an inter stream, from the header's mode bytes."""
+    m0, m1 = hdr["modes"]
+    bits = np.unpackbits(np.frombuffer(data, np.uint8, m1 - m0, m0), bitorder="little")[:blocks]
+    return torch.from_numpy(bits.astype(np.int32)).to(dev)
+
+
+def _decoder_read(what, name, left, status, checks, sets, ph, timings):
+    """The decode's one device->host read and what it refuses: a geometry that does not expand level by level, a malformed
+    container, a value that `left` its range.  name: the stream's name in the refusals."""
+    back = torch.cat([status, checks.reshape(-1)]).cpu().numpy()
+    if timings is not None:
+        torch.cuda.synchronize(status.device)
+        timings["stages_ms"] = ph.report()
     _check_plan(back[2:], sets, what)
     if back[0] != 0:
-        raise L.PccError(f"attribute stream: malformed rANS container (status {int(back[0])})")
+        raise L.PccError(f"{name}: malformed rANS container (status {int(back[0])})")
     if back[1] != 0:
-        raise L.PccError("attribute stream: a coefficient or a reconstructed value left the +-2^30 range")
-    return out
+        raise L.PccError(f"{name}: {left}")
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -696,7 +732,7 @@ def _inter_state(cs, sets, origin, depth, ref, channels, colour, d_flag, prepare
     grid = blocks.grid() if (depth > bl and S.USE_GRID) else None         # the root's single node is searched
     bargs = (L.ptr(blocks.keys), blocks.n, *S.grid_args(grid), bl)
     match = torch.empty(cs.n, dtype=torch.int32, device=dev)
-    L.call("pcc_lift_inter_match", L.ptr(sets[depth].keys), cs.n, *bargs, L.ptr(vec), G.SEARCH, *G._ref_args(rs), *origin, L.ptr(match),
+    L.call("pcc_lift_inter_match", L.ptr(sets[depth].keys), cs.n, *bargs, L.ptr(vec), G.SEARCH, *G.ref_args(rs), *origin, L.ptr(match),
            d_flag, L.stream())
     if rs is None:
         return bargs, blocks.n, match, None, 0, (vec, grid)
@@ -707,15 +743,15 @@ def _inter_state(cs, sets, origin, depth, ref, channels, colour, d_flag, prepare
     return bargs, blocks.n, match, tv, rs.n, (vec, grid)
 
 
-def _rans_body(coef, idx, symbols, segment_symbols, dev, what, done=None):
-    """`u32 length | rANS container` of the symbol vector; one device->host read (size + container).  done: an event recorded
-    behind the coder's launches."""
+def _rans_body(coef, idx, symbols, segment_symbols, dev, what, ph=None):
+    """`u32 length | rANS container` of the symbol vector; one device->host read (size + container).  ph: `geometry.Phases`
+    that get the mark "index_rans" behind the coder's launches."""
     plan = R.Plan(symbols, 1, 1, segments_for(symbols, segment_symbols))
     cap = R.align8(plan.capacity)
     blob = torch.zeros(8 + cap, dtype=torch.uint8, device=dev)
     R.encode(_tables(dev), plan, coef, idx, blob.data_ptr() + 8, blob.data_ptr())
-    if done is not None:
-        done.record()
+    if ph is not None:
+        ph.mark("index_rans")
     host = blob.cpu().numpy()
     nb = int(host[:8].view(np.int64)[0])
     if not 0 < nb <= cap:
@@ -742,7 +778,7 @@ def _encode_inter_lossy(what, cs, levels, perm, ref, qp, cqo, colour, mode, segm
     origin, depth = tuple(cs.bounds.lo), _depth_of(cs)
     rows = n - 1
     with torch.cuda.device(dev):
-        ph = G._Phases(timings is not None)
+        ph = G.Phases(timings is not None)
         sets = G.level_sets(cs, origin, depth)
         ph.mark("start")
         d_flag = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -797,10 +833,10 @@ def _encode_inter_lossy(what, cs, levels, perm, ref, qp, cqo, colour, mode, segm
         out += bytes(side) + np.packbits(modes.astype(bool), bitorder="little").tobytes() + body
         intra = None
         if mode == "auto":
-            dc, side0, body0 = _intra_tail(what, sets, masks, offs, checks, coef, v_child, steps, depth, ch, rows, segment_symbols, dev, None)
+            dc, side0, body0 = _intra_tail(what, sets, masks, offs, checks, coef, v_child, depth, ch, rows, segment_symbols, dev, G.Phases(False))
             intra = bytearray(HEADER.pack(MAGIC, n, depth, ch, int(colour), qp, cqo))
-            for q in dc:
-                intra += _zigzag(q)
+            for q, step in zip(dc, steps):
+                intra += _zigzag(quantise(q, step))
             intra += bytes(side0) + body0
             ph.mark("intra_stream_ms")
         if timings is not None:
@@ -826,47 +862,26 @@ def encode_attributes_lossless(cloud, colour=True, attrs=None, predict=True, seg
     stream (fewer than two voxels still travel as intra; depth 15 raises); "intra", or no reference: today's stream byte for
     byte."""
     what = "encode_attributes_lossless"
-    if mode not in ("auto", "inter", "intra"):
-        raise L.PccError(f"{what}: mode {mode!r} is not one of auto, inter, intra")
-    cloud, levels = _attribute_rows(cloud, attrs, what)
-    ref = None
-    if reference is not None and mode != "intra":                         # "intra" never looks at the reference
-        ref = _reference_rows(reference, reference_attrs, levels.shape[1], bool(predict), what)
-    cs, perm, keep = G.canonical_rows(cloud, what)
-    if keep is not None:
-        raise L.PccError(f"{what}: {levels.shape[0] - cs.n} rows repeat a voxel; merge them first (voxelize.voxel_grid)")
-    n, ch = cs.n, levels.shape[1]
-    if n >= MAX_POINTS:
-        raise L.PccError(f"{what}: {n} points, the limit is 2^26 - 1")
+    cs, levels, perm, ref, depth, inter = _encoder_input(what, cloud, attrs, reference, reference_attrs, mode, bool(predict))
+    n, ch, dev = cs.n, levels.shape[1], cs.device
     colour, predict = bool(colour) and ch == 3, bool(predict)
     if n == 0:
         return LOSSLESS_HEADER.pack(LOSSLESS_MAGIC, 0, 0, ch, F_STORED)
-    dev = cs.device
-    if levels.device != dev:
-        raise L.PccError(f"{what}: points and attrs are on different devices")
-    origin, depth = tuple(cs.bounds.lo), _depth_of(cs)
+    origin = tuple(cs.bounds.lo)
     rows = n - 1
-    inter = ref is not None and mode != "intra" and n >= 2
-    if inter and depth > INTER_MAX_DEPTH:
-        if mode == "inter":
-            raise L.PccError(f"{what}: inter streams exist up to depth {INTER_MAX_DEPTH}, the cloud has depth {depth}")
-        inter = False
     with torch.cuda.device(dev):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)] if timings is not None else None
-        ph = G._Phases(timings is not None and inter)
+        ph = G.Phases(timings is not None)          # the stages of every stream, and under the key "inter" those only an inter stream has
         sets = G.level_sets(cs, origin, depth)
         if inter:
-            ph.mark("start")
+            ph.mark(None, "inter")
             d_flag = torch.zeros(1, dtype=torch.int32, device=dev)
             bargs, nb, match, tv, nr, _keep = _inter_state(cs, sets, origin, depth, ref, ch, colour, L.ptr(d_flag))
-            ph.mark("motion_match_ms")
-        if ev:
-            ev[0].record()
+            ph.mark("motion_match_ms", "inter")
+        ph.mark()
         values = torch.empty((n, ch), dtype=torch.int32, device=dev)
         L.call("pcc_lift_prepare", L.ptr(levels), L.ptr(perm), n, ch, int(colour), L.ptr(values), L.stream())
         masks, offs, checks = _plan(sets, depth, dev)
-        if ev:
-            ev[1].record()
+        ph.mark("prepare_plan")
         coef = torch.zeros((max(rows, 1), ch), dtype=torch.int32, device=dev)
         w, v = [None] * (depth + 1), [None] * depth + [values]
         for l in range(depth - 1, -1, -1):
@@ -874,8 +889,7 @@ def encode_attributes_lossless(cloud, colour=True, attrs=None, predict=True, seg
             v[l] = torch.empty((sets[l].n, ch), dtype=torch.int32, device=dev)
             L.call("pcc_lift_forward", *_level_args(sets[l], sets[l + 1]), L.ptr(offs[l]), L.ptr(w[l + 1]), L.ptr(v[l + 1]), ch, L.ptr(w[l]),
                    L.ptr(v[l]), L.ptr(coef), sets[l].n - 1, rows, L.stream())
-        if ev:
-            ev[2].record()
+        ph.mark("forward")
         last = depth - 1
         if predict and rows:
             for l in range(last if inter else depth):
@@ -886,28 +900,10 @@ def encode_attributes_lossless(cloud, colour=True, attrs=None, predict=True, seg
             sums = torch.empty((nb, 2), dtype=torch.int32, device=dev)
             L.call("pcc_lift_inter_residual", *_node_level_args(sets[last], sets[depth], last == 0), *bargs, L.ptr(offs[last]), L.ptr(v[last]),
                    ch, L.ptr(match), L.ptr(tv), nr, L.ptr(coef), L.ptr(coef_t), sets[last].n - 1, rows, L.ptr(sums), L.ptr(d_flag), L.stream())
-        if ev:
-            ev[3].record()
+        ph.mark("residual")
         out, stored = None, False
         if not inter or mode == "auto":
-            parts = [v[0].reshape(-1), checks.reshape(-1)]
-            if rows:
-                idx = torch.empty(rows * ch, dtype=torch.int32, device=dev)
-                hist = torch.empty(depth * 6 * N_SLOTS, dtype=torch.int32, device=dev)
-                _fill_index(masks, offs, sets, depth, ch, None, idx, rows)
-                L.call("pcc_raht_hist", L.ptr(coef), L.ptr(idx), rows * ch, depth * 6, L.ptr(hist), L.stream())
-                parts.append(hist)
-            back = torch.cat(parts).cpu().numpy()                          # one read: root values, the plan's checks, the histograms
-            _check_plan(back[ch:ch + 4 * depth], sets, what)
-            root = [int(back[c]) for c in range(ch)]
-            side = choose_members(back[ch + 4 * depth:]) if rows else [0] * (depth * 6)
-            if ev:
-                ev[4].record()
-            body = b""
-            if rows:
-                d_side = torch.tensor(side, dtype=torch.int32, device=dev)
-                _fill_index(masks, offs, sets, depth, ch, d_side, idx, rows)
-                body = _rans_body(coef, idx, rows * ch, segment_symbols, dev, what, ev[5] if ev else None)    # one read: size + container
+            root, side, body = _intra_tail(what, sets, masks, offs, checks, coef, v[0], depth, ch, rows, segment_symbols, dev, ph)
             out = bytearray(LOSSLESS_HEADER.pack(LOSSLESS_MAGIC, n, depth, ch, (F_COLOUR if colour else 0) | (F_PREDICT if predict else 0)))
             for q in root:
                 out += _zigzag(q)
@@ -919,7 +915,7 @@ def encode_attributes_lossless(cloud, colour=True, attrs=None, predict=True, seg
         if inter:
             # the select pass: modes from the block sums, the temporal rows of mode-1 blocks into coef, their rows into the groups
             # of level `depth`; then the members, the member index and the container as above
-            ph.mark("before_select")
+            ph.mark(None, "inter")
             groups = (depth + 1) * 6
             node = sets[last]
             d_mode = torch.empty(nb, dtype=torch.int32, device=dev)
@@ -937,13 +933,13 @@ def encode_attributes_lossless(cloud, colour=True, attrs=None, predict=True, seg
                 raise L.PccError(f"{what}: the blocks, vectors or matches of the cloud are inconsistent")
             modes = np.packbits(back[at + 1:at + 1 + nb].astype(bool), bitorder="little").tobytes()
             side = choose_members(back[at + 1 + nb:])
-            ph.mark("select_hist_choose_ms")
+            ph.mark("select_hist_choose_ms", "inter")
             d_side = torch.tensor(side, dtype=torch.int32, device=dev)
             _fill_index(masks, offs, sets, last, ch, d_side, idx, rows)
             L.call("pcc_lift_inter_select", *sel, None, L.ptr(d_mode), L.ptr(d_side), L.ptr(idx), None, None, node.n - 1, rows, L.ptr(d_flag),
                    L.stream())
             body = _rans_body(coef, idx, rows * ch, segment_symbols, dev, what)          # one read: size + container
-            ph.mark("inter_index_rans_ms")
+            ph.mark("inter_index_rans_ms", "inter")
             coded = bytearray(INTER_HEADER.pack(INTER_MAGIC, n, depth, ch, F_PREDICT | (F_COLOUR if colour else 0), G.BLOCK_LOG2, G.SEARCH, nb))
             for c in range(ch):
                 coded += _zigzag(int(back[c]))
@@ -955,14 +951,13 @@ def encode_attributes_lossless(cloud, colour=True, attrs=None, predict=True, seg
                 out = coded
         if timings is not None:
             torch.cuda.synchronize(dev)
-            timings["stages_ms"] = {"prepare_plan": ev[0].elapsed_time(ev[1]), "forward": ev[1].elapsed_time(ev[2]),
-                                    "residual": ev[2].elapsed_time(ev[3])}
+            timings["stages_ms"] = ph.report()
             if not inter or mode == "auto":
-                timings["stages_ms"].update({"index_hist_choose": ev[3].elapsed_time(ev[4]), "index_rans": ev[4].elapsed_time(ev[5]) if rows else 0.0})
+                timings["stages_ms"].setdefault("index_rans", 0.0)         # (a single voxel has no rows to code)
                 timings["host_reads_by_construction"] = (2 if rows else 1) + int(stored)   # beyond those of building the level sets
                 timings["stored"] = stored
             if inter:
-                timings["inter_stages_ms"] = {k: val for k, val in ph.report().items() if k != "before_select"}
+                timings["inter_stages_ms"] = ph.report("inter")
     return bytes(out)
 
 
@@ -979,17 +974,9 @@ def decode_attributes_lossless(data, geometry, device=None, reference=None, refe
     what = "decode_attributes_lossless"
     hdr = parse_lossless_header(data, have_reference=reference is not None)
     inter = hdr["inter"]
-    ref = _reference_rows(reference, reference_attrs, hdr["channels"], True, what) if inter else None
-    if torch.is_tensor(geometry) and device is not None:
-        geometry = geometry.to(device)
-    cs = G.canonical_rows(geometry, what)[0]
+    cs, ref = _decoder_input(what, hdr, geometry, device, reference, reference_attrs)
     dev = cs.device
-    if dev.type != "cuda" or (device is not None and torch.device(device).type != "cuda"):
-        raise L.PccError(f"{what} runs on a GPU (no CPU fallback)")
     n, depth, ch, colour, predict = hdr["n"], hdr["depth"], hdr["channels"], hdr["colour"], hdr["predict"]
-    if cs.n != n or (n and _depth_of(cs) != depth):
-        raise L.PccError(f"{what}: the stream codes {n} points at depth {depth}, the geometry has {cs.n} at depth "
-                         f"{_depth_of(cs) if cs.n else 0}")
     if n == 0:
         return torch.empty((0, ch), dtype=torch.uint8, device=dev)
     if hdr["stored"]:
@@ -997,26 +984,14 @@ def decode_attributes_lossless(data, geometry, device=None, reference=None, refe
         return torch.from_numpy(np.frombuffer(data, np.uint8, b1 - b0, b0).reshape(n, ch).copy()).to(dev)
     rows = n - 1
     with torch.cuda.device(dev):
-        ph = G._Phases(timings is not None)
-        ph.mark("start")
-        sets = G.level_sets(cs, tuple(cs.bounds.lo), depth)
-        ph.mark("level_sets_ms")
-        masks, offs, checks = _plan(sets, depth, dev)
-        weights = [None] * (depth + 1)                                      # the voxels weigh 1: no array
-        for l in range(depth - 1, -1, -1):
-            weights[l] = torch.empty(sets[l].n, dtype=torch.int32, device=dev)
-            L.call("pcc_raht_weights", *_level_args(sets[l], sets[l + 1]), L.ptr(weights[l + 1]), L.ptr(weights[l]), L.stream())
-        status = torch.zeros(2, dtype=torch.int32, device=dev)             # rANS status | clamp flag
-        coef = torch.zeros(max(rows, 1) * ch, dtype=torch.int32, device=dev)
+        ph = G.Phases(timings is not None)
+        sets, masks, offs, checks, weights, status, coef = _decoder_plan(cs, depth, ch, ph)
         last = depth - 1
-        ph.mark("plan_weights_ms")
         if inter:
             if hdr["blocks"] != sets[max(0, depth - G.BLOCK_LOG2)].n:
                 raise L.PccError(f"{what}: the stream codes {hdr['blocks']} blocks, the geometry has {sets[max(0, depth - G.BLOCK_LOG2)].n}")
             bargs, nb, match, tv, nr, _keep = _inter_state(cs, sets, tuple(cs.bounds.lo), depth, ref, ch, colour, status.data_ptr() + 4)
-            m0, m1 = hdr["modes"]
-            bits = np.unpackbits(np.frombuffer(data, np.uint8, m1 - m0, m0), bitorder="little")[:nb]
-            d_mode = torch.from_numpy(bits.astype(np.int32)).to(dev)
+            d_mode = _block_modes(data, hdr, nb, dev)
             ph.mark("motion_match_ms")
         if rows:
             b0, b1 = hdr["payload"]
@@ -1043,13 +1018,6 @@ def decode_attributes_lossless(data, geometry, device=None, reference=None, refe
         out = torch.empty((n, ch), dtype=torch.uint8, device=dev)
         L.call("pcc_lift_finish", L.ptr(v), n, ch, int(colour), L.ptr(out), status.data_ptr() + 4, L.stream())
         ph.mark("inverse_finish_ms")
-        back = torch.cat([status, checks.reshape(-1)]).cpu().numpy()         # the decode's one device->host read
-        if timings is not None:
-            torch.cuda.synchronize(dev)
-            timings["stages_ms"] = ph.report()
-    _check_plan(back[2:], sets, what)
-    if back[0] != 0:
-        raise L.PccError(f"lossless attribute stream: malformed rANS container (status {int(back[0])})")
-    if back[1] != 0:
-        raise L.PccError("lossless attribute stream: a symbol, a reconstructed value or a level left its legal range")
+        _decoder_read(what, "lossless attribute stream", "a symbol, a reconstructed value or a level left its legal range", status, checks,
+                      sets, ph, timings)
     return out

@@ -51,6 +51,7 @@ come (no canonicalisation first: the set of warped cells does not depend on thei
 canonicalisation of the reference would have cost, and decodes the inner stream as before.
 """
 import ctypes as C
+import itertools
 import struct
 
 import numpy as np
@@ -77,17 +78,6 @@ POPCOUNT = np.array([bin(v).count("1") for v in range(256)], dtype=np.int64)
 def segments_for(nodes, segment_nodes=SEGMENT_NODES):
     """Row segments (= rANS streams) of a coded level."""
     return R.segments_for(nodes, segment_nodes, 65536)
-
-
-class TableState:
-    """Backward-adaptive (context, byte) counts.  After every level (raw ones included) the old counts are halved and the
-    level's histogram [64, 256] is added."""
-
-    def __init__(self):
-        self.counts = np.zeros((N_CTX, 256), dtype=np.int64)
-
-    def update(self, hist):
-        self.counts = (self.counts >> 1) + np.asarray(hist, dtype=np.int64).reshape(N_CTX, 256)
 
 
 def derive_tables(counts, pop):
@@ -440,7 +430,7 @@ def encode_geometry(x, segment_nodes=SEGMENT_NODES, timings=None, reference=None
             raise L.PccError("encode_geometry: a global motion transform needs the reference it moves")
         return _encode_global(cs, reference_set(reference), global_motion, mode, segment_nodes, timings)
     if reference is None or mode == "intra" or cs.n == 0:
-        return _encode_intra(cs, segment_nodes, timings)
+        return _encode(cs, INTRA, segment_nodes, timings)
     rs = reference_set(reference)
     plain = _encode_against(cs, rs, mode, segment_nodes, timings)
     if global_motion is None or rs is None:
@@ -464,44 +454,50 @@ def _encode_global(cs, rs, T, mode, segment_nodes, timings):
     ws = M.warp_set(rs, T) if rs is not None else None
     if ws is not None and ws.n == 0:
         ws = None
-    inner = _encode_intra(cs, segment_nodes, timings) if (mode == "intra" or cs.n == 0) else _encode_against(cs, ws, mode, segment_nodes, timings)
+    inner = _encode(cs, INTRA, segment_nodes, timings) if (mode == "intra" or cs.n == 0) else _encode_against(cs, ws, mode, segment_nodes, timings)
     return bytes([MAGIC_GLOBAL]) + T.pack() + inner
 
 
 def _encode_against(cs, rs, mode, segment_nodes, timings):
     """The stream of the canonical non-empty set `cs` against the reference set `rs` (None: empty) under mode "inter" / "auto"."""
-    inter = _encode_inter(cs, rs, segment_nodes, timings)
+    inter = _encode(cs, rs, segment_nodes, timings)
     if mode == "inter":
         return inter
-    intra = _encode_intra(cs, segment_nodes, None)
+    intra = _encode(cs, INTRA, segment_nodes, None)
     if timings is not None:
         timings["inter_bytes"], timings["intra_bytes"] = len(inter), len(intra)
     return inter if len(inter) < len(intra) else intra
 
 
-def _ref_args(rs):
+def ref_args(rs):
     """Kernel arguments (keys, n, bits, rank, h) of a reference set; None: the empty reference."""
     if rs is None:
         return None, 0, None, None, None
     return (L.ptr(rs.keys), rs.n, *S.grid_args(rs.grid() if S.USE_GRID else None))
 
 
-class _Phases:
-    """Device time between named marks (tools/geometry_inter_timing.py); inert when the caller asked for no timings."""
+class Phases:
+    """Device time between consecutive marks, under the later mark's name (a mark without a name only starts a span); inert
+    when the caller asked for no timings.  Two series run side by side and do not cut each other's spans: the marks that carry
+    a level (a level number -- an intra stream's rows, tools/geometry_timing.py -- or any other key) and the marks that carry
+    none (the phases of a whole call, tools/geometry_inter_timing.py)."""
 
     def __init__(self, on):
         self.marks = [] if on else None
 
-    def mark(self, name):
+    def mark(self, name=None, level=None):
         if self.marks is not None:
             ev = torch.cuda.Event(enable_timing=True)
             ev.record()
-            self.marks.append((name, ev))
+            self.marks.append((name, level, ev))
 
-    def report(self):
+    def report(self, level=None):
+        """name -> ms of the series `level` belongs to, summed over the marks of `level`."""
+        series = [m for m in self.marks if (m[1] is None) == (level is None)]
         out = {}
-        for (_, a), (name, b) in zip(self.marks[:-1], self.marks[1:]):
-            out[name] = out.get(name, 0.0) + a.elapsed_time(b)
+        for (_, _, a), (name, at, b) in zip(series[:-1], series[1:]):
+            if name is not None and at == level:
+                out[name] = out.get(name, 0.0) + a.elapsed_time(b)
         return out
 
 
@@ -521,73 +517,90 @@ def motion_vectors(cs, rs, origin, depth, sets=None, counts=False):
     cnt = torch.empty((blocks.n, (2 * SEARCH + 1) ** 3), dtype=torch.int32, device=dev) if counts else None
     L.call("pcc_geom_inter_block_bits", L.ptr(blocks.keys), blocks.n, bl, L.ptr(voxels.keys), voxels.n,
            *S.grid_args(voxels.grid() if S.USE_GRID else None), 0, 0, 0, None, SEARCH, L.ptr(cur), L.ptr(bad), L.stream())
-    L.call("pcc_geom_inter_motion", L.ptr(blocks.keys), blocks.n, bl, L.ptr(cur), *_ref_args(rs), *origin, SEARCH, L.ptr(cnt), L.ptr(vec),
+    L.call("pcc_geom_inter_motion", L.ptr(blocks.keys), blocks.n, bl, L.ptr(cur), *ref_args(rs), *origin, SEARCH, L.ptr(cnt), L.ptr(vec),
            L.stream())
     return (blocks, bl, cur, vec, cnt) if counts else (blocks, bl, cur, vec)
 
 
-def _encode_inter(cs, rs, segment_nodes, timings):
-    """The inter stream (0xA8) of the canonical non-empty set `cs` against the reference set `rs` (None: empty).  Device->host
-    reads: those of the intra encoder -- the vectors travel with the raw levels' bytes."""
+INTRA = object()          # `_encode(cs, INTRA, ...)`: no reference at all (None is the empty reference of an inter stream)
+
+
+def _encode(cs, rs, segment_nodes, timings):
+    """The stream of the canonical set `cs`: intra (0xA7) when `rs` is INTRA, else inter (0xA8) against the reference set `rs`
+    (None: empty).  One walk over the levels: those above `first` (= depth for an intra stream) take the intra kernels, the
+    others the inter ones.  Device->host reads: bounds, level sizes, every level's histograms, the raw levels' bytes (an inter
+    stream's vectors ride in that read), the payload."""
     n = cs.n
+    if n == 0:
+        return HEADER.pack(MAGIC, 0, 0, 0, 0, 0)
+    inter = rs is not INTRA
     origin = tuple(cs.bounds.lo)
     depth = max(1, max(cs.bounds.hi[i] - origin[i] for i in range(3)).bit_length())
-    first = max(0, depth - BLOCK_LOG2)
+    first = max(0, depth - BLOCK_LOG2) if inter else depth
+    rows = N_ROWS if inter else N_CTX
     k_vec = (2 * SEARCH + 1) ** 3
     dev = cs.device
     lib = L.load()
-    ph = _Phases(timings is not None)
+    ph = Phases(timings is not None)
     with torch.cuda.device(dev):
-        ph.mark("start")
+        ph.mark()
         sets = level_sets(cs, origin, depth)
         ph.mark("level_sets_ms")
-        blocks, bl, _, vec = motion_vectors(cs, rs, origin, depth, sets)
-        ph.mark("motion_search_ms")
-        nb = blocks.n
-        bgrid = blocks.grid() if (first and S.USE_GRID) else None
-        bad = torch.zeros(1, dtype=torch.int32, device=dev)
-        pred = torch.empty(nb * lib.pcc_geom_inter_pyramid_words(), dtype=torch.int64, device=dev)
-        L.call("pcc_geom_inter_block_bits", L.ptr(blocks.keys), nb, bl, *_ref_args(rs), *origin, L.ptr(vec), SEARCH, L.ptr(pred), L.ptr(bad),
-               L.stream())
-        ph.mark("compensation_ms")
-        hw, hwi = lib.pcc_geom_hist_words(), lib.pcc_geom_inter_hist_words()
         nodes = [s.n for s in sets[:depth]]
         at = np.concatenate([[0], np.cumsum(nodes)]).tolist()
         sym = torch.empty(at[-1], dtype=torch.int32, device=dev)        # what the rANS coder sees
-        idx = torch.empty(at[-1], dtype=torch.int32, device=dev)        # its table row: context + 64 * present
-        byte = torch.empty(at[-1], dtype=torch.int32, device=dev)       # the occupancy bytes of the inter levels (raw levels travel as these)
-        hist = torch.zeros(first * hw + (depth - first) * hwi, dtype=torch.int32, device=dev)
-        h_at = [l * hw if l < first else first * hw + (l - first) * hwi for l in range(depth)]
+        idx = torch.empty(at[-1], dtype=torch.int32, device=dev)        # its table row: context (+ 64 * present in an inter level)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        words = [lib.pcc_geom_hist_words()] * first
+        nb = 0
+        if inter:
+            blocks, bl, _, vec = motion_vectors(cs, rs, origin, depth, sets)
+            ph.mark("motion_search_ms")
+            nb = blocks.n
+            bgrid = blocks.grid() if (first and S.USE_GRID) else None
+            pred = torch.empty(nb * lib.pcc_geom_inter_pyramid_words(), dtype=torch.int64, device=dev)
+            L.call("pcc_geom_inter_block_bits", L.ptr(blocks.keys), nb, bl, *ref_args(rs), *origin, L.ptr(vec), SEARCH, L.ptr(pred), L.ptr(bad),
+                   L.stream())
+            ph.mark("compensation_ms")
+            byte = torch.empty(at[-1], dtype=torch.int32, device=dev)   # the occupancy bytes of the inter levels (raw levels travel as these)
+            words += [lib.pcc_geom_inter_hist_words()] * (depth - first)
+        h_at = [0, *itertools.accumulate(words)]
+        hist = torch.zeros(h_at[-1], dtype=torch.int32, device=dev)
         for l in range(depth):
             node, child = sets[l], sets[l + 1]
             sp, ip, hp = sym.data_ptr() + 4 * at[l], idx.data_ptr() + 4 * at[l], hist.data_ptr() + 4 * h_at[l]
+            ph.mark(None, l)                                               # (a set without a grid index builds it in `grid()`: the level's time)
             ngrid = S.grid_args(node.grid() if (l and S.USE_GRID) else None)
             cgrid = S.grid_args(child.grid() if S.USE_GRID else None)
             if l < first:
                 L.call("pcc_geom_occ_ctx", L.ptr(node.keys), node.n, node.ts, *ngrid, L.ptr(child.keys), child.n, *cgrid, sp, ip, L.stream())
+                ph.mark("occ_ctx_ms", l)
                 L.call("pcc_geom_hist", sp, ip, node.n, hp, L.ptr(bad), L.stream())
             else:
                 L.call("pcc_geom_inter_occ_ctx", L.ptr(node.keys), node.n, node.ts, *ngrid, L.ptr(child.keys), child.n, *cgrid,
                        L.ptr(blocks.keys), nb, *S.grid_args(bgrid), bl, L.ptr(pred), byte.data_ptr() + 4 * at[l], sp, None, ip, L.stream())
                 L.call("pcc_geom_inter_hist", sp, ip, node.n, hp, L.ptr(bad), L.stream())
+            ph.mark("hist_ms", l)
         ph.mark("symbols_hist_ms")
         h_hist = hist.cpu().numpy().astype(np.int64)                       # one read: every level's histograms
         raw_lv = [l for l in range(depth) if nodes[l] < RAW_NODES]
-        parts = [(sym if l < first else byte)[at[l]:at[l + 1]] for l in raw_lv] + [vec]
-        got = torch.cat(parts).to(torch.uint8).cpu().numpy()               # one read: the raw levels' bytes and the vectors
-        raw_bytes, p = {}, 0
-        for l in raw_lv:
-            raw_bytes[l] = got[p:p + nodes[l]].tobytes()
-            p += nodes[l]
-        h_vec = got[p:p + nb]
-        # containers: the vector list (when it is coded) and the coded levels, one rANS launch each into a shared blob
-        state = np.zeros((N_ROWS, 256), dtype=np.int64)
-        coded = [l for l in range(depth) if nodes[l] >= RAW_NODES]
-        code_vec = k_vec > 1 and nb >= RAW_NODES
-        jobs = (["vec"] if code_vec else []) + coded
-        plans = {l: R.Plan(nodes[l], 1, 1, segments_for(nodes[l], segment_nodes)) for l in coded}
+        parts = [(sym if l < first else byte)[at[l]:at[l + 1]] for l in raw_lv] + ([vec] if inter else [])
+        raw_bytes, h_vec = {}, None
+        if parts:
+            got = torch.cat(parts).to(torch.uint8).cpu().numpy()           # one read: the raw levels' bytes and the vectors
+            p = 0
+            for l in raw_lv:
+                raw_bytes[l] = got[p:p + nodes[l]].tobytes()
+                p += nodes[l]
+            h_vec = got[p:p + nb]
+        # containers: the vector list (when it is coded) and the coded levels, tables from the levels before, one rANS launch each
+        # into a shared blob [sizes | containers]
+        code_vec = inter and k_vec > 1 and nb >= RAW_NODES
+        symbols = {l: nodes[l] for l in range(depth) if nodes[l] >= RAW_NODES}
         if code_vec:
-            plans["vec"] = R.Plan(nb, 1, 1, segments_for(nb, segment_nodes))
+            symbols = {"vec": nb, **symbols}
+        jobs = list(symbols)
+        plans = {j: R.Plan(symbols[j], 1, 1, segments_for(symbols[j], segment_nodes)) for j in jobs}
         caps = {j: R.align8(plans[j].capacity) for j in jobs}
         head = 8 * max(len(jobs), 1)
         blob = torch.zeros(head + sum(caps.values()), dtype=torch.uint8, device=dev)
@@ -596,7 +609,9 @@ def _encode_inter(cs, rs, segment_nodes, timings):
         def run(job, tabs, sp, ip):
             nonlocal begin
             keep.append(tabs)
+            ph.mark(None, job)
             R.encode(tabs, plans[job], sp, ip, blob.data_ptr() + begin, blob.data_ptr() + 8 * jobs.index(job))
+            ph.mark("rans_ms", job)
             where[job] = (begin, caps[job])
             begin += caps[job]
 
@@ -606,19 +621,21 @@ def _encode_inter(cs, rs, segment_nodes, timings):
             keep.append(v_idx)
             run("vec", R.fresh_cdf_tables(f"geometry_vectors{k_vec}", dev, vector_table(v_hist), np.array([k_vec + 2], dtype=np.int32),
                                           np.zeros(1, dtype=np.int32)), L.ptr(vec), L.ptr(v_idx))
+        # backward-adaptive (row, byte) counts: after every level (raw ones included) the old counts are halved and the level's are added
+        state = np.zeros((rows, 256), dtype=np.int64)
+        side = {}
         for l in range(depth):
-            h = h_hist[h_at[l]:h_at[l] + (hw if l < first else hwi)]
-            sp, ip = sym.data_ptr() + 4 * at[l], idx.data_ptr() + 4 * at[l]
-            if l < first:
-                if l in plans:
-                    run(l, R.fresh_cdf_tables("geometry", dev, derive_tables(state[:N_CTX], h[N_CTX * 256:]), TABLE_SIZES, TABLE_OFFSETS), sp, ip)
-                state = state >> 1
-                state[:N_CTX] += h[:N_CTX * 256].reshape(N_CTX, 256)
-            else:
-                if l in plans:
-                    cdf = derive_tables_inter(state, h[N_ROWS * 256:N_ROWS * 256 + 8], h[N_ROWS * 256 + 8:])
-                    run(l, R.fresh_cdf_tables("geometry_inter", dev, cdf, INTER_SIZES, INTER_OFFSETS), sp, ip)
-                state = (state >> 1) + h[:N_ROWS * 256].reshape(N_ROWS, 256)
+            h = h_hist[h_at[l]:h_at[l + 1]]
+            r = N_CTX if l < first else N_ROWS
+            if l in plans:
+                side[l] = [int(v) for v in h[r * 256:]]                      # popcount classes (8), then an inter level's distance classes (9)
+                if l < first:
+                    tabs = R.fresh_cdf_tables("geometry", dev, derive_tables(state[:N_CTX], side[l]), TABLE_SIZES, TABLE_OFFSETS)
+                else:
+                    tabs = R.fresh_cdf_tables("geometry_inter", dev, derive_tables_inter(state, side[l][:8], side[l][8:]), INTER_SIZES, INTER_OFFSETS)
+                run(l, tabs, sym.data_ptr() + 4 * at[l], idx.data_ptr() + 4 * at[l])
+            state >>= 1
+            state[:r] += h[:r * 256].reshape(r, 256)
         ph.mark("tables_rans_ms")
         host = blob.cpu().numpy()                                          # one read: sizes + containers
         sizes = host[:head].view(np.int64)
@@ -626,12 +643,12 @@ def _encode_inter(cs, rs, segment_nodes, timings):
 
     def container(job):
         b0, cap = where[job]
-        nb_ = int(sizes[jobs.index(job)])
-        if not 0 < nb_ <= cap:
-            raise L.PccError(f"encode_geometry: container {job} produced {nb_} bytes for a capacity of {cap}")
-        return host[b0:b0 + nb_].tobytes()
+        got = int(sizes[jobs.index(job)])
+        if not 0 < got <= cap:
+            raise L.PccError(f"encode_geometry: {'container' if inter else 'level'} {job} produced {got} bytes for a capacity of {cap}")
+        return host[b0:b0 + got].tobytes()
 
-    out = bytearray(HEADER_INTER.pack(MAGIC_INTER, n, depth, *origin, BLOCK_LOG2, SEARCH))
+    out = bytearray(HEADER_INTER.pack(MAGIC_INTER, n, depth, *origin, BLOCK_LOG2, SEARCH) if inter else HEADER.pack(MAGIC, n, depth, *origin))
     for l in range(depth):
         if l == first and k_vec > 1:
             if code_vec:
@@ -644,111 +661,22 @@ def _encode_inter(cs, rs, segment_nodes, timings):
         if l in raw_bytes:
             out += raw_bytes[l]
             continue
-        h = h_hist[h_at[l]:h_at[l] + (hw if l < first else hwi)]
         body = container(l)
         if l < first:
-            out += SIDE.pack(*[int(v) for v in h[N_CTX * 256:]], len(body))
+            out += SIDE.pack(*side[l], len(body))
         else:
-            pop, dist = [int(v) for v in h[N_ROWS * 256:N_ROWS * 256 + 8]], [int(v) for v in h[N_ROWS * 256 + 8:]]
             # (the distance classes do not give the child total, so it travels: the next level's node count)
-            out += SIDE_INTER.pack(*pop, *dist, nodes[l + 1] if l + 1 < depth else n, len(body))
+            out += SIDE_INTER.pack(*side[l], nodes[l + 1] if l + 1 < depth else n, len(body))
         out += body
     if timings is not None:
         torch.cuda.synchronize(dev)
-        timings["inter"] = ph.report()
-        timings["blocks"] = nb
-        timings["zero_vectors"] = int((h_vec == 0).sum())
-        timings["host_reads_by_construction"] = 3 + 1 + 1                  # bounds, level sizes, histograms | bytes + vectors | payload
-    return bytes(out)
-
-
-def _encode_intra(cs, segment_nodes, timings):
-    """The intra stream (0xA7) of the canonical set `cs`."""
-    n = cs.n
-    origin = tuple(cs.bounds.lo)
-    if n == 0:
-        return HEADER.pack(MAGIC, 0, 0, 0, 0, 0)
-    depth = max(1, max(cs.bounds.hi[i] - origin[i] for i in range(3)).bit_length())
-    dev = cs.device
-    lib = L.load()
-    with torch.cuda.device(dev):
-        sets = level_sets(cs, origin, depth)
-        hw = lib.pcc_geom_hist_words()
-        nodes = [s.n for s in sets[:depth]]
-        at = np.concatenate([[0], np.cumsum(nodes)]).tolist()
-        sym = torch.empty(at[-1], dtype=torch.int32, device=dev)
-        ctx = torch.empty(at[-1], dtype=torch.int32, device=dev)
-        hist = torch.zeros((depth, hw), dtype=torch.int32, device=dev)
-        bad = torch.zeros(1, dtype=torch.int32, device=dev)
-        ev = []
-        for l in range(depth):
-            node, child = sets[l], sets[l + 1]
-            if timings is not None:
-                ev.append([torch.cuda.Event(enable_timing=True) for _ in range(3)])
-                ev[l][0].record()
-            L.call("pcc_geom_occ_ctx", L.ptr(node.keys), node.n, node.ts, *S.grid_args(node.grid() if (l and S.USE_GRID) else None),
-                   L.ptr(child.keys), child.n, *S.grid_args(child.grid() if S.USE_GRID else None), sym.data_ptr() + 4 * at[l], ctx.data_ptr() + 4 * at[l],
-                   L.stream())
-            if timings is not None:
-                ev[l][1].record()
-            L.call("pcc_geom_hist", sym.data_ptr() + 4 * at[l], ctx.data_ptr() + 4 * at[l], node.n, hist[l].data_ptr(), L.ptr(bad),
-                   L.stream())
-            if timings is not None:
-                ev[l][2].record()
-        h_hist = hist.cpu().numpy().astype(np.int64)                       # one read: every level's histograms
-        raw_lv = [l for l in range(depth) if nodes[l] < RAW_NODES]
-        raw_bytes = {}
-        if raw_lv:
-            got = torch.cat([sym[at[l]:at[l + 1]] for l in raw_lv]).to(torch.uint8).cpu().numpy().tobytes()   # one read
-            p = 0
-            for l in raw_lv:
-                raw_bytes[l] = got[p:p + nodes[l]]
-                p += nodes[l]
-        # coded levels: tables from the levels before, one rANS launch each into a shared blob [sizes | containers]
-        state = TableState()
-        coded = [l for l in range(depth) if nodes[l] >= RAW_NODES]
-        plans = {l: R.Plan(nodes[l], 1, 1, segments_for(nodes[l], segment_nodes)) for l in coded}
-        caps = {l: R.align8(plans[l].capacity) for l in coded}
-        head = 8 * max(len(coded), 1)
-        blob = torch.zeros(head + sum(caps.values()), dtype=torch.uint8, device=dev)
-        begin, keep, where = head, [], {}
-        t_code = []
-        for l in range(depth):
-            if l in plans:
-                tabs = R.fresh_cdf_tables("geometry", dev, derive_tables(state.counts, h_hist[l, N_CTX * 256:]), TABLE_SIZES, TABLE_OFFSETS)
-                keep.append(tabs)
-                if timings is not None:
-                    t_code.append((l, torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
-                    t_code[-1][1].record()
-                R.encode(tabs, plans[l], sym.data_ptr() + 4 * at[l], ctx.data_ptr() + 4 * at[l], blob.data_ptr() + begin,
-                         blob.data_ptr() + 8 * coded.index(l))
-                if timings is not None:
-                    t_code[-1][2].record()
-                where[l] = (begin, caps[l])
-                begin += caps[l]
-            state.update(h_hist[l, :N_CTX * 256])
-        host = blob.cpu().numpy()                                          # one read: sizes + containers
-        sizes = host[:head].view(np.int64)
-    out = bytearray(HEADER.pack(MAGIC, n, depth, *origin))
-    for l in range(depth):
-        if l in raw_bytes:
-            out += raw_bytes[l]
+        if inter:
+            timings.update(inter=ph.report(), blocks=nb, zero_vectors=int((h_vec == 0).sum()))
         else:
-            b0, cap = where[l]
-            nb = int(sizes[coded.index(l)])
-            if not 0 < nb <= cap:
-                raise L.PccError(f"encode_geometry: level {l} produced {nb} bytes for a capacity of {cap}")
-            out += SIDE.pack(*[int(v) for v in h_hist[l, N_CTX * 256:]], nb)
-            out += host[b0:b0 + nb].tobytes()
-    if timings is not None:
-        torch.cuda.synchronize(dev)
-        timings["levels"] = [{"level": l, "nodes": nodes[l], "occ_ctx_ms": ev[l][0].elapsed_time(ev[l][1]),
-                              "hist_ms": ev[l][1].elapsed_time(ev[l][2])} for l in range(depth)]
-        for l, a, b in t_code:
-            timings["levels"][l]["rans_ms"] = a.elapsed_time(b)
-        # by construction, not counted: the input's bounds, the stride chain's sizes, the histograms, the raw levels' bytes,
-        # the payload (tensor rows that are not yet canonical add the canonicalisation's count)
-        timings["host_reads_by_construction"] = 3 + (1 if raw_lv else 0) + 1
+            timings["levels"] = [{"level": l, "nodes": nodes[l], **ph.report(l)} for l in range(depth)]
+        # by construction, not counted: the input's bounds, the stride chain's sizes, the histograms | the raw levels' bytes + the
+        # vectors | the payload (tensor rows that are not yet canonical add the canonicalisation's count)
+        timings["host_reads_by_construction"] = 3 + (1 if parts else 0) + 1
     return bytes(out)
 
 
@@ -776,65 +704,71 @@ def _canonical_children(keys, n, pitch, depth_level, dev, counts_ptr):
     return out, None
 
 
-def _payloads(data, levels):
+def _payloads(data, levels, vectors=None, blocks=0):
     """Host buffers for ONE upload each: the coded levels' rANS containers (`rans.stage`) and the raw levels' bytes as int32
-    symbols."""
-    coded = [l for l, lv in enumerate(levels) if not lv["raw"]]
-    buf, offsets = R.stage(data, [levels[l]["payload"] for l in coded])
+    symbols.  An inter stream's vector list rides as the job "vec": its container when it is coded, else one index per block
+    behind the raw levels' bytes (zeros when the stream carries none)."""
+    jobs = [l for l, lv in enumerate(levels) if not lv["raw"]]
+    spans = [levels[l]["payload"] for l in jobs]
     raw_at, raw = {}, []
     for l, lv in enumerate(levels):
         if lv["raw"]:
             raw_at[l] = len(raw)
             raw.extend(data[lv["payload"][0]:lv["payload"][1]])
-    return buf, dict(zip(coded, offsets)), np.asarray(raw if raw else [1], dtype=np.int32), raw_at
-
-
-def _decode_inter(hdr, data, dev, rs, as_set, timings):
-    """The decoder of an inter stream (0xA8).  The levels above the blocks run as in `decode_geometry`; once the blocks are
-    known the vectors are decoded (or uploaded), the predicted pyramids are built from the reference, and every level from
-    there on draws `present` and the prediction byte from them.  Sizes come from the header alone (the pyramids from the block
-    level's node count), so there is still ONE device->host read, at the end; it also carries the vector list's rANS status and
-    range check and both class histograms of every inter level.  A wrong reference or a damaged payload can only give wrong
-    keys inside the cube until that read."""
-    n, depth, origin, first, search = hdr["n"], hdr["depth"], hdr["origin"], hdr["first"], hdr["search"]
-    bl = depth - first
-    k_vec = (2 * search + 1) ** 3
-    lib = L.load()
-    hw, hwi = lib.pcc_geom_hist_words(), lib.pcc_geom_inter_hist_words()
-    levels, vh = hdr["levels"], hdr["vectors"]
-    ph = _Phases(timings is not None)
-    with torch.cuda.device(dev):
-        ph.mark("start")
-        coded = [l for l, lv in enumerate(levels) if not lv["raw"]]
-        spans = [levels[l]["payload"] for l in coded] + ([] if vh["raw"] else [vh["payload"]])
-        h_buf, offsets = R.stage(data, spans)
-        where = dict(zip(coded + ["vec"], offsets))
-        raw_at, raw = {}, []
-        for l, lv in enumerate(levels):
-            if lv["raw"]:
-                raw_at[l] = len(raw)
-                raw.extend(data[lv["payload"][0]:lv["payload"][1]])
+    if vectors is not None and vectors["raw"]:
+        b0, b1 = vectors["payload"]
         raw_at["vec"] = len(raw)
-        raw.extend(data[vh["payload"][0]:vh["payload"][1]] if vh["raw"] and k_vec > 1 else [0] * (levels[first]["nodes"] if vh["raw"] else 1))
-        d_buf, d_raw = torch.from_numpy(h_buf).to(dev), torch.from_numpy(np.asarray(raw, dtype=np.int32)).to(dev)
+        raw.extend(data[b0:b1] if b1 > b0 else [0] * blocks)
+    elif vectors is not None:
+        jobs, spans = jobs + ["vec"], spans + [vectors["payload"]]
+    buf, offsets = R.stage(data, spans)
+    return buf, dict(zip(jobs, offsets)), np.asarray(raw, dtype=np.int32), raw_at          # (level 0 is one node: always raw)
+
+
+def _decode(hdr, data, dev, rs, as_set, timings):
+    """The level walk of `decode_geometry` for a non-empty cloud; `rs` is the reference set of an inter stream (None: empty).
+    Levels above `first` (= depth for an intra stream) decode against the contexts alone.  In an inter stream, once the
+    blocks (level `first`) are known the vectors are decoded (or uploaded), the predicted pyramids are built from the
+    reference, and every level from there on draws `present` and the prediction byte from them.  Sizes come from the header
+    alone (the pyramids from the block level's node count), so there is ONE device->host read, at the end; it also carries
+    the vector list's rANS status and range check and both class histograms of every inter level.  A wrong reference or a
+    damaged payload can only give wrong keys inside the cube until that read."""
+    n, depth, origin, levels = hdr["n"], hdr["depth"], hdr["origin"], hdr["levels"]
+    inter = bool(hdr.get("inter"))
+    first = hdr["first"] if inter else depth
+    lib = L.load()
+    words = [lib.pcc_geom_hist_words()] * first
+    ph = Phases(timings is not None)
+    with torch.cuda.device(dev):
+        ph.mark()
+        vh, nb = (hdr["vectors"], levels[first]["nodes"]) if inter else (None, 0)
+        h_buf, where, h_raw, raw_at = _payloads(data, levels, vh, nb)
+        d_buf, d_raw = torch.from_numpy(h_buf).to(dev), torch.from_numpy(h_raw).to(dev)
         const = R.fixed_tables("geometry", dev, None, TABLE_SIZES, TABLE_OFFSETS)
-        consti = R.fixed_tables("geometry_inter", dev, None, INTER_SIZES, INTER_OFFSETS)
-        state = torch.zeros(N_ROWS * 256, dtype=torch.int64, device=dev)
-        hist = torch.zeros(first * hw + (depth - first) * hwi, dtype=torch.int32, device=dev)
-        h_at = [l * hw if l < first else first * hw + (l - first) * hwi for l in range(depth)]
-        # per level: status | bad byte | child total (i64) | distinct, off-lattice (i64 x 2); row `depth`: the vector list's status | bad index
-        flags = torch.zeros((depth + 1, 8), dtype=torch.int32, device=dev)
+        # the level's cdf and decoder blob are derived on the device (`pcc_geom_tables`), in place, before each coded level
         tabs = R.Tables(torch.empty((N_CTX, N_SYM + 2), dtype=torch.int32, device=dev), const.sizes, const.offsets,
                         dec=torch.zeros(lib.pcc_geom_dec_table_bytes(), dtype=torch.uint8, device=dev))
-        tabsi = R.Tables(torch.empty((N_ROWS, INTER_STRIDE), dtype=torch.int32, device=dev), consti.sizes, consti.offsets,
-                         dec=torch.zeros(lib.pcc_geom_inter_dec_table_bytes(), dtype=torch.uint8, device=dev))
+        if inter:
+            search, bl = hdr["search"], depth - first
+            k_vec = (2 * search + 1) ** 3
+            words += [lib.pcc_geom_inter_hist_words()] * (depth - first)
+            consti = R.fixed_tables("geometry_inter", dev, None, INTER_SIZES, INTER_OFFSETS)
+            tabsi = R.Tables(torch.empty((N_ROWS, INTER_STRIDE), dtype=torch.int32, device=dev), consti.sizes, consti.offsets,
+                             dec=torch.zeros(lib.pcc_geom_inter_dec_table_bytes(), dtype=torch.uint8, device=dev))
+            bkeys = bgrid = pred = None
+        state = torch.zeros((N_ROWS if inter else N_CTX) * 256, dtype=torch.int64, device=dev)
+        h_at = [0, *itertools.accumulate(words)]
+        hist = torch.zeros(h_at[-1], dtype=torch.int32, device=dev)
+        # per level: status | bad byte | child total (i64) | distinct, off-lattice (i64 x 2); an inter stream's row `depth`: the
+        # vector list's status | bad index
+        flags = torch.zeros((depth + inter, 8), dtype=torch.int32, device=dev)
         keys = torch.tensor([_key_of(0, 0, 0)], dtype=torch.int64, device=dev)
         grid, by_grid = None, []
-        bkeys = bgrid = pred = None
-        nb = levels[first]["nodes"]
         for l, lv in enumerate(levels):
             m, pitch, total = lv["nodes"], 1 << (depth - l), lv["children"]
             fp, hp = flags.data_ptr() + 32 * l, hist.data_ptr() + 4 * h_at[l]
+            nbytes = lv["payload"][1] - lv["payload"][0]
+            ph.mark(None, l)
             if l == first:
                 vp = flags.data_ptr() + 32 * depth
                 if vh["raw"]:
@@ -849,21 +783,22 @@ def _decode_inter(hdr, data, dev, rs, as_set, timings):
                              nb, 1, 1, vh["streams"], vec, vp)
                 bkeys, bgrid = keys, grid
                 pred = torch.empty(nb * lib.pcc_geom_inter_pyramid_words(), dtype=torch.int64, device=dev)
-                L.call("pcc_geom_inter_block_bits", L.ptr(bkeys), nb, bl, *_ref_args(rs), *origin, L.ptr(vec), search, L.ptr(pred), vp + 4,
+                L.call("pcc_geom_inter_block_bits", L.ptr(bkeys), nb, bl, *ref_args(rs), *origin, L.ptr(vec), search, L.ptr(pred), vp + 4,
                        L.stream())
                 ph.mark("vectors_compensation_ms")
             if l < first:
                 ctx = torch.empty(m, dtype=torch.int32, device=dev)
                 L.call("pcc_geom_occ_ctx", L.ptr(keys), m, pitch, *S.grid_args(grid), None, 0, None, None, None, None, L.ptr(ctx), L.stream())
+                ph.mark("ctx_ms", l)
                 if lv["raw"]:
-                    sym = d_raw[raw_at[l]:raw_at[l] + m]
+                    byte = d_raw[raw_at[l]:raw_at[l] + m]
                 else:
                     L.call("pcc_geom_tables", L.ptr(state), (C.c_uint32 * 8)(*lv["pop"]), L.ptr(tabs.cdf), L.ptr(tabs.dec), L.stream())
-                    sym = torch.empty(m, dtype=torch.int32, device=dev)
-                    R.decode(tabs, d_buf.data_ptr() + where[l], lv["payload"][1] - lv["payload"][0], ctx, m, 1, 1, lv["streams"], sym, fp)
-                L.call("pcc_geom_hist", L.ptr(sym), L.ptr(ctx), m, hp, fp + 4, L.stream())
+                    byte = torch.empty(m, dtype=torch.int32, device=dev)
+                    R.decode(tabs, d_buf.data_ptr() + where[l], nbytes, ctx, m, 1, 1, lv["streams"], byte, fp)
+                ph.mark("symbols_ms", l)
+                L.call("pcc_geom_hist", L.ptr(byte), L.ptr(ctx), m, hp, fp + 4, L.stream())
                 L.call("pcc_geom_state_update", L.ptr(state), hp, L.stream())
-                byte = sym
             else:
                 idx = torch.empty(m, dtype=torch.int32, device=dev)
                 r = torch.empty(m, dtype=torch.int32, device=dev)
@@ -877,7 +812,7 @@ def _decode_inter(hdr, data, dev, rs, as_set, timings):
                     L.call("pcc_geom_inter_tables", L.ptr(state), (C.c_uint32 * 8)(*lv["pop"]), (C.c_uint32 * 9)(*lv["dist"]), L.ptr(tabsi.cdf),
                            L.ptr(tabsi.dec), L.stream())
                     sym = torch.empty(m, dtype=torch.int32, device=dev)
-                    R.decode(tabsi, d_buf.data_ptr() + where[l], lv["payload"][1] - lv["payload"][0], idx, m, 1, 1, lv["streams"], sym, fp)
+                    R.decode(tabsi, d_buf.data_ptr() + where[l], nbytes, idx, m, 1, 1, lv["streams"], sym, fp)
                     byte = torch.empty(m, dtype=torch.int32, device=dev)
                     L.call("pcc_geom_inter_map", L.ptr(sym), L.ptr(idx), L.ptr(r), m, 1, L.ptr(byte), fp + 4, L.stream())
                 L.call("pcc_geom_inter_hist", L.ptr(sym), L.ptr(idx), m, hp, fp + 4, L.stream())
@@ -887,26 +822,33 @@ def _decode_inter(hdr, data, dev, rs, as_set, timings):
             off = torch.empty(m + 1, dtype=torch.int32, device=dev)
             ws = L.workspace(lib.pcc_geom_offsets_ws_bytes(m), dev)
             L.call("pcc_geom_child_offsets", L.ptr(byte), m, L.ptr(off), fp + 8, fp + 4, L.ptr(ws), ws.numel(), L.stream())
+            ph.mark("hist_scan_ms", l)
+            # sized by the header's child count; slots a damaged payload leaves unwritten hold the cube's corner cell
             child = torch.full((total,), _key_of(0, 0, 0), dtype=torch.int64, device=dev)
             L.call("pcc_geom_expand", L.ptr(keys), L.ptr(byte), L.ptr(off), m, pitch >> 1, L.ptr(child), total, L.stream())
             keys, grid = _canonical_children(child, total, pitch >> 1, l + 1, dev, fp + 16)
             by_grid.append(grid is not None)
+            ph.mark("expand_canonical_ms", l)
             ph.mark("expand_canonical_ms")
         xyz = torch.empty((n, 3), dtype=torch.int32, device=dev)
         akeys = torch.empty(n, dtype=torch.int64, device=dev) if as_set else None
         L.call("pcc_geom_finish", L.ptr(keys), n, origin[0], origin[1], origin[2], L.ptr(akeys), L.ptr(xyz), L.stream())
-        cls = [hist[h_at[l] + (N_CTX * 256 if l < first else N_ROWS * 256):h_at[l] + (hw if l < first else hwi)] for l in range(depth)]
-        parts = [flags.reshape(-1)] + cls
+        # every level's class histograms, the words behind its (row, byte) counts: one strided view per kind of level
+        parts = [flags.reshape(-1)]
+        if first:
+            parts.append(hist[:h_at[first]].view(first, -1)[:, N_CTX * 256:].reshape(-1))
+        if first < depth:
+            parts.append(hist[h_at[first]:].view(depth - first, -1)[:, N_ROWS * 256:].reshape(-1))
         if as_set:
             parts += [xyz.amin(dim=0), xyz.amax(dim=0)]
         back = torch.cat(parts).cpu().numpy()                                  # the decode's one device->host read
         ph.mark("finish_read_ms")
-        fl = back[:8 * (depth + 1)].reshape(depth + 1, 8)
-        p = 8 * (depth + 1)
-        if fl[depth, 0] != 0 or fl[depth, 1] != 0:
+        p = flags.numel()
+        fl = back[:p].reshape(-1, 8)
+        if inter and (fl[depth, 0] != 0 or fl[depth, 1] != 0):
             raise L.PccError(f"geometry stream: malformed vector list (status {int(fl[depth, 0])}, index out of range {int(fl[depth, 1])})")
         for l, lv in enumerate(levels):
-            width = 8 if l < first else 17
+            width = words[l] - (N_CTX if l < first else N_ROWS) * 256
             got, p = [int(v) for v in back[p:p + width]], p + width
             total, distinct, off_lattice = (int(v) for v in fl[l, 2:8].view(np.int64))
             if fl[l, 0] != 0:
@@ -914,12 +856,15 @@ def _decode_inter(hdr, data, dev, rs, as_set, timings):
             if fl[l, 1] != 0 or total != lv["children"]:
                 raise L.PccError(f"geometry stream: level {l} decodes to {total} children, the header gives {lv['children']}")
             if not lv["raw"] and got != [int(v) for v in lv["pop"]] + [int(v) for v in lv.get("dist", [])]:
-                raise L.PccError(f"geometry stream: level {l} does not decode to its class histograms")
+                raise L.PccError(f"geometry stream: level {l} does not decode to its {'class histograms' if inter else 'popcount histogram'}")
             if by_grid[l] and (off_lattice or distinct != lv["children"]):
                 raise L.PccError(f"geometry stream: level {l} expands to {distinct} distinct cells, the header gives {lv['children']}")
         if timings is not None:
             torch.cuda.synchronize(dev)
-            timings["inter"] = ph.report()
+            if inter:
+                timings["inter"] = ph.report()
+            else:
+                timings["levels"] = [{"level": l, "nodes": lv["nodes"], "raw": lv["raw"], **ph.report(l)} for l, lv in enumerate(levels)]
             timings["host_reads_by_construction"] = 1
         if not as_set:
             return xyz
@@ -946,97 +891,19 @@ def decode_geometry(data, device, as_set=False, reference=None, timings=None):
     transform = hdr.get("transform")
     if transform is not None:
         data = bytes(data[hdr["inner"]:])              # (the payload spans of the dictionary count from here)
-    if hdr.get("inter"):
-        if transform is None:
-            rs = reference_set(reference, "decode_geometry")
-        else:
-            # the warp takes the reference rows as they are -- the set of warped cells does not depend on their order -- and
-            # its one read (row count and bounds of the warped set) stands where the canonicalisation of the reference stood;
-            # every launch of it is sized by the reference's row count
-            rs = M.warp_set(reference, transform)
-            rs = rs if rs.n else None
-        return _decode_inter(hdr, data, dev, rs, as_set, timings)
-    n, depth, origin = hdr["n"], hdr["depth"], hdr["origin"]
-    if n == 0:
+    if hdr["n"] == 0:
         empty = torch.empty((0, 3), dtype=torch.int32, device=dev)
         return S.CoordSet(torch.empty(1, dtype=torch.int64, device=dev), 0, 1, S.Bounds(0, (0, 0, 0), (0, 0, 0))) if as_set else empty
-    lib = L.load()
-    hw = lib.pcc_geom_hist_words()
-    levels = hdr["levels"]
-    with torch.cuda.device(dev):
-        h_buf, where, h_raw, raw_at = _payloads(data, levels)
-        d_buf, d_raw = torch.from_numpy(h_buf).to(dev), torch.from_numpy(h_raw).to(dev)
-        const = R.fixed_tables("geometry", dev, None, TABLE_SIZES, TABLE_OFFSETS)
-        state = torch.zeros(N_CTX * 256, dtype=torch.int64, device=dev)
-        hist = torch.zeros((depth, hw), dtype=torch.int32, device=dev)
-        flags = torch.zeros((depth, 8), dtype=torch.int32, device=dev)     # status | bad byte | child total (i64) | distinct, off-lattice (i64 x 2)
-        # the level's cdf and decoder blob are derived on the device (`pcc_geom_tables`), in place, before each coded level
-        tabs = R.Tables(torch.empty((N_CTX, N_SYM + 2), dtype=torch.int32, device=dev), const.sizes, const.offsets,
-                        dec=torch.zeros(lib.pcc_geom_dec_table_bytes(), dtype=torch.uint8, device=dev))
-        keys = torch.tensor([_key_of(0, 0, 0)], dtype=torch.int64, device=dev)
-        grid, by_grid, tl = None, [], []
-        for l, lv in enumerate(levels):
-            m, pitch, total = lv["nodes"], 1 << (depth - l), lv["children"]
-            fp = flags.data_ptr() + 32 * l
-            evs = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if timings is not None else None
-            if evs:
-                evs[0].record()
-            ctx = torch.empty(m, dtype=torch.int32, device=dev)
-            L.call("pcc_geom_occ_ctx", L.ptr(keys), m, pitch, *S.grid_args(grid), None, 0, None, None, None, None, L.ptr(ctx), L.stream())
-            if evs:
-                evs[1].record()
-            if lv["raw"]:
-                sym = d_raw[raw_at[l]:raw_at[l] + m]
-            else:
-                nb = lv["payload"][1] - lv["payload"][0]
-                L.call("pcc_geom_tables", L.ptr(state), (C.c_uint32 * 8)(*lv["pop"]), L.ptr(tabs.cdf), L.ptr(tabs.dec), L.stream())
-                sym = torch.empty(m, dtype=torch.int32, device=dev)
-                R.decode(tabs, d_buf.data_ptr() + where[l], nb, ctx, m, 1, 1, lv["streams"], sym, fp)
-            if evs:
-                evs[2].record()
-            L.call("pcc_geom_hist", L.ptr(sym), L.ptr(ctx), m, hist[l].data_ptr(), fp + 4, L.stream())
-            L.call("pcc_geom_state_update", L.ptr(state), hist[l].data_ptr(), L.stream())
-            off = torch.empty(m + 1, dtype=torch.int32, device=dev)
-            ws = L.workspace(lib.pcc_geom_offsets_ws_bytes(m), dev)
-            L.call("pcc_geom_child_offsets", L.ptr(sym), m, L.ptr(off), fp + 8, fp + 4, L.ptr(ws), ws.numel(), L.stream())
-            if evs:
-                evs[3].record()
-            # sized by the header's child count; slots a damaged payload leaves unwritten hold the cube's corner cell
-            child = torch.full((total,), _key_of(0, 0, 0), dtype=torch.int64, device=dev)
-            L.call("pcc_geom_expand", L.ptr(keys), L.ptr(sym), L.ptr(off), m, pitch >> 1, L.ptr(child), total, L.stream())
-            keys, grid = _canonical_children(child, total, pitch >> 1, l + 1, dev, fp + 16)
-            by_grid.append(grid is not None)
-            if evs:
-                evs[4].record()
-                tl.append((l, m, lv["raw"], evs))
-        xyz = torch.empty((n, 3), dtype=torch.int32, device=dev)
-        akeys = torch.empty(n, dtype=torch.int64, device=dev) if as_set else None
-        L.call("pcc_geom_finish", L.ptr(keys), n, origin[0], origin[1], origin[2], L.ptr(akeys), L.ptr(xyz), L.stream())
-        parts = [flags.reshape(-1), hist[:, N_CTX * 256:].reshape(-1)]
-        if as_set:
-            parts += [xyz.amin(dim=0), xyz.amax(dim=0)]
-        back = torch.cat(parts).cpu().numpy()                                  # the decode's one device->host read
-        fl, pops = back[:8 * depth].reshape(depth, 8), back[8 * depth:16 * depth].reshape(depth, 8)
-        for l, lv in enumerate(levels):
-            total, distinct, off_lattice = (int(v) for v in fl[l, 2:8].view(np.int64))
-            if fl[l, 0] != 0:
-                raise L.PccError(f"geometry stream: malformed rANS container in level {l} (status {int(fl[l, 0])})")
-            if fl[l, 1] != 0 or total != lv["children"]:
-                raise L.PccError(f"geometry stream: level {l} decodes to {total} children, the header gives {lv['children']}")
-            if not lv["raw"] and [int(v) for v in pops[l]] != [int(v) for v in lv["pop"]]:
-                raise L.PccError(f"geometry stream: level {l} does not decode to its popcount histogram")
-            if by_grid[l] and (off_lattice or distinct != lv["children"]):
-                raise L.PccError(f"geometry stream: level {l} expands to {distinct} distinct cells, the header gives {lv['children']}")
-        if timings is not None:
-            torch.cuda.synchronize(dev)
-            timings["levels"] = [{"level": l, "nodes": m, "raw": raw, "ctx_ms": e[0].elapsed_time(e[1]),
-                                  "symbols_ms": e[1].elapsed_time(e[2]), "hist_scan_ms": e[2].elapsed_time(e[3]),
-                                  "expand_canonical_ms": e[3].elapsed_time(e[4])} for l, m, raw, e in tl]
-            timings["host_reads_by_construction"] = 1
-        if not as_set:
-            return xyz
-        lo_hi = back[16 * depth:].reshape(2, 3).tolist()
-        return S.CoordSet(akeys, n, 1, S.Bounds(0, lo_hi[0], lo_hi[1]), on_lattice=True)
+    rs = None
+    if hdr.get("inter") and transform is None:
+        rs = reference_set(reference, "decode_geometry")
+    elif hdr.get("inter"):
+        # the warp takes the reference rows as they are -- the set of warped cells does not depend on their order -- and
+        # its one read (row count and bounds of the warped set) stands where the canonicalisation of the reference stood;
+        # every launch of it is sized by the reference's row count
+        rs = M.warp_set(reference, transform)
+        rs = rs if rs.n else None
+    return _decode(hdr, data, dev, rs, as_set, timings)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
