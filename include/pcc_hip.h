@@ -704,6 +704,31 @@ int pcc_geom_inter_tables(const uint64_t* state, const uint32_t* h_pop, const ui
                           void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 8f-3b* wide block motion of the inter coders (DESIGN.md section 7e "Wide search", stream format 0xAA): the search of 8f-3b' over
+ *       [-search, search]^3 with 1 <= search <= 7.  A vector is a DISPLACEMENT, int32 (dx + 8) | (dy + 8) << 4 | (dz + 8) << 8, never
+ *       an index into a table.  Blocks, pyramids, the reference set and the origin are given as in 8f-3b'.
+ * pcc_geom_wide_motion      disp[b] = the vector with the most voxels p of the block for which reference(origin + p - v) is
+ *                           occupied; ties to the smaller dx^2 + dy^2 + dz^2, then to the lexicographically smaller (dx, dy, dz):
+ *                           for search <= 2 the vector pcc_geom_inter_motion picks.  counts (nullable) receives the match counts
+ *                           [n_blocks, (2 search + 1)^3] in plain lexicographic (dx, dy, dz) order.  No atomics, integers only.
+ * pcc_geom_wide_block_bits  pcc_geom_inter_block_bits with disp[b] in place of an index (disp is required).  A component outside
+ *                           +-search (or a bit above the 12) sets *d_bad and the block's vector counts as zero.
+ * pcc_geom_wide_pack        disp[i] from comps[i] = (dx + search, dy + search, dz + search), what an 0xAA vector list codes; a
+ *                           component outside 0 .. 2 search sets *d_bad and counts as zero displacement on that axis.
+ * pcc_geom_wide_unpack      the inverse (a displacement outside the range unpacks as zero).
+ * ---------------------------------------------------------------------------------------- */
+int pcc_geom_wide_motion(const int64_t* block_keys, int64_t n_blocks, int32_t block_log2, const uint64_t* cur_pyramid,
+                         const int64_t* ref_keys, int64_t n_ref, const uint64_t* ref_bits, const int32_t* ref_rank,
+                         const int32_t* h_ref, int32_t ox, int32_t oy, int32_t oz, int32_t search, int32_t* counts /*nullable*/,
+                         int32_t* disp, void* stream);
+int pcc_geom_wide_block_bits(const int64_t* block_keys, int64_t n_blocks, int32_t block_log2, const int64_t* src_keys,
+                             int64_t n_src, const uint64_t* src_bits, const int32_t* src_rank, const int32_t* h_src,
+                             int32_t ox, int32_t oy, int32_t oz, const int32_t* disp, int32_t search, uint64_t* pyramid,
+                             int32_t* d_bad, void* stream);
+int pcc_geom_wide_pack(const int32_t* comps, int64_t n, int32_t search, int32_t* disp, int32_t* d_bad, void* stream);
+int pcc_geom_wide_unpack(const int32_t* disp, int64_t n, int32_t search, int32_t* comps, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * 8f-3b'' global motion of the inter coders (DESIGN.md section 7e "Global motion"; motion.py): one rigid transform per frame,
  *       applied to the reference before the block motion of 8f-3b'.
  *       The transform is 12 int32 on the HOST: M[3][3] row-major in Q24, then t[3] in Q8 voxels; |M_ij| <= PCC_MOTION_MAX_M,
@@ -907,6 +932,8 @@ int pcc_lift_finish(const int32_t* values, int64_t n, int32_t channels, int32_t 
  * pcc_lift_inter_match     match[i] of voxel i (voxel_keys origin-relative, origin ox, oy, oz): with its block's vector d the
  *                          reference row at p - d, else at the first occupied of the 26 cells around it ordered by
  *                          (|o|^2, 9 (ox + 1) + 3 (oy + 1) + (oz + 1)), else -1.
+ * pcc_lift_inter_match_wide  the same with disp[b], a packed displacement of 8f-3b* with 1 <= search <= 7, in place of an index
+ *                          (streams 0xB7 and 0xB8); a displacement outside +-search counts as zero and sets bit 0 of *d_flag.
  * pcc_lift_inter_residual  after pcc_lift_forward: rows of the level -= Hp of the spatial prediction (what pcc_lift_residual
  *                          does) and coef_t [rows_total - row_base, channels] = H - Hp of the temporal prediction (a matched
  *                          child: ref_values of its match; an unmatched one: the spatial prediction); sums [n_blocks, 2] int32
@@ -924,6 +951,11 @@ int pcc_lift_inter_match(const int64_t* voxel_keys, int64_t n, const int64_t* bl
                          const int32_t* vec, int32_t search, const int64_t* ref_keys, int64_t n_ref, const uint64_t* ref_bits,
                          const int32_t* ref_rank, const int32_t* h_ref, int32_t ox, int32_t oy, int32_t oz, int32_t* match,
                          int32_t* d_flag, void* stream);
+int pcc_lift_inter_match_wide(const int64_t* voxel_keys, int64_t n, const int64_t* block_keys, int64_t n_blocks,
+                              const uint64_t* block_bits, const int32_t* block_rank, const int32_t* h_block, int32_t block_log2,
+                              const int32_t* disp, int32_t search, const int64_t* ref_keys, int64_t n_ref, const uint64_t* ref_bits,
+                              const int32_t* ref_rank, const int32_t* h_ref, int32_t ox, int32_t oy, int32_t oz, int32_t* match,
+                              int32_t* d_flag, void* stream);
 int pcc_lift_inter_residual(const int64_t* keys, int64_t n, int32_t pitch, const uint64_t* bits, const int32_t* rank,
                             const int32_t* h_grid, const int64_t* child_keys, int64_t n_child, const uint64_t* child_bits,
                             const int32_t* child_rank, const int32_t* h_child, const int64_t* block_keys, int64_t n_blocks,

@@ -30,9 +30,9 @@ import torch
 
 from . import lib as L
 from . import sparse as S
-from .attributes import (INTER_LOSSY_MAGIC, INTER_MAGIC, decode_attributes, decode_attributes_lossless, encode_attributes,
-                         encode_attributes_lossless)
-from .geometry import canonical_rows, decode_geometry, encode_geometry, stream_transform
+from .attributes import (INTER_LOSSY_MAGIC, INTER_MAGIC, WIDE_LOSSY_MAGIC, WIDE_MAGIC, decode_attributes, decode_attributes_lossless,
+                         encode_attributes, encode_attributes_lossless)
+from .geometry import canonical_rows, decode_geometry, encode_geometry, stream_search, stream_transform
 from .motion import warp_cloud
 from .voxelize import voxel_grid
 
@@ -68,14 +68,15 @@ def scaled_voxels(cloud, position_scale):
 
 
 @torch.no_grad()
-def compress_anchor(cloud, qp, position_scale=1.0, chroma_qp_offset=-2, reference=None, attributes="intra"):
+def compress_anchor(cloud, qp, position_scale=1.0, chroma_qp_offset=-2, reference=None, attributes="intra", search=None):
     """[N, 6] GPU cloud (xyz, rgb in [0, 1]) -> bytes.  position_scale in (0, 1]: below 1 the points are scaled first; points
     that then share a cell are merged with their mean colour.  qp, chroma_qp_offset: `attributes.encode_attributes`.
     reference: voxels IN THE SCALED DOMAIN that `decompress_anchor` will be given too (the previous frame's decoded geometry,
     say): the geometry is then coded against them where that is shorter (`geometry.encode_geometry`).  attributes: "intra" --
     colour ignores the reference; "auto" / "inter" -- the mode of `attributes.encode_attributes`, which then needs an [M, 6]
     reference of distinct scaled-domain integer voxels with rgb in [0, 1]: the previous frame AS DECODED
-    (`compress_anchor_sequence` keeps that loop closed)."""
+    (`compress_anchor_sequence` keeps that loop closed).  search: the block vectors' range, as in `geometry.encode_geometry`
+    (None, 2 .. 7 or "auto"); the colour coder uses the range the geometry stream ended with, 2 where it fell back to intra."""
     what = "compress_anchor"
     if attributes not in ("auto", "inter", "intra"):
         raise L.PccError(f"{what}: attributes {attributes!r} is not one of auto, inter, intra")
@@ -92,11 +93,12 @@ def compress_anchor(cloud, qp, position_scale=1.0, chroma_qp_offset=-2, referenc
     c4 = torch.cat([torch.zeros((g.index.shape[0], 1), dtype=torch.int32, device=cloud.device), g.index], dim=1).contiguous()
     cs = S.coordset_from_coords(c4, 1)[0]                    # the grid's rows are ascending: canonical as they are
     levels = torch.round(g.attrs.to(torch.float64) * 255.0).clamp_(0, 255).to(torch.uint8)
-    geometry = encode_geometry(cs, reference=reference)
+    geometry = encode_geometry(cs, reference=reference, search=search)
     if attributes == "intra":
         colours = encode_attributes(cs, qp, chroma_qp_offset, attrs=levels)
     else:
-        colours = encode_attributes(cs, qp, chroma_qp_offset, attrs=levels, reference=reference, mode=attributes)
+        colours = encode_attributes(cs, qp, chroma_qp_offset, attrs=levels, reference=reference, mode=attributes,
+                                    search=stream_search(geometry))
     return HEADER.pack(MAGIC, scale, len(geometry)) + geometry + colours
 
 
@@ -104,7 +106,7 @@ def _decode_anchor(data, device, reference):
     """(position scale, the decoded voxel set in the scaled domain, its uint8 levels): what `decompress_anchor` returns and what
     the next frame of a sequence is coded against both come from here."""
     scale, geometry, attributes = parse_container(data)
-    inter = len(attributes) > 0 and attributes[0] == INTER_LOSSY_MAGIC
+    inter = len(attributes) > 0 and attributes[0] in (INTER_LOSSY_MAGIC, WIDE_LOSSY_MAGIC)
     if inter and not _has_colours(reference):
         raise L.PccError("decompress_anchor: the colours are coded against a reference; an [M, 6] reference cloud is required")
     cs = decode_geometry(geometry, device, as_set=True, reference=reference)
@@ -129,7 +131,7 @@ def decompress_anchor(data, device, reference=None):
 
 
 @torch.no_grad()
-def compress_anchor_sequence(frames, qp, position_scale=1.0, chroma_qp_offset=-2, intra_period=32):
+def compress_anchor_sequence(frames, qp, position_scale=1.0, chroma_qp_offset=-2, intra_period=32, search=None):
     """Frames ([N, 6] clouds as for `compress_anchor`) -> one stream per frame, closed loop: frame i is coded on its own when
     i % intra_period == 0, else against frame i - 1 AS DECODED -- its voxels in the scaled domain and its decoded colours --
     with geometry and colour both "auto".  The encoder decodes every stream it wrote to hold what the decoder will hold.
@@ -142,7 +144,7 @@ def compress_anchor_sequence(frames, qp, position_scale=1.0, chroma_qp_offset=-2
             out.append(compress_anchor(frame, qp, position_scale, chroma_qp_offset))
             prev = None
         else:
-            out.append(compress_anchor(frame, qp, position_scale, chroma_qp_offset, reference=prev, attributes="auto"))
+            out.append(compress_anchor(frame, qp, position_scale, chroma_qp_offset, reference=prev, attributes="auto", search=search))
         _, cs, levels = _decode_anchor(out[-1], frame.device, prev)
         prev = _decoded_cloud(1.0, cs, levels)
     return out
@@ -196,7 +198,7 @@ def _colour_reference(reference, geometry):
 
 
 @torch.no_grad()
-def compress_lossless(cloud, reference=None, attributes="intra", global_motion=None):
+def compress_lossless(cloud, reference=None, attributes="intra", global_motion=None, search=None):
     """[N, 6] GPU cloud of distinct voxels (integer xyz, rgb in [0, 1]: colours become round(255 c)) -> bytes from which
     `decompress_lossless` returns the same voxels with the same levels.  Non-integer coordinates and repeated voxels raise
     PccError: voxelise first (`voxelize.voxel_grid`).  reference: a voxel cloud (its first three columns) the decoder holds
@@ -204,7 +206,8 @@ def compress_lossless(cloud, reference=None, attributes="intra", global_motion=N
     ignore the reference; "auto" / "inter" -- the mode of `attributes.encode_attributes_lossless`, which then needs an [M, 6]
     reference of distinct voxels and codes the colours against its colours.  global_motion: as in
     `geometry.encode_geometry` (None, "auto" or a RigidTransform); when the geometry comes out wrapped, the colours are coded
-    against the warped reference."""
+    against the warped reference.  search: the block vectors' range, as in `geometry.encode_geometry` (None, 2 .. 7 or "auto");
+    the colour coder uses the range the geometry stream ended with, 2 where it fell back to intra."""
     what = "compress_lossless"
     if attributes not in ("auto", "inter", "intra"):
         raise L.PccError(f"{what}: attributes {attributes!r} is not one of auto, inter, intra")
@@ -223,11 +226,12 @@ def compress_lossless(cloud, reference=None, attributes="intra", global_motion=N
         raise L.PccError(f"{what}: {cloud.shape[0] - cs.n} rows repeat a voxel; merge them first (voxelize.voxel_grid)")
     levels = torch.round(cloud[:, 3:6].to(torch.float64) * 255.0).clamp_(0, 255).to(torch.uint8)
     levels = (levels if perm is None else levels[perm]).contiguous()
-    geometry = encode_geometry(cs, reference=reference, global_motion=global_motion)
+    geometry = encode_geometry(cs, reference=reference, global_motion=global_motion, search=search)
     if attributes == "intra":
         colours = encode_attributes_lossless(cs, attrs=levels)
     else:
-        colours = encode_attributes_lossless(cs, attrs=levels, reference=_colour_reference(reference, geometry), mode=attributes)
+        colours = encode_attributes_lossless(cs, attrs=levels, reference=_colour_reference(reference, geometry), mode=attributes,
+                                             search=stream_search(geometry))
     return LOSSLESS_HEADER.pack(LOSSLESS_MAGIC, len(geometry)) + geometry + colours
 
 
@@ -237,7 +241,7 @@ def decompress_lossless(data, device, reference=None):
     them gives the levels back).  reference: the cloud `compress_lossless` was given; a stream whose colours are coded against
     it (magic byte 0xB6 of the attribute part) raises PccError when the reference has no colours."""
     geometry, attributes = parse_lossless_container(data)
-    inter = len(attributes) > 0 and attributes[0] == INTER_MAGIC
+    inter = len(attributes) > 0 and attributes[0] in (INTER_MAGIC, WIDE_MAGIC)
     if inter and not _has_colours(reference):
         raise L.PccError("decompress_lossless: the colours are coded against a reference; an [M, 6] reference cloud is required")
     cs = decode_geometry(geometry, device, as_set=True, reference=reference)
@@ -247,7 +251,7 @@ def decompress_lossless(data, device, reference=None):
 
 
 @torch.no_grad()
-def compress_lossless_sequence(frames, intra_period=32, global_motion=None):
+def compress_lossless_sequence(frames, intra_period=32, global_motion=None, search=None):
     """Frames ([N, 6] clouds as for `compress_lossless`) -> one stream per frame: frame i is coded on its own when
     i % intra_period == 0, else against frame i - 1 with geometry and colour both "auto" (lossless: the decoder holds the same
     frame) and `global_motion` as given.  Every stream decodes with `decompress_lossless(stream, device, reference=previous
@@ -259,7 +263,7 @@ def compress_lossless_sequence(frames, intra_period=32, global_motion=None):
         if i % int(intra_period) == 0:
             out.append(compress_lossless(frame))
         else:
-            out.append(compress_lossless(frame, reference=prev, attributes="auto", global_motion=global_motion))
+            out.append(compress_lossless(frame, reference=prev, attributes="auto", global_motion=global_motion, search=search))
         prev = frame
     return out
 

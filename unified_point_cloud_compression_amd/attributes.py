@@ -10,6 +10,8 @@ this project's own stream: no G-PCC syntax and no bit-compatibility claim, the s
              | C zig-zag varints (the quantised root DC residual) | (depth + 1) x 6 side bytes
              | ceil(blocks / 8) mode bytes (block b: bit b & 7 of byte b >> 3) | u32 length | rANS container
              (coded against a reference cloud the decoder holds, in the coefficient domain; no vector travels; "Inter frames" in 7f)
+    wide:    u8 0xB8 | the 0xB4 layout byte for byte, search in 3 .. 7: the matches come from block vectors searched over
+             [-search, search]^3 (`encode_attributes(..., search=)`; the decoder re-runs that search; 0xB4 itself reads 2 only)
 
 The geometry is not in the stream: the decoder is handed it and refuses a stream whose n or depth differ from the set's.
 Level l of the transform is level l of the octree (`geometry.level_sets`); inside a node three stages of weighted Haar
@@ -34,6 +36,7 @@ over the same levels, rows, groups, family and container with a reversible arith
     inter:   u8 0xB6 | u32 n | u8 depth | u8 C | u8 flags (bit 1, and bit 0 for YCoCg-R) | u8 block_log2 | u8 search | u32 blocks
              | C zig-zag varints | (depth + 1) x 6 side bytes | ceil(blocks / 8) mode bytes (block b: bit b & 7 of byte b >> 3)
              | u32 length | rANS container            (coded against a reference cloud the decoder holds; no vector travels)
+    wide:    u8 0xB7 | the 0xB6 layout byte for byte, search in 3 .. 7 (`encode_attributes_lossless(..., search=)`, as 0xB8 above)
 """
 import ctypes as C
 import struct
@@ -55,6 +58,7 @@ LIMIT = 1 << 30            # the decoder's clamp on q * step and on every butter
 QP_MIN, QP_MAX = 4, 51
 HEADER = struct.Struct("<BIBBBBb")
 INTER_LOSSY_MAGIC = 0xB4   # inter frames, format version 1: coefficients predicted from a reference cloud
+WIDE_LOSSY_MAGIC = 0xB8    # the 0xB4 layout byte for byte with the block vectors searched over +-3 .. +-7 (the header's search byte)
 INTER_LOSSY_HEADER = struct.Struct("<BIBBBBbBBI")
 STEP_TABLE = (256, 287, 323, 362, 406, 456)                 # Q8: 2^(k / 6), k = 0..5
 THETA = (55109, 46341, 38968, 32768)                        # Q16: 2^(-k / 4), k = 1..4
@@ -176,10 +180,11 @@ def parse_header(data, have_reference=True):
     """{n, depth, channels, colour, qp, chroma_qp_offset, steps, dc (quantised root DC per channel), side (depth * 6 members),
     payload=(begin, end) or None, streams, inter}.  Raises PccError on a bad magic byte, on channels, qp or depth out of range,
     on a root DC or side byte out of range, on truncation, on trailing bytes and on a length that disagrees with the data --
-    before any GPU work.  An inter stream (0xB4) has inter=True, dc = the quantised root DC residual, (depth + 1) * 6 side bytes
+    before any GPU work.  An inter stream (0xB4, or 0xB8: the same layout searched over +-3 .. +-7) has inter=True, dc = the
+    quantised root DC residual, (depth + 1) * 6 side bytes
     and block_log2, search, blocks, modes=(begin, end) besides; refused for it as well: a block size or search range other than
     this build's, depth > 14, n < 2, a block count of 0 or above n, set padding bits of the mode bytes, and have_reference=False."""
-    inter = len(data) > 0 and data[0] == INTER_LOSSY_MAGIC
+    inter = len(data) > 0 and data[0] in (INTER_LOSSY_MAGIC, WIDE_LOSSY_MAGIC)
     name = "inter attribute stream" if inter else "attribute stream"
     head = INTER_LOSSY_HEADER if inter else HEADER
     if inter and not have_reference:
@@ -187,8 +192,8 @@ def parse_header(data, have_reference=True):
     if len(data) < head.size:
         raise L.PccError(f"{name} truncated inside the header")
     magic, n, depth, ch, flags, qp, cqo = HEADER.unpack_from(data, 0)
-    if magic not in (MAGIC, INTER_LOSSY_MAGIC):
-        raise L.PccError(f"attribute stream: magic byte {magic:#x}, this build reads {MAGIC:#x} and {INTER_LOSSY_MAGIC:#x}")
+    if magic not in (MAGIC, INTER_LOSSY_MAGIC, WIDE_LOSSY_MAGIC):
+        raise L.PccError(f"attribute stream: magic byte {magic:#x}, this build reads {MAGIC:#x}, {INTER_LOSSY_MAGIC:#x} and {WIDE_LOSSY_MAGIC:#x}")
     if not 1 <= ch <= MAX_C:
         raise L.PccError(f"attribute stream: {ch} channels outside 1..{MAX_C}")
     if flags & ~1 or (flags & 1 and ch != 3):
@@ -202,8 +207,7 @@ def parse_header(data, have_reference=True):
     hdr = {"inter": inter}
     if inter:
         block_log2, search, blocks = INTER_LOSSY_HEADER.unpack_from(data, 0)[7:]
-        if block_log2 != G.BLOCK_LOG2 or search != G.SEARCH:
-            raise L.PccError(f"{name}: block_log2 {block_log2}, search {search}; this build reads {G.BLOCK_LOG2} and {G.SEARCH}")
+        _check_range(name, block_log2, search, magic == WIDE_LOSSY_MAGIC)
         if n < 2:
             raise L.PccError(f"{name}: header claims {n} points, an inter stream codes 2 .. 2^26 - 1")
         if depth > INTER_MAX_DEPTH:
@@ -256,6 +260,23 @@ def parse_header(data, have_reference=True):
 # ------------------------------------------------------------------------------------------------------------------------
 # device side
 # ------------------------------------------------------------------------------------------------------------------------
+def _check_range(name, block_log2, search, wide):
+    """The block size and search range of an inter header: G.SEARCH under the narrow magic bytes, G.WIDE_SEARCH under the wide ones."""
+    lo, hi = G.WIDE_SEARCH if wide else (G.SEARCH, G.SEARCH)
+    if block_log2 != G.BLOCK_LOG2 or not lo <= search <= hi:
+        reads = f"{lo}..{hi}" if wide else f"{G.SEARCH}"
+        raise L.PccError(f"{name}: block_log2 {block_log2}, search {search}; this build reads {G.BLOCK_LOG2} and {reads}")
+
+
+def _colour_search(search, what):
+    """The search range of a colour encoder: an int in 2 .. 7 (None: 2).  "auto" belongs to the geometry coder -- the colour follows
+    the range the geometry stream ended with (`geometry.stream_search`)."""
+    search = G.check_search(search, what)
+    if search == "auto":
+        raise L.PccError(f"{what}: search \"auto\" is the geometry coder's; give the range its stream ended with (geometry.stream_search)")
+    return search
+
+
 def _tables(dev):
     """The family on the device, with its encoder entries and decoder blob: one upload per device."""
     return R.fixed_tables("raht", dev, table_family()[0], TABLE_SIZES, TABLE_OFFSETS, enc=True, dec=True)
@@ -378,7 +399,7 @@ def _intra_tail(what, sets, masks, offs, checks, coef, v_root, depth, ch, rows, 
 
 @torch.no_grad()
 def encode_attributes(cloud, qp, chroma_qp_offset=-2, colour=True, attrs=None, segment_symbols=SEGMENT_SYMBOLS, timings=None,
-                      reference=None, reference_attrs=None, mode="auto"):
+                      reference=None, reference_attrs=None, mode="auto", search=None):
     """[N, 6] GPU tensor (xyz, then rgb in [0, 1]: colours become round(255 c)), or a pitch-1 CoordSet / [N, >= 3] rows with
     `attrs` uint8 [N, C], 1 <= C <= 8 -> bytes.  Any row order (attributes follow their rows into canonical order; a set's
     attributes are in the set's order).  Duplicate voxels, CPU tensors and batched input raise PccError.  colour: the integer
@@ -389,8 +410,11 @@ def encode_attributes(cloud, qp, chroma_qp_offset=-2, colour=True, attrs=None, s
     count.  mode "auto": the shorter of the inter (0xB4) and the intra (0xB3) stream, intra on a tie and at depth 15 -- by
     stream length alone: against an unrelated reference the shorter stream may decode to a lower PSNR than the intra one
     (DESIGN.md 7f); "inter": the inter stream (fewer than two voxels still travel as intra; depth 15 raises); "intra", or no
-    reference: today's stream byte for byte."""
+    reference: today's stream byte for byte.  search: the range of the block vectors the inter stream's matches come from --
+    None or 2: 0xB4 as ever; 3 .. 7: the stream 0xB8, the 0xB4 layout with that range in its header (no vector travels: the
+    decoder re-runs the wide search)."""
     what = "encode_attributes"
+    search = _colour_search(search, what)
     cs, levels, perm, ref, depth, inter = _encoder_input(what, cloud, attrs, reference, reference_attrs, mode, True, chroma_qp_offset)
     qp, cqo = min(max(int(qp), QP_MIN), QP_MAX), int(chroma_qp_offset)
     n, ch, dev = cs.n, levels.shape[1], cs.device
@@ -398,7 +422,7 @@ def encode_attributes(cloud, qp, chroma_qp_offset=-2, colour=True, attrs=None, s
     if n == 0:
         return HEADER.pack(MAGIC, 0, 0, ch, int(colour), qp, cqo) + b"\x00" * ch
     if inter:
-        return _encode_inter_lossy(what, cs, levels, perm, ref, qp, cqo, colour, mode, segment_symbols, timings)
+        return _encode_inter_lossy(what, cs, levels, perm, ref, qp, cqo, colour, mode, segment_symbols, timings, search)
     steps = steps_for(qp, cqo, ch)
     h_steps = (C.c_int32 * ch)(*steps)
     rows = n - 1
@@ -462,7 +486,7 @@ def decode_attributes(data, geometry, device=None, reference=None, reference_att
                 raise L.PccError(f"{what}: the stream codes {hdr['blocks']} blocks, the geometry has {sets[first].n}")
             flag = status.data_ptr() + 4
             bargs, nb, match, tv, nr, _keep = _inter_state(cs, sets, tuple(cs.bounds.lo), depth, ref, ch, hdr["colour"], flag,
-                                                           "pcc_raht_prepare")
+                                                           "pcc_raht_prepare", hdr["search"])
             d_mode = _block_modes(data, hdr, nb, dev)
             ph.mark("motion_match_ms")
             # the prediction's transform: P with the mode-0 blocks zeroed, then the same forward pass, rows left unquantised
@@ -571,6 +595,7 @@ LOSSLESS_HEADER = struct.Struct("<BIBBB")
 F_COLOUR, F_PREDICT, F_STORED = 1, 2, 4
 SYMBOL_LIMIT = 1023        # the decoder's clamp on a symbol; a valid one is within +-1020
 INTER_MAGIC = 0xB6         # inter frames, format version 1: the last level may be predicted from a reference cloud
+WIDE_MAGIC = 0xB7          # the 0xB6 layout byte for byte with the block vectors searched over +-3 .. +-7 (the header's search byte)
 INTER_HEADER = struct.Struct("<BIBBBBBI")
 INTER_MAX_DEPTH = 14       # (depth + 1) * 6 groups within the 90 of pcc_raht_hist
 
@@ -602,19 +627,18 @@ def _root_values(data, at, n, channels, colour, name):
 
 
 def _parse_inter_header(data, have_reference):
-    """The 0xB6 half of `parse_lossless_header`."""
+    """The 0xB6 / 0xB7 half of `parse_lossless_header`."""
     name = "inter lossless attribute stream"
     if not have_reference:
         raise L.PccError(f"{name}: the stream is coded against a reference cloud and none was given")
     if len(data) < INTER_HEADER.size:
         raise L.PccError(f"{name} truncated inside the header")
-    _, n, depth, ch, flags, block_log2, search, blocks = INTER_HEADER.unpack_from(data, 0)
+    magic, n, depth, ch, flags, block_log2, search, blocks = INTER_HEADER.unpack_from(data, 0)
     if not 1 <= ch <= MAX_C:
         raise L.PccError(f"{name}: {ch} channels outside 1..{MAX_C}")
     if flags not in (F_PREDICT, F_PREDICT | F_COLOUR) or (flags & F_COLOUR and ch != 3):
         raise L.PccError(f"{name}: flags {flags:#x} with {ch} channels")
-    if block_log2 != G.BLOCK_LOG2 or search != G.SEARCH:
-        raise L.PccError(f"{name}: block_log2 {block_log2}, search {search}; this build reads {G.BLOCK_LOG2} and {G.SEARCH}")
+    _check_range(name, block_log2, search, magic == WIDE_MAGIC)
     if not 2 <= n < MAX_POINTS:
         raise L.PccError(f"{name}: header claims {n} points, an inter stream codes 2 .. 2^26 - 1")
     if not 1 <= depth <= INTER_MAX_DEPTH or n > 8 ** min(depth, 10):
@@ -649,10 +673,11 @@ def parse_lossless_header(data, have_reference=True):
     streams, raw=(begin, end) or None, inter}.  Raises PccError on a bad magic byte, an unknown flag, the colour flag without
     three channels, channels, n or depth out of range, a root outside its channel's range, a side byte that names no table,
     truncation, trailing bytes, a container length that disagrees with the data and a stored body of the wrong size --
-    before any GPU work.  An inter stream (0xB6) has inter=True, (depth + 1) * 6 side bytes and block_log2, search, blocks,
+    before any GPU work.  An inter stream (0xB6, or 0xB7: the same layout searched over +-3 .. +-7) has inter=True,
+    (depth + 1) * 6 side bytes and block_log2, search, blocks,
     modes=(begin, end) besides; refused for it as well: a block size or search range other than this build's, depth > 14,
     n < 2, a block count of 0 or above n, set padding bits of the mode bytes, and have_reference=False."""
-    if len(data) and data[0] == INTER_MAGIC:
+    if len(data) and data[0] in (INTER_MAGIC, WIDE_MAGIC):
         return _parse_inter_header(data, have_reference)
     if len(data) < LOSSLESS_HEADER.size:
         raise L.PccError("lossless attribute stream truncated inside the header")
@@ -720,20 +745,21 @@ def _reference_rows(reference, reference_attrs, channels, predict, what):
     return rs, levels, perm
 
 
-def _inter_state(cs, sets, origin, depth, ref, channels, colour, d_flag, prepare="pcc_lift_prepare"):
+def _inter_state(cs, sets, origin, depth, ref, channels, colour, d_flag, prepare="pcc_lift_prepare", search=G.SEARCH):
     """What both sides of an inter stream (0xB6 and 0xB4) recompute from the geometry and the reference: (the block arguments of
     the pcc_lift_inter_* / pcc_raht_inter_* entry points, the block count, int32 match row per voxel, int32 [M, C] prepared
     reference values or None, M).  `geometry.motion_vectors` gives the vectors; the tensors the arguments point into live in
     `sets` and the result.  prepare: the entry point that turns the reference's levels into the coder's values (plain or
-    YCoCg-R levels for the lossless coder, Q8 with BT.709 for the RAHT coder: "pcc_raht_prepare")."""
+    YCoCg-R levels for the lossless coder, Q8 with BT.709 for the RAHT coder: "pcc_raht_prepare").  search above 2: the wide search,
+    whose vectors are packed displacements (`pcc_lift_inter_match_wide`)."""
     rs, levels, perm = ref
     dev = cs.device
-    blocks, bl, _, vec = G.motion_vectors(cs, rs, origin, depth, sets)
+    blocks, bl, _, vec = G.motion_vectors(cs, rs, origin, depth, sets, search=search)
     grid = blocks.grid() if (depth > bl and S.USE_GRID) else None         # the root's single node is searched
     bargs = (L.ptr(blocks.keys), blocks.n, *S.grid_args(grid), bl)
     match = torch.empty(cs.n, dtype=torch.int32, device=dev)
-    L.call("pcc_lift_inter_match", L.ptr(sets[depth].keys), cs.n, *bargs, L.ptr(vec), G.SEARCH, *G.ref_args(rs), *origin, L.ptr(match),
-           d_flag, L.stream())
+    L.call("pcc_lift_inter_match_wide" if search > G.MAX_SEARCH else "pcc_lift_inter_match", L.ptr(sets[depth].keys), cs.n, *bargs, L.ptr(vec),
+           search, *G.ref_args(rs), *origin, L.ptr(match), d_flag, L.stream())
     if rs is None:
         return bargs, blocks.n, match, None, 0, (vec, grid)
     if levels.device != dev:
@@ -768,8 +794,9 @@ def _inter_index(masks, offs, sets, depth, first, ch, bargs, d_mode, d_side, idx
                L.ptr(d_side), L.ptr(idx), L.ptr(coef_p), L.ptr(coef), sets[l].n - 1, rows, d_flag, L.stream())
 
 
-def _encode_inter_lossy(what, cs, levels, perm, ref, qp, cqo, colour, mode, segment_symbols, timings):
-    """The inter half of `encode_attributes` (n >= 2, depth <= 14): the 0xB4 stream and, for mode "auto", the 0xB3 stream from
+def _encode_inter_lossy(what, cs, levels, perm, ref, qp, cqo, colour, mode, segment_symbols, timings, search=G.SEARCH):
+    """The inter half of `encode_attributes` (n >= 2, depth <= 14): the 0xB4 stream (0xB8 when `search` is above 2) and, for
+    mode "auto", the 0xB3 stream from
     the same forward pass; the shorter is returned, intra on a tie.  Device->host reads beyond the level sets: 2 for the inter
     stream (modes, root DCs and histograms; the container), 2 more for the intra stream of "auto"."""
     n, ch, dev = cs.n, levels.shape[1], cs.device
@@ -782,7 +809,7 @@ def _encode_inter_lossy(what, cs, levels, perm, ref, qp, cqo, colour, mode, segm
         sets = G.level_sets(cs, origin, depth)
         ph.mark("start")
         d_flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        bargs, nb, match, tv, nr, _keep = _inter_state(cs, sets, origin, depth, ref, ch, colour, L.ptr(d_flag), "pcc_raht_prepare")
+        bargs, nb, match, tv, nr, _keep = _inter_state(cs, sets, origin, depth, ref, ch, colour, L.ptr(d_flag), "pcc_raht_prepare", search)
         first = depth - bargs[-1]
         ph.mark("motion_match_ms")
         values = torch.empty((n, ch), dtype=torch.int32, device=dev)
@@ -827,7 +854,8 @@ def _encode_inter_lossy(what, cs, levels, perm, ref, qp, cqo, colour, mode, segm
         _inter_index(masks, offs, sets, depth, first, ch, bargs, d_mode, d_side, idx, None, None, rows, L.ptr(d_flag))
         body = _rans_body(coef_p, idx, rows * ch, segment_symbols, dev, what)          # one read: size + container
         ph.mark("index_rans_ms")
-        out = bytearray(INTER_LOSSY_HEADER.pack(INTER_LOSSY_MAGIC, n, depth, ch, int(colour), qp, cqo, G.BLOCK_LOG2, G.SEARCH, nb))
+        out = bytearray(INTER_LOSSY_HEADER.pack(WIDE_LOSSY_MAGIC if search > G.MAX_SEARCH else INTER_LOSSY_MAGIC, n, depth, ch, int(colour), qp, cqo,
+                                                G.BLOCK_LOG2, search, nb))
         for q in root:
             out += _zigzag(q)
         out += bytes(side) + np.packbits(modes.astype(bool), bitorder="little").tobytes() + body
@@ -850,7 +878,7 @@ def _encode_inter_lossy(what, cs, levels, perm, ref, qp, cqo, colour, mode, segm
 
 @torch.no_grad()
 def encode_attributes_lossless(cloud, colour=True, attrs=None, predict=True, segment_symbols=SEGMENT_SYMBOLS, timings=None,
-                               reference=None, reference_attrs=None, mode="auto"):
+                               reference=None, reference_attrs=None, mode="auto", search=None):
     """The input forms and refusals of `encode_attributes` -> bytes that `decode_attributes_lossless` turns back into the very
     uint8 levels (colours of an [N, 6] cloud become round(255 c) first).  colour: YCoCg-R in front of the lifting (three
     channels only).  predict: code every butterfly against its prediction from the parent level.  When the coded stream would
@@ -860,8 +888,10 @@ def encode_attributes_lossless(cloud, colour=True, attrs=None, predict=True, seg
     in its row order; distinct voxels, the cloud's channel count, predict=True.  mode "auto": the shorter of the inter (0xB6)
     and the intra (0xB5) stream, intra on a tie and at depth 15 -- never longer than without a reference; "inter": the inter
     stream (fewer than two voxels still travel as intra; depth 15 raises); "intra", or no reference: today's stream byte for
-    byte."""
+    byte.  search: the range of the block vectors the matches come from -- None or 2: 0xB6 as ever; 3 .. 7: the stream 0xB7, the
+    0xB6 layout with that range in its header (no vector travels: the decoder re-runs the wide search)."""
     what = "encode_attributes_lossless"
+    search = _colour_search(search, what)
     cs, levels, perm, ref, depth, inter = _encoder_input(what, cloud, attrs, reference, reference_attrs, mode, bool(predict))
     n, ch, dev = cs.n, levels.shape[1], cs.device
     colour, predict = bool(colour) and ch == 3, bool(predict)
@@ -875,7 +905,7 @@ def encode_attributes_lossless(cloud, colour=True, attrs=None, predict=True, seg
         if inter:
             ph.mark(None, "inter")
             d_flag = torch.zeros(1, dtype=torch.int32, device=dev)
-            bargs, nb, match, tv, nr, _keep = _inter_state(cs, sets, origin, depth, ref, ch, colour, L.ptr(d_flag))
+            bargs, nb, match, tv, nr, _keep = _inter_state(cs, sets, origin, depth, ref, ch, colour, L.ptr(d_flag), search=search)
             ph.mark("motion_match_ms", "inter")
         ph.mark()
         values = torch.empty((n, ch), dtype=torch.int32, device=dev)
@@ -940,7 +970,8 @@ def encode_attributes_lossless(cloud, colour=True, attrs=None, predict=True, seg
                    L.stream())
             body = _rans_body(coef, idx, rows * ch, segment_symbols, dev, what)          # one read: size + container
             ph.mark("inter_index_rans_ms", "inter")
-            coded = bytearray(INTER_HEADER.pack(INTER_MAGIC, n, depth, ch, F_PREDICT | (F_COLOUR if colour else 0), G.BLOCK_LOG2, G.SEARCH, nb))
+            coded = bytearray(INTER_HEADER.pack(WIDE_MAGIC if search > G.MAX_SEARCH else INTER_MAGIC, n, depth, ch, F_PREDICT | (F_COLOUR if colour else 0),
+                                                G.BLOCK_LOG2, search, nb))
             for c in range(ch):
                 coded += _zigzag(int(back[c]))
             coded += bytes(side) + modes + body
@@ -990,7 +1021,8 @@ def decode_attributes_lossless(data, geometry, device=None, reference=None, refe
         if inter:
             if hdr["blocks"] != sets[max(0, depth - G.BLOCK_LOG2)].n:
                 raise L.PccError(f"{what}: the stream codes {hdr['blocks']} blocks, the geometry has {sets[max(0, depth - G.BLOCK_LOG2)].n}")
-            bargs, nb, match, tv, nr, _keep = _inter_state(cs, sets, tuple(cs.bounds.lo), depth, ref, ch, colour, status.data_ptr() + 4)
+            bargs, nb, match, tv, nr, _keep = _inter_state(cs, sets, tuple(cs.bounds.lo), depth, ref, ch, colour, status.data_ptr() + 4,
+                                                           search=hdr["search"])
             d_mode = _block_modes(data, hdr, nb, dev)
             ph.mark("motion_match_ms")
         if rows:

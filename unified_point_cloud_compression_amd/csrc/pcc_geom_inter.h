@@ -1,10 +1,15 @@
 // Block motion of the inter frames, what the geometry coder (pcc_geom_inter.hip) and the colour coder (pcc_lift_inter.hip) share:
-// the candidate vectors in their coded order and the probe of a reference set given in absolute coordinates.
+// the candidate vectors in their coded order, the packed displacements of the wide search, the layout of a block's occupancy
+// pyramid and the probe of a reference set given in absolute coordinates.
 #pragma once
 #include "pcc_common.h"
 #include "pcc_conv.h"
 
 static constexpr int INTER_MAX_CAND = 125;
+
+static constexpr int INTER_PYR = 75;                     // words per block: tier 4 at 0 (64), tier 3 at 64 (8), tiers 2, 1, 0 at 72, 73, 74
+
+__device__ __forceinline__ int inter_tier(int e) { return e == 4 ? 0 : (e == 3 ? 64 : 74 - e); }
 
 struct InterCands { int n; int v[INTER_MAX_CAND]; };     // (dx + 8) | (dy + 8) << 4 | (dz + 8) << 8, by |v|^2 then lexicographically
 
@@ -26,6 +31,17 @@ __device__ inline int inter_row(const PccGrid& g, const int64_t* __restrict__ ke
 __device__ __forceinline__ void inter_cand(const InterCands& c, int j, int& dx, int& dy, int& dz) {
   const int p = c.v[j];
   dx = (p & 15) - 8; dy = ((p >> 4) & 15) - 8; dz = ((p >> 8) & 15) - 8;
+}
+
+// ---- the wide search (pcc_geom_wide.hip): a vector is a packed DISPLACEMENT, the packing of InterCands::v, not an index ----------
+__device__ __forceinline__ int wide_pack(int dx, int dy, int dz) { return (dx + 8) | ((dy + 8) << 4) | ((dz + 8) << 8); }
+
+// the displacement of a packed word, (0, 0, 0) and false when a component leaves +-search
+__device__ __forceinline__ bool wide_unpack(int p, int search, int& dx, int& dy, int& dz) {
+  dx = (p & 15) - 8; dy = ((p >> 4) & 15) - 8; dz = ((p >> 8) & 15) - 8;
+  const bool ok = (p >> 12) == 0 && dx >= -search && dx <= search && dy >= -search && dy <= search && dz >= -search && dz <= search;
+  if (!ok) dx = dy = dz = 0;
+  return ok;
 }
 
 static int inter_cands(int search, const char* who, InterCands* out) {

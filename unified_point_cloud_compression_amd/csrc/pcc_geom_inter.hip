@@ -18,7 +18,6 @@
 static constexpr int INTER_ROWS = 128;
 static constexpr int INTER_HIST = INTER_ROWS * 256;      // [row][symbol], then 8 popcount classes (absent), 9 distance classes (present)
 static constexpr int INTER_CLASSES = 17;
-static constexpr int INTER_PYR = 75;                     // words per block: tier 4 at 0 (64), tier 3 at 64 (8), tiers 2, 1, 0 at 72, 73, 74
 static constexpr int INTER_CDF_STRIDE = 258;
 static constexpr int INTER_CDF_TOTAL = 64 * 257 + 64 * 258;
 
@@ -36,8 +35,6 @@ static constexpr InterRho inter_make_rho() {
   return t;
 }
 __constant__ InterRho INTER_RHO = inter_make_rho();
-
-__device__ __forceinline__ int inter_tier(int e) { return e == 4 ? 0 : (e == 3 ? 64 : 74 - e); }
 
 __device__ __forceinline__ int inter_bit(const unsigned long long* w, int e, int lx, int ly, int lz) {
   const int c = (lx << (2 * e)) | (ly << e) | lz;

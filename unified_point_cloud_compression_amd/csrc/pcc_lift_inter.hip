@@ -4,6 +4,7 @@
 // (pcc_geom_inter.hip); the decoder re-runs the search, so no vector travels.  Levels above the last are coded by pcc_lift.hip.
 //   k_lift_inter_match      per voxel p of a block with vector d: the reference row at p - d or, when that cell is empty, at the
 //                           first occupied of its 26 neighbours by (|o|^2, k = 9 (ox + 1) + 3 (oy + 1) + (oz + 1)); -1: unmatched
+//   k_lift_inter_match_wide the same with a packed displacement per block (the wide search of pcc_geom_wide.hip, streams 0xB7 / 0xB8)
 //   k_lift_inter_residual   per last-level node both residual sets -- rows -= Hp of the spatial prediction, as k_lift_residual, and
 //                           H - Hp of the temporal one (a matched child predicted by its match's values, an unmatched one spatially)
 //                           into a second buffer -- and sum |symbol| of each set added to the node's block (int32, order independent)
@@ -52,6 +53,26 @@ __global__ void __launch_bounds__(256) k_lift_inter_match(const int64_t* __restr
   if (j < 0 || j >= cands.n) { atomicOr(d_flag, 1); j = 0; }
   int dx, dy, dz;
   inter_cand(cands, j, dx, dy, dz);
+  const int qx = ox + pcc_key_x(key) - dx, qy = oy + pcc_key_y(key) - dy, qz = oz + pcc_key_z(key) - dz;
+  int m = -1;
+  for (int d2 = 0; d2 <= 3 && m < 0; ++d2)
+    for (int k = 0; k < 27 && m < 0; ++k) {
+      const int ax = k / 9 - 1, ay = (k / 3) % 3 - 1, az = k % 3 - 1;
+      if (ax * ax + ay * ay + az * az == d2) m = inter_row(rg, rkeys, nr, qx + ax, qy + ay, qz + az);
+    }
+  match[i] = m;
+}
+
+// k_lift_inter_match with a packed displacement per block (the wide search); one outside +-search counts as zero and sets the flag
+__global__ void __launch_bounds__(256) k_lift_inter_match_wide(const int64_t* __restrict__ vkeys, int n, LiftBlocks B, const int* __restrict__ disp,
+                                                               int search, const int64_t* __restrict__ rkeys, int nr, PccGrid rg, int ox,
+                                                               int oy, int oz, int* __restrict__ match, int* __restrict__ d_flag) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t key = vkeys[i];
+  const int row = lift_block_of(B, key);
+  int dx, dy, dz;
+  if (!wide_unpack(row < 0 ? -1 : disp[row], search, dx, dy, dz)) atomicOr(d_flag, 1);
   const int qx = ox + pcc_key_x(key) - dx, qy = oy + pcc_key_y(key) - dy, qz = oz + pcc_key_z(key) - dz;
   int m = -1;
   for (int d2 = 0; d2 <= 3 && m < 0; ++d2)
@@ -275,6 +296,26 @@ extern "C" int pcc_lift_inter_match(const int64_t* voxel_keys, int64_t n, const 
   PCC_REQUIRE(!g.bits || h_ref[6] == 1, "pcc_lift_inter_match: the reference grid must have pitch 1");
   k_lift_inter_match<<<(unsigned)pcc_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(voxel_keys, (int)n, B, vec, c, ref_keys, (int)n_ref, g, ox,
                                                                                 oy, oz, match, d_flag);
+  PCC_LAUNCH_CHECK();
+  return PCC_OK;
+}
+
+extern "C" int pcc_lift_inter_match_wide(const int64_t* voxel_keys, int64_t n, const int64_t* block_keys, int64_t n_blocks,
+                                         const uint64_t* block_bits, const int32_t* block_rank, const int32_t* h_block, int32_t block_log2,
+                                         const int32_t* disp, int32_t search, const int64_t* ref_keys, int64_t n_ref,
+                                         const uint64_t* ref_bits, const int32_t* ref_rank, const int32_t* h_ref, int32_t ox, int32_t oy,
+                                         int32_t oz, int32_t* match, int32_t* d_flag, void* stream) {
+  PCC_REQUIRE(voxel_keys && disp && match && d_flag && n > 0 && n < (1ll << 26), "pcc_lift_inter_match_wide: bad arguments");
+  PCC_REQUIRE(n_ref >= 0 && n_ref < (1ll << 26) && (n_ref == 0 || ref_keys), "pcc_lift_inter_match_wide: bad reference set");
+  PCC_REQUIRE(inter_origin_ok(ox, oy, oz), "pcc_lift_inter_match_wide: origin outside the 16-bit key range");
+  PCC_REQUIRE(search >= 1 && search <= 7, "pcc_lift_inter_match_wide: search range %d outside 1..7", search);
+  LiftBlocks B;
+  if (!lift_blocks("pcc_lift_inter_match_wide", block_keys, n_blocks, block_bits, block_rank, h_block, block_log2, &B)) return PCC_EINVAL;
+  PccGrid g;
+  PCC_TRY(pcc_grid_from_host(n_ref ? ref_bits : nullptr, ref_rank, h_ref, "pcc_lift_inter_match_wide", &g));
+  PCC_REQUIRE(!g.bits || h_ref[6] == 1, "pcc_lift_inter_match_wide: the reference grid must have pitch 1");
+  k_lift_inter_match_wide<<<(unsigned)pcc_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(voxel_keys, (int)n, B, disp, search, ref_keys, (int)n_ref,
+                                                                                     g, ox, oy, oz, match, d_flag);
   PCC_LAUNCH_CHECK();
   return PCC_OK;
 }

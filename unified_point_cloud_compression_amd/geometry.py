@@ -40,10 +40,24 @@ rho^-1(byte XOR predicted byte), rho = 0..255 by (popcount, value), with table r
 own (`derive_tables_inter`).  The kernels are those of csrc/pcc_geom_inter.hip; the encoder's vectors ride in the read that
 fetches the raw levels' bytes, the decoder still reads ONCE, at the end.  `encode_sequence` / `decode_sequence` chain frames.
 
+Wide search (`encode_geometry(x, reference=r, search=3..7)`, DESIGN.md section 7e "Wide search"): the same stream with the block
+vectors searched over [-search, search]^3 by `pcc_geom_wide_motion` and listed as displacements, one component at a time.
+
+    stream  = u8 0xAA | the rest of the 0xA8 layout, search in 3 .. 7, with
+    vectors = per block, in canonical order, the components (dx + search, dy + search, dz + search), each in 0 .. 2 * search:
+              raw:    three bytes each, x y z                                  (fewer than RAW_NODES blocks)
+              coded:  3 x [u8 m | m x (u8 value, u32 count) ascending], one histogram per component, each summing to the blocks
+                      | u32 length | ONE rANS container over the [blocks, 3] components, table row = component, the three rows
+                      built by the rule of `vector_table` with K = 2 * search + 1
+
+Most matches win; ties go to the smaller dx^2 + dy^2 + dz^2, then to the lexicographically smaller (dx, dy, dz) -- the lowest index
+of `candidates(search)`, so the rule of 0xA8.  search = None or 2 writes 0xA8 byte for byte; "auto" codes at 2 and at 7 and keeps
+the shorter stream (2 on a tie).  An 0xA8 stream whose search byte is not 0..2 and an 0xAA stream whose is not 3..7 are refused.
+
 Global motion (`encode_geometry(x, reference=r, global_motion=...)`, DESIGN.md section 7e "Global motion"): one rigid transform
 moves the whole reference before the blocks look at it.
 
-    stream  = u8 0xA9 | 9 x i32 M (Q24, row by row) | 3 x i32 t (Q8 voxels) | an 0xA7 or 0xA8 stream as above        (49 bytes + it)
+    stream  = u8 0xA9 | 9 x i32 M (Q24, row by row) | 3 x i32 t (Q8 voxels) | an 0xA7, 0xA8 or 0xAA stream as above  (49 bytes + it)
 
 The stream behind the transform is coded against `motion.warp_cloud(reference, T)`, an integer warp both sides repeat
 (`pcc_motion_warp`).  `parse_header` checks the transform's ranges on the host; the decoder warps the reference rows as they
@@ -126,6 +140,8 @@ GLOBAL_HEADER = 1 + M.PACKED.size
 BLOCK_LOG2 = 4            # blocks are the nodes at pitch 16: one motion vector each
 SEARCH = 2                # vectors in [-2, 2]^3: 125 candidates, an index fits a byte
 MAX_SEARCH = 2
+MAGIC_WIDE = 0xAA         # the 0xA8 layout with search in WIDE_SEARCH and the vectors listed as displacements, per component
+WIDE_SEARCH = (3, 7)      # dx + 8 fits the 4 bits of a packed displacement, a window column of 16 + 2 * 7 z cells fits a word
 HEADER_INTER = struct.Struct("<BIB3iBB")
 SIDE_INTER = struct.Struct("<8I9III")      # popcount classes of the absent nodes | distance classes of the present | children | length
 N_ROWS = 2 * N_CTX        # table rows: context + 64 * present
@@ -229,9 +245,42 @@ def _parse_vectors(data, at, blocks, k):
     return {"raw": False, "payload": (at, at + nbytes), "hist": hist, "streams": streams}, at + nbytes
 
 
+def _parse_vectors_wide(data, at, blocks, search):
+    """The vector list of an 0xAA stream: (dict(raw, payload, hist, streams), end); hist = the three component histograms."""
+    k = 2 * search + 1
+    if blocks < RAW_NODES:
+        if at + 3 * blocks > len(data):
+            raise L.PccError("geometry stream truncated inside the vector list")
+        if max(data[at:at + 3 * blocks]) >= k:
+            raise L.PccError(f"geometry stream: a vector component outside 0..{k - 1}")
+        return {"raw": True, "payload": (at, at + 3 * blocks), "hist": None, "streams": 0}, at + 3 * blocks
+    hists = []
+    for axis in "xyz":
+        if at + 1 > len(data) or at + 1 + 5 * data[at] > len(data):
+            raise L.PccError("geometry stream truncated inside the vector histograms")
+        hist, last = [0] * k, -1
+        for j in range(data[at]):
+            i, c = struct.unpack_from("<BI", data, at + 1 + 5 * j)
+            if not last < i < k or c == 0:
+                raise L.PccError(f"geometry stream: the {axis} histogram of the vectors lists components 0..{k - 1} in ascending order, "
+                                 "each with a count")
+            hist[i], last = c, i
+        if sum(hist) != blocks:
+            raise L.PccError(f"geometry stream: the {axis} histogram of the vectors counts {sum(hist)} of {blocks} blocks")
+        at += 1 + 5 * data[at]
+        hists.append(hist)
+    if at + 4 > len(data):
+        raise L.PccError("geometry stream truncated inside the vector histograms")
+    nbytes = int.from_bytes(data[at:at + 4], "little")
+    at += 4
+    streams = _container_streams(data, at, nbytes, 3 * blocks, "the vector list")
+    return {"raw": False, "payload": (at, at + nbytes), "hist": hists, "streams": streams}, at + nbytes
+
+
 def parse_header(data, have_reference=True):
     """Walk the stream on the host: {n, depth, origin, levels}; levels[l] = dict(nodes, children, raw, payload=(begin, end),
-    pop).  An inter stream (0xA8) adds inter=True, block_log2, search, first (the level of the blocks) and vectors = dict(raw,
+    pop).  An inter stream (0xA8, or 0xAA: the wide search, whose `vectors["hist"]` are three component histograms) adds
+    inter=True, block_log2, search, first (the level of the blocks) and vectors = dict(raw,
     payload, hist, streams); its levels carry `inter` (coded against the prediction) and, coded ones of those, `dist`.  Raises PccError on a bad magic byte, depth, n, block size or search
     range, on an inter stream when the caller has no reference, on truncated or inconsistent side information and on trailing
     bytes -- before any GPU work.  A global-motion wrapper (0xA9) is refused without a reference too; its transform's ranges are
@@ -251,19 +300,21 @@ def parse_header(data, have_reference=True):
     if len(data) < HEADER.size:
         raise L.PccError("geometry stream truncated inside the header")
     magic, n, depth, ox, oy, oz = HEADER.unpack_from(data, 0)
-    if magic not in (MAGIC, MAGIC_INTER):
-        raise L.PccError(f"geometry stream: magic byte {magic:#x}, this build reads {MAGIC:#x}, {MAGIC_INTER:#x} and {MAGIC_GLOBAL:#x}")
-    inter = magic == MAGIC_INTER
+    if magic not in (MAGIC, MAGIC_INTER, MAGIC_WIDE):
+        raise L.PccError(f"geometry stream: magic byte {magic:#x}, this build reads {MAGIC:#x}, {MAGIC_INTER:#x}, {MAGIC_GLOBAL:#x} and "
+                         f"{MAGIC_WIDE:#x}")
+    inter, wide = magic != MAGIC, magic == MAGIC_WIDE
     at, first, k, block_log2, search = HEADER.size, depth, 1, 0, 0
     if inter:
         if not have_reference:
-            raise L.PccError("geometry stream: an inter stream (0xa8) decodes against a reference cloud, none was given")
+            raise L.PccError(f"geometry stream: an inter stream ({magic:#x}) decodes against a reference cloud, none was given")
         if len(data) < HEADER_INTER.size:
             raise L.PccError("geometry stream truncated inside the header")
         block_log2, search = data[at], data[at + 1]
         at = HEADER_INTER.size
-        if block_log2 != BLOCK_LOG2 or search > MAX_SEARCH:
-            raise L.PccError(f"geometry stream: block_log2 {block_log2} / search {search}, this build reads {BLOCK_LOG2} / 0..{MAX_SEARCH}")
+        lo, hi = WIDE_SEARCH if wide else (0, MAX_SEARCH)
+        if block_log2 != BLOCK_LOG2 or not lo <= search <= hi:
+            raise L.PccError(f"geometry stream ({magic:#x}): block_log2 {block_log2} / search {search}, this build reads {BLOCK_LOG2} / {lo}..{hi}")
         if n == 0:
             raise L.PccError("geometry stream: an empty cloud travels as an intra stream")
         first, k = max(0, depth - block_log2), (2 * search + 1) ** 3
@@ -281,7 +332,7 @@ def parse_header(data, have_reference=True):
     nodes, levels, vectors = 1, [], None
     for lvl in range(depth):
         if inter and lvl == first:
-            vectors, at = _parse_vectors(data, at, nodes, k)
+            vectors, at = _parse_vectors_wide(data, at, nodes, search) if wide else _parse_vectors(data, at, nodes, k)
         if nodes < RAW_NODES:
             if at + nodes > len(data):
                 raise L.PccError(f"geometry stream truncated inside raw level {lvl}")
@@ -407,7 +458,7 @@ def reference_set(reference, what="encode_geometry"):
 
 
 @torch.no_grad()
-def encode_geometry(x, segment_nodes=SEGMENT_NODES, timings=None, reference=None, mode="auto", global_motion=None):
+def encode_geometry(x, segment_nodes=SEGMENT_NODES, timings=None, reference=None, mode="auto", global_motion=None, search=None):
     """[N, >= 3] GPU tensor (any row order, duplicates allowed, floats floored) or pitch-1 CoordSet -> bytes.
     segment_nodes: nodes per rANS stream (tests lower it to cut small levels into several streams; the decoder reads the
     stream count from each container).  timings: a dict that receives per-level device events (tools/geometry_timing.py).
@@ -419,27 +470,32 @@ def encode_geometry(x, segment_nodes=SEGMENT_NODES, timings=None, reference=None
     stream u8 0xA9 | 12 x i32 T | the stream above coded against `motion.warp_cloud(reference, T)` under `mode` (a reference
     is required).  "auto" -- T = `motion.estimate_rigid(x, reference)`; the wrapper and the plain stream are both coded and
     the shorter one is returned, the plain one on a tie, when nothing matches or T is the identity: never longer than without
-    global motion."""
+    global motion.
+    search (DESIGN.md section 7e "Wide search"): the range of the block vectors of an inter stream.  None or 2 -- [-2, 2]^3, the
+    0xA8 stream, today's bytes.  3 .. 7 -- [-search, search]^3, the 0xAA stream.  "auto" -- coded at 2 and at 7, the shorter stream
+    is kept, 2 on a tie; with mode "auto" that stream is then compared with the intra one as before, so a wider search never
+    costs bytes, only encode time.  0 and 1 are refused: the encoder has never written them."""
     if mode not in ("auto", "inter", "intra"):
         raise L.PccError(f"encode_geometry: mode {mode!r} is not one of auto, inter, intra")
+    search = check_search(search, "encode_geometry")
     if not (global_motion is None or isinstance(global_motion, M.RigidTransform) or (isinstance(global_motion, str) and global_motion == "auto")):
         raise L.PccError(f"encode_geometry: global_motion {global_motion!r} is not None, \"auto\" or a RigidTransform")
     cs = _input_set(x)
     if isinstance(global_motion, M.RigidTransform):
         if reference is None:
             raise L.PccError("encode_geometry: a global motion transform needs the reference it moves")
-        return _encode_global(cs, reference_set(reference), global_motion, mode, segment_nodes, timings)
+        return _encode_global(cs, reference_set(reference), global_motion, mode, segment_nodes, timings, search)
     if reference is None or mode == "intra" or cs.n == 0:
         return _encode(cs, INTRA, segment_nodes, timings)
     rs = reference_set(reference)
-    plain = _encode_against(cs, rs, mode, segment_nodes, timings)
+    plain = _encode_against(cs, rs, mode, segment_nodes, timings, search)
     if global_motion is None or rs is None:
         return plain
     T = M.estimate_rigid(cs, rs)
     if T is None or T.is_identity():
         return plain
     tw = {} if timings is not None else None
-    wrapped = _encode_global(cs, rs, T, mode, segment_nodes, tw)
+    wrapped = _encode_global(cs, rs, T, mode, segment_nodes, tw, search)
     take = len(wrapped) < len(plain)
     if timings is not None:
         if take:                                   # the events of the stream that is returned, not of the discarded one
@@ -449,18 +505,50 @@ def encode_geometry(x, segment_nodes=SEGMENT_NODES, timings=None, reference=None
     return wrapped if take else plain
 
 
-def _encode_global(cs, rs, T, mode, segment_nodes, timings):
+def _encode_global(cs, rs, T, mode, segment_nodes, timings, search=SEARCH):
     """The wrapper stream (0xA9) of the canonical set `cs`: the transform, then `cs` against the warped reference set."""
     ws = M.warp_set(rs, T) if rs is not None else None
     if ws is not None and ws.n == 0:
         ws = None
-    inner = _encode(cs, INTRA, segment_nodes, timings) if (mode == "intra" or cs.n == 0) else _encode_against(cs, ws, mode, segment_nodes, timings)
+    inner = _encode(cs, INTRA, segment_nodes, timings) if (mode == "intra" or cs.n == 0) else _encode_against(cs, ws, mode, segment_nodes, timings, search)
     return bytes([MAGIC_GLOBAL]) + T.pack() + inner
 
 
-def _encode_against(cs, rs, mode, segment_nodes, timings):
-    """The stream of the canonical non-empty set `cs` against the reference set `rs` (None: empty) under mode "inter" / "auto"."""
-    inter = _encode(cs, rs, segment_nodes, timings)
+def check_search(search, what):
+    """The search range an encoder was asked for: SEARCH for None, an int in 2 .. 7, or "auto" (shared with attributes.py)."""
+    if search is None:
+        return SEARCH
+    if isinstance(search, str) and search == "auto":
+        return search
+    if isinstance(search, bool) or not isinstance(search, int) or not SEARCH <= search <= WIDE_SEARCH[1]:
+        raise L.PccError(f"{what}: search {search!r} is not None, \"auto\" or an int in {SEARCH} .. {WIDE_SEARCH[1]} (ranges 0 and 1 are read "
+                         "but never written)")
+    return search
+
+
+def stream_search(data):
+    """The search range a geometry stream ended with: its header's byte for an inter stream (0xA8 / 0xAA, also behind a global-motion
+    wrapper), SEARCH for an intra one -- the range a colour coder that follows the geometry uses."""
+    at = GLOBAL_HEADER if len(data) >= 1 and data[0] == MAGIC_GLOBAL else 0
+    if len(data) >= at + HEADER_INTER.size and data[at] in (MAGIC_INTER, MAGIC_WIDE):
+        return data[at + HEADER_INTER.size - 1]
+    return SEARCH
+
+
+def _encode_against(cs, rs, mode, segment_nodes, timings, search=SEARCH):
+    """The stream of the canonical non-empty set `cs` against the reference set `rs` (None: empty) under mode "inter" / "auto"
+    with the search range `search` (an int, or "auto": the shorter of SEARCH and the widest range, SEARCH on a tie)."""
+    if search == "auto":
+        inter = _encode(cs, rs, segment_nodes, timings)
+        tw = {} if timings is not None else None
+        widest = _encode(cs, rs, segment_nodes, tw, WIDE_SEARCH[1])
+        if len(widest) < len(inter):
+            inter = widest
+            if timings is not None:                    # the events of the stream that is kept
+                timings.clear()
+                timings.update(tw)
+    else:
+        inter = _encode(cs, rs, segment_nodes, timings, search)
     if mode == "inter":
         return inter
     intra = _encode(cs, INTRA, segment_nodes, None)
@@ -501,9 +589,11 @@ class Phases:
         return out
 
 
-def motion_vectors(cs, rs, origin, depth, sets=None, counts=False):
+def motion_vectors(cs, rs, origin, depth, sets=None, counts=False, search=SEARCH):
     """(blocks set, block_log2 of this cloud, current pyramid, int32 vector index per block[, int32 match counts [blocks, K]]) of
-    the canonical set `cs` against the reference `rs`: `pcc_geom_inter_block_bits` on the frame itself, `pcc_geom_inter_motion`."""
+    the canonical set `cs` against the reference `rs`: `pcc_geom_inter_block_bits` on the frame itself, `pcc_geom_inter_motion`.
+    search above 2: `pcc_geom_wide_motion`, which gives packed displacements (dx + 8) | (dy + 8) << 4 | (dz + 8) << 8 in place of
+    indices and the counts in lexicographic (dx, dy, dz) order."""
     lib = L.load()
     dev = cs.device
     sets = level_sets(cs, origin, depth) if sets is None else sets
@@ -514,20 +604,20 @@ def motion_vectors(cs, rs, origin, depth, sets=None, counts=False):
     cur = torch.empty(blocks.n * pw, dtype=torch.int64, device=dev)
     bad = torch.zeros(1, dtype=torch.int32, device=dev)
     vec = torch.empty(blocks.n, dtype=torch.int32, device=dev)
-    cnt = torch.empty((blocks.n, (2 * SEARCH + 1) ** 3), dtype=torch.int32, device=dev) if counts else None
+    cnt = torch.empty((blocks.n, (2 * search + 1) ** 3), dtype=torch.int32, device=dev) if counts else None
     L.call("pcc_geom_inter_block_bits", L.ptr(blocks.keys), blocks.n, bl, L.ptr(voxels.keys), voxels.n,
            *S.grid_args(voxels.grid() if S.USE_GRID else None), 0, 0, 0, None, SEARCH, L.ptr(cur), L.ptr(bad), L.stream())
-    L.call("pcc_geom_inter_motion", L.ptr(blocks.keys), blocks.n, bl, L.ptr(cur), *ref_args(rs), *origin, SEARCH, L.ptr(cnt), L.ptr(vec),
-           L.stream())
+    L.call("pcc_geom_wide_motion" if search > MAX_SEARCH else "pcc_geom_inter_motion", L.ptr(blocks.keys), blocks.n, bl, L.ptr(cur),
+           *ref_args(rs), *origin, search, L.ptr(cnt), L.ptr(vec), L.stream())
     return (blocks, bl, cur, vec, cnt) if counts else (blocks, bl, cur, vec)
 
 
 INTRA = object()          # `_encode(cs, INTRA, ...)`: no reference at all (None is the empty reference of an inter stream)
 
 
-def _encode(cs, rs, segment_nodes, timings):
-    """The stream of the canonical set `cs`: intra (0xA7) when `rs` is INTRA, else inter (0xA8) against the reference set `rs`
-    (None: empty).  One walk over the levels: those above `first` (= depth for an intra stream) take the intra kernels, the
+def _encode(cs, rs, segment_nodes, timings, search=SEARCH):
+    """The stream of the canonical set `cs`: intra (0xA7) when `rs` is INTRA, else inter (0xA8; 0xAA when `search` is above 2)
+    against the reference set `rs` (None: empty).  One walk over the levels: those above `first` (= depth for an intra stream) take the intra kernels, the
     others the inter ones.  Device->host reads: bounds, level sizes, every level's histograms, the raw levels' bytes (an inter
     stream's vectors ride in that read), the payload."""
     n = cs.n
@@ -538,7 +628,9 @@ def _encode(cs, rs, segment_nodes, timings):
     depth = max(1, max(cs.bounds.hi[i] - origin[i] for i in range(3)).bit_length())
     first = max(0, depth - BLOCK_LOG2) if inter else depth
     rows = N_ROWS if inter else N_CTX
-    k_vec = (2 * SEARCH + 1) ** 3
+    wide = inter and search > MAX_SEARCH
+    k_vec = (2 * search + 1) if wide else (2 * SEARCH + 1) ** 3          # the alphabet of a vector symbol: a component, or an index
+    per = 3 if wide else 1                                               # symbols per block in the vector list
     dev = cs.device
     lib = L.load()
     ph = Phases(timings is not None)
@@ -554,13 +646,16 @@ def _encode(cs, rs, segment_nodes, timings):
         words = [lib.pcc_geom_hist_words()] * first
         nb = 0
         if inter:
-            blocks, bl, _, vec = motion_vectors(cs, rs, origin, depth, sets)
+            blocks, bl, _, vec = motion_vectors(cs, rs, origin, depth, sets, search=search)
             ph.mark("motion_search_ms")
             nb = blocks.n
             bgrid = blocks.grid() if (first and S.USE_GRID) else None
             pred = torch.empty(nb * lib.pcc_geom_inter_pyramid_words(), dtype=torch.int64, device=dev)
-            L.call("pcc_geom_inter_block_bits", L.ptr(blocks.keys), nb, bl, *ref_args(rs), *origin, L.ptr(vec), SEARCH, L.ptr(pred), L.ptr(bad),
-                   L.stream())
+            L.call("pcc_geom_wide_block_bits" if wide else "pcc_geom_inter_block_bits", L.ptr(blocks.keys), nb, bl, *ref_args(rs), *origin,
+                   L.ptr(vec), search, L.ptr(pred), L.ptr(bad), L.stream())
+            if wide:                                                    # what the vector list codes: [blocks, 3] components
+                disp, vec = vec, torch.empty(3 * nb, dtype=torch.int32, device=dev)
+                L.call("pcc_geom_wide_unpack", L.ptr(disp), nb, search, L.ptr(vec), L.stream())
             ph.mark("compensation_ms")
             byte = torch.empty(at[-1], dtype=torch.int32, device=dev)   # the occupancy bytes of the inter levels (raw levels travel as these)
             words += [lib.pcc_geom_inter_hist_words()] * (depth - first)
@@ -592,13 +687,13 @@ def _encode(cs, rs, segment_nodes, timings):
             for l in raw_lv:
                 raw_bytes[l] = got[p:p + nodes[l]].tobytes()
                 p += nodes[l]
-            h_vec = got[p:p + nb]
+            h_vec = got[p:p + per * nb]
         # containers: the vector list (when it is coded) and the coded levels, tables from the levels before, one rANS launch each
         # into a shared blob [sizes | containers]
         code_vec = inter and k_vec > 1 and nb >= RAW_NODES
         symbols = {l: nodes[l] for l in range(depth) if nodes[l] >= RAW_NODES}
         if code_vec:
-            symbols = {"vec": nb, **symbols}
+            symbols = {"vec": per * nb, **symbols}
         jobs = list(symbols)
         plans = {j: R.Plan(symbols[j], 1, 1, segments_for(symbols[j], segment_nodes)) for j in jobs}
         caps = {j: R.align8(plans[j].capacity) for j in jobs}
@@ -616,11 +711,11 @@ def _encode(cs, rs, segment_nodes, timings):
             begin += caps[job]
 
         if code_vec:
-            v_hist = np.bincount(h_vec, minlength=k_vec)
-            v_idx = torch.zeros(nb, dtype=torch.int32, device=dev)
+            v_hist = [np.bincount(h_vec[c::per], minlength=k_vec) for c in range(per)]
+            v_idx = torch.arange(per * nb, dtype=torch.int32, device=dev) % per        # table row = component (one row: an index)
             keep.append(v_idx)
-            run("vec", R.fresh_cdf_tables(f"geometry_vectors{k_vec}", dev, vector_table(v_hist), np.array([k_vec + 2], dtype=np.int32),
-                                          np.zeros(1, dtype=np.int32)), L.ptr(vec), L.ptr(v_idx))
+            run("vec", R.fresh_cdf_tables(f"geometry_vectors{per}x{k_vec}", dev, np.concatenate([vector_table(h) for h in v_hist]),
+                                          np.full(per, k_vec + 2, dtype=np.int32), np.zeros(per, dtype=np.int32)), L.ptr(vec), L.ptr(v_idx))
         # backward-adaptive (row, byte) counts: after every level (raw ones included) the old counts are halved and the level's are added
         state = np.zeros((rows, 256), dtype=np.int64)
         side = {}
@@ -648,13 +743,15 @@ def _encode(cs, rs, segment_nodes, timings):
             raise L.PccError(f"encode_geometry: {'container' if inter else 'level'} {job} produced {got} bytes for a capacity of {cap}")
         return host[b0:b0 + got].tobytes()
 
-    out = bytearray(HEADER_INTER.pack(MAGIC_INTER, n, depth, *origin, BLOCK_LOG2, SEARCH) if inter else HEADER.pack(MAGIC, n, depth, *origin))
+    out = bytearray(HEADER_INTER.pack(MAGIC_WIDE if wide else MAGIC_INTER, n, depth, *origin, BLOCK_LOG2, search) if inter
+                    else HEADER.pack(MAGIC, n, depth, *origin))
     for l in range(depth):
         if l == first and k_vec > 1:
             if code_vec:
-                occ = np.flatnonzero(v_hist)
                 body = container("vec")
-                out += struct.pack("<B", len(occ)) + b"".join(struct.pack("<BI", int(i), int(v_hist[i])) for i in occ)
+                for h in v_hist:
+                    occ = np.flatnonzero(h)
+                    out += struct.pack("<B", len(occ)) + b"".join(struct.pack("<BI", int(i), int(h[i])) for i in occ)
                 out += struct.pack("<I", len(body)) + body
             else:
                 out += h_vec.tobytes()
@@ -671,7 +768,7 @@ def _encode(cs, rs, segment_nodes, timings):
     if timings is not None:
         torch.cuda.synchronize(dev)
         if inter:
-            timings.update(inter=ph.report(), blocks=nb, zero_vectors=int((h_vec == 0).sum()))
+            timings.update(inter=ph.report(), blocks=nb, zero_vectors=int((h_vec.reshape(nb, per) == (search if wide else 0)).all(axis=1).sum()))
         else:
             timings["levels"] = [{"level": l, "nodes": nodes[l], **ph.report(l)} for l in range(depth)]
         # by construction, not counted: the input's bounds, the stride chain's sizes, the histograms | the raw levels' bytes + the
@@ -718,7 +815,7 @@ def _payloads(data, levels, vectors=None, blocks=0):
     if vectors is not None and vectors["raw"]:
         b0, b1 = vectors["payload"]
         raw_at["vec"] = len(raw)
-        raw.extend(data[b0:b1] if b1 > b0 else [0] * blocks)
+        raw.extend(data[b0:b1] if b1 > b0 else [0] * blocks)               # (one index, or three components, per block)
     elif vectors is not None:
         jobs, spans = jobs + ["vec"], spans + [vectors["payload"]]
     buf, offsets = R.stage(data, spans)
@@ -750,7 +847,9 @@ def _decode(hdr, data, dev, rs, as_set, timings):
                         dec=torch.zeros(lib.pcc_geom_dec_table_bytes(), dtype=torch.uint8, device=dev))
         if inter:
             search, bl = hdr["search"], depth - first
-            k_vec = (2 * search + 1) ** 3
+            wide = search > MAX_SEARCH
+            k_vec = (2 * search + 1) if wide else (2 * search + 1) ** 3
+            per = 3 if wide else 1
             words += [lib.pcc_geom_inter_hist_words()] * (depth - first)
             consti = R.fixed_tables("geometry_inter", dev, None, INTER_SIZES, INTER_OFFSETS)
             tabsi = R.Tables(torch.empty((N_ROWS, INTER_STRIDE), dtype=torch.int32, device=dev), consti.sizes, consti.offsets,
@@ -772,19 +871,23 @@ def _decode(hdr, data, dev, rs, as_set, timings):
             if l == first:
                 vp = flags.data_ptr() + 32 * depth
                 if vh["raw"]:
-                    vec = d_raw[raw_at["vec"]:raw_at["vec"] + nb]
+                    vec = d_raw[raw_at["vec"]:raw_at["vec"] + per * nb]
                 else:
-                    v_cdf, v_sizes = vector_table(vh["hist"]), np.array([k_vec + 2], dtype=np.int32)
-                    v_const = R.fixed_tables(f"geometry_vectors{k_vec}", dev, None, v_sizes, np.zeros(1, dtype=np.int32))
-                    vt = R.Tables(torch.from_numpy(v_cdf).to(dev), v_const.sizes, v_const.offsets,     # (the header's histogram: host work)
+                    v_hists = vh["hist"] if wide else [vh["hist"]]
+                    v_cdf, v_sizes = np.concatenate([vector_table(h) for h in v_hists]), np.full(per, k_vec + 2, dtype=np.int32)
+                    v_const = R.fixed_tables(f"geometry_vectors{per}x{k_vec}", dev, None, v_sizes, np.zeros(per, dtype=np.int32))
+                    vt = R.Tables(torch.from_numpy(v_cdf).to(dev), v_const.sizes, v_const.offsets,     # (the header's histograms: host work)
                                   dec=torch.from_numpy(R._dec_blob(v_cdf, v_sizes)).to(dev))
-                    vec = torch.empty(nb, dtype=torch.int32, device=dev)
-                    R.decode(vt, d_buf.data_ptr() + where["vec"], vh["payload"][1] - vh["payload"][0], torch.zeros(nb, dtype=torch.int32, device=dev),
-                             nb, 1, 1, vh["streams"], vec, vp)
+                    vec = torch.empty(per * nb, dtype=torch.int32, device=dev)
+                    R.decode(vt, d_buf.data_ptr() + where["vec"], vh["payload"][1] - vh["payload"][0],
+                             torch.arange(per * nb, dtype=torch.int32, device=dev) % per, per * nb, 1, 1, vh["streams"], vec, vp)
+                if wide:                                                # components -> displacements; one above 2 * search sets the flag
+                    comps, vec = vec.contiguous(), torch.empty(nb, dtype=torch.int32, device=dev)
+                    L.call("pcc_geom_wide_pack", L.ptr(comps), nb, search, L.ptr(vec), vp + 4, L.stream())
                 bkeys, bgrid = keys, grid
                 pred = torch.empty(nb * lib.pcc_geom_inter_pyramid_words(), dtype=torch.int64, device=dev)
-                L.call("pcc_geom_inter_block_bits", L.ptr(bkeys), nb, bl, *ref_args(rs), *origin, L.ptr(vec), search, L.ptr(pred), vp + 4,
-                       L.stream())
+                L.call("pcc_geom_wide_block_bits" if wide else "pcc_geom_inter_block_bits", L.ptr(bkeys), nb, bl, *ref_args(rs), *origin,
+                       L.ptr(vec), search, L.ptr(pred), vp + 4, L.stream())
                 ph.mark("vectors_compensation_ms")
             if l < first:
                 ctx = torch.empty(m, dtype=torch.int32, device=dev)
@@ -876,7 +979,7 @@ def _decode(hdr, data, dev, rs, as_set, timings):
 def decode_geometry(data, device, as_set=False, reference=None, timings=None):
     """bytes -> int32 [n, 3] rows (x, y, z) in canonical order on `device`; as_set=True: the canonical pitch-1 CoordSet
     instead (no caller re-sorts).  Raises PccError on a malformed stream; never returns anything but exactly the header's n
-    rows.  reference: the cloud an inter stream (0xA8) was coded against (same kinds of input as `encode_geometry` takes);
+    rows.  reference: the cloud an inter stream (0xA8, 0xAA) was coded against (same kinds of input as `encode_geometry` takes);
     an intra stream ignores it, an inter stream without one is refused.
 
     Every buffer and launch is sized by what `parse_header` derived on the host (each level's nodes <= children <= n); the
@@ -919,10 +1022,11 @@ def stream_transform(data):
     return M.RigidTransform.unpack(data[1:GLOBAL_HEADER])
 
 
-def encode_sequence(frames, intra_period=32, mode="auto", segment_nodes=SEGMENT_NODES, global_motion=None):
+def encode_sequence(frames, intra_period=32, mode="auto", segment_nodes=SEGMENT_NODES, global_motion=None, search=None):
     """One stream per frame: frame i is coded against frame i - 1, every `intra_period`-th frame (0, intra_period, ...) without a
     reference.  The coder is lossless, so the decoder's previous frame is the encoder's.  mode and global_motion as in
-    `encode_geometry` (global_motion applies to the frames that have a reference; `decode_sequence` reads it from the streams)."""
+    `encode_geometry` (global_motion applies to the frames that have a reference; `decode_sequence` reads it from the streams);
+    search as in `encode_geometry`, for the frames that have a reference."""
     if int(intra_period) < 1:
         raise L.PccError(f"encode_sequence: intra_period {intra_period} must be at least 1")
     out, prev = [], None
@@ -930,7 +1034,7 @@ def encode_sequence(frames, intra_period=32, mode="auto", segment_nodes=SEGMENT_
         cs = _input_set(frame)
         ref = None if i % int(intra_period) == 0 else prev
         out.append(encode_geometry(cs, segment_nodes=segment_nodes, reference=ref, mode=mode,
-                                   global_motion=global_motion if ref is not None else None))
+                                   global_motion=global_motion if ref is not None else None, search=search))
         prev = cs
     return out
 

@@ -168,7 +168,11 @@ SIGNATURES = {
     "pcc_geom_inter_hist": (C.c_int, [_p, _p, _i64, _p, _p, _p]),
     "pcc_geom_inter_dec_table_bytes": (_i64, []),
     "pcc_geom_inter_tables": (C.c_int, [_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _p, _p, _p]),
-    "pcc_motion_warp": (C.c_int, [_p, _i64, C.POINTER(_i32), _p, _p, _p]),
+    "pcc_geom_wide_motion": (C.c_int, [_p, _i64, _i32, _p, _p, _i64, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p]),
+    "pcc_geom_wide_block_bits": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _p, _p, _i32, _i32, _i32, _p, _i32, _p, _p, _p]),
+    "pcc_geom_wide_pack": (C.c_int, [_p, _i64, _i32, _p, _p, _p]),
+    "pcc_geom_wide_unpack": (C.c_int, [_p, _i64, _i32, _p, _p]),
+    "pcc_motion_warp":(C.c_int, [_p, _i64, C.POINTER(_i32), _p, _p, _p]),
     "pcc_motion_gather": (C.c_int, [_p, _i32, _i64, _p, _p, _i64, _p, _p]),
     "pcc_motion_icp_ws_bytes": (_sz, [_i64]),
     "pcc_motion_icp_terms": (C.c_int, [_p, _i64, _p, _i64, _p, _p, C.POINTER(_i32), _p, C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -201,6 +205,8 @@ SIGNATURES = {
                                    _p]),
     "pcc_lift_finish": (C.c_int, [_p, _i64, _i32, _i32, _p, _p, _p]),
     "pcc_lift_inter_match": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _p, _i32, _p, _i32, _p, _i64, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p]),
+    "pcc_lift_inter_match_wide": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _p, _i32, _p, _i32, _p, _i64, _p, _p, _p, _i32, _i32, _i32, _p, _p,
+                                            _p]),
     "pcc_lift_inter_residual": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _i64, _p, _p, _p, _i32, _p, _p, _i32, _p, _p,
                                           _i64, _p, _p, _i64, _i64, _p, _p, _p]),
     "pcc_lift_inter_select": (C.c_int, [_p, _p, _p, _i64, _i32, _i32, _p, _i64, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p]),

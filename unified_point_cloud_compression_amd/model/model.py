@@ -376,11 +376,12 @@ class UnifiedModel(CompressionModel):
 
     # ---- lossless geometry, lossy colour: the voxels travel in a geometry stream of their own ---------
     @torch.no_grad()
-    def compress_lossless_geometry(self, pointcloud, q, block_size=1024, reference=None):
+    def compress_lossless_geometry(self, pointcloud, q, block_size=1024, reference=None, search=None):
         """-> (strings, shapes, geometry, q_vals), one entry per block of `partition`: the latents' strings as `compress` codes
         them and `geometry[i]` = `encode_geometry` of the block's input set.  Neither k nor the latent coordinates are
         returned: `decompress_lossless_geometry` derives both from the decoded voxels.  reference: a voxel cloud the decoder
-        holds too (the previous frame); every block's geometry is coded against the whole of it where that is shorter."""
+        holds too (the previous frame); every block's geometry is coded against the whole of it where that is shorter.
+        search: the block vectors' range of those streams, as in `geometry.encode_geometry` (None, 2 .. 7 or "auto")."""
         from ..geometry import encode_geometry, reference_set
         if not pointcloud.is_cuda:
             raise L.PccError("compress_lossless_geometry expects the point cloud on the GPU")
@@ -392,7 +393,7 @@ class UnifiedModel(CompressionModel):
             symbols, shape, _, _ = self.compress_block(x_block, q, sets=sets)
             strings.append(symbols)
             shapes.append(shape)
-            geometry.append(encode_geometry(sets[-1], reference=reference))
+            geometry.append(encode_geometry(sets[-1], reference=reference, search=search))
             q_vals.append(q)
         return strings, shapes, geometry, q_vals
 
