@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel identity of two builds of csrc/: a plain diff, CPU only, runs no kernel.
 
-    tools/kernel_identity.py PARENT_CSRC NEW_CSRC [--arch gfx950] [--llvm /opt/rocm/llvm/bin]
+    tools/kernel_identity.py PARENT_CSRC NEW_CSRC [--arch gfx950] [--llvm /opt/rocm/llvm/bin] [--rename OLD=NEW ...]
 
 Both directories hold the *.o files of a `make` of csrc/.  The gfx950 code object of every object file is unbundled, every
 kernel is keyed by its mangled name across the WHOLE library (kernels may move between object files), and for each name the
@@ -11,6 +11,8 @@ two builds are compared in
     of the `llvm-readelf --notes` metadata.
 Device functions (code symbols without a kernel descriptor) are listed and compared the same way.  A kernel found in more than
 one object file of a build (a template kernel launched from two sources is compiled twice) is counted and named for each build.
+--rename OLD=NEW (repeatable) reads the parent's source name OLD as NEW in every mangled name, so that a kernel whose parameter
+type was renamed is compared with its successor and not listed as removed and added.
 Exit status 0 when the kernel names are the same set, every kernel is identical and no kernel of the new build sits in more than
 one object file, 1 otherwise.
 """
@@ -84,9 +86,27 @@ def metadata(co, llvm):
     return out
 
 
-def load(csrc, arch, llvm):
+def renamer(pairs):
+    """OLD=NEW options -> a function on text: every mangled source name <len>OLD becomes <len>NEW (type, function and kernel
+    names alike; substitutions inside a mangled name keep their positions when a name is only replaced)"""
+    subs = []
+    for pair in pairs:
+        old, _, new = pair.partition("=")
+        if not old or not new:
+            sys.exit("--rename takes OLD=NEW, got %r" % pair)
+        subs.append((re.compile(r"(?<![0-9])%d%s" % (len(old), re.escape(old))), "%d%s" % (len(new), new)))   # the length ends the name
+
+    def apply(text):
+        for pat, to in subs:
+            text = pat.sub(to, text)
+        return text
+    return apply
+
+
+def load(csrc, arch, llvm, rename=lambda text: text):
     """kernels {name: (object, instructions, fields)}, device functions {name: (object, instructions)}, objects without code,
-    {kernel name: [objects]} of the kernels found in more than one object file"""
+    {kernel name: [objects]} of the kernels found in more than one object file.  rename: applied to every symbol name before it
+    is keyed, and to the branch targets of the instruction text, which name their symbol"""
     kernels, funcs, empty, where = {}, {}, [], {}
     with tempfile.TemporaryDirectory() as tmp:
         for obj in sorted(glob.glob(os.path.join(csrc, "*.o"))):
@@ -95,7 +115,8 @@ def load(csrc, arch, llvm):
             if co is None:
                 empty.append(base)
                 continue
-            dis, meta = disassembly(co, llvm), metadata(co, llvm)
+            dis = {rename(name): [rename(line) for line in ins] for name, ins in disassembly(co, llvm).items()}
+            meta = {rename(name): fields for name, fields in metadata(co, llvm).items()}
             for name, ins in dis.items():
                 if name in meta:
                     if name in kernels and kernels[name][1:] != (ins, {f: meta[name].get(f) for f in FIELDS}):
@@ -127,8 +148,11 @@ def main():
     ap.add_argument("--arch", default="gfx950")
     ap.add_argument("--llvm", default="/opt/rocm/llvm/bin")
     ap.add_argument("--diff", type=int, default=20, help="lines of instruction diff printed per differing kernel")
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW",
+                    help="a source name (type, function) that the new build spells NEW: applied to the parent's symbol names before "
+                         "they are keyed, so a kernel whose parameter type was renamed meets its successor; repeatable")
     args = ap.parse_args()
-    pk, pf, pe, pdup = load(args.parent_csrc, args.arch, args.llvm)
+    pk, pf, pe, pdup = load(args.parent_csrc, args.arch, args.llvm, renamer(args.rename))
     nk, nf, ne, ndup = load(args.new_csrc, args.arch, args.llvm)
     dm = demangle(sorted(set(pk) | set(nk) | set(pf) | set(nf)), args.llvm)
 
@@ -136,6 +160,8 @@ def main():
           % args.arch)
     print("name across the whole library and compared one by one (llvm-readelf --notes metadata, llvm-objdump -d instruction text and")
     print("encodings).")
+    if args.rename:
+        print("source names of the parent read as the new build spells them: " + ", ".join(r.replace("=", " -> ") for r in args.rename))
     print()
     print("kernels: parent %d, new %d" % (len(pk), len(nk)))
     for title, names, src in (("removed kernels", sorted(set(pk) - set(nk)), pk), ("added kernels", sorted(set(nk) - set(pk)), nk)):

@@ -25,7 +25,9 @@ parallel.  Everything on this side -- the steps, the family, the member choice, 
 There is no CPU fallback.  Device->host reads: encode 2 beyond building the level sets (the histograms with the root DC, the
 container); decode ONE at the end (the rANS status and the clamp flag; either raises PccError).  `parse_header` rejects a
 damaged stream on the host before any GPU work, and every buffer and launch is sized by the geometry set, never by the
-payload.
+payload.  All six headers of this file are one layout with optional parts: the table `KINDS` says per magic byte which parts a
+stream has and what its fields may hold, `_parse` (behind `parse_header` and `parse_lossless_header`) reads it and `_stream`
+writes it.
 
 `encode_attributes_lossless` / `decode_attributes_lossless` (second half of this file) are a separate coder
 over the same levels, rows, groups, family and container with a reversible arithmetic and their own stream:
@@ -38,6 +40,7 @@ over the same levels, rows, groups, family and container with a reversible arith
              | u32 length | rANS container            (coded against a reference cloud the decoder holds; no vector travels)
     wide:    u8 0xB7 | the 0xB6 layout byte for byte, search in 3 .. 7 (`encode_attributes_lossless(..., search=)`, as 0xB8 above)
 """
+import collections
 import ctypes as C
 import struct
 
@@ -60,6 +63,14 @@ HEADER = struct.Struct("<BIBBBBb")
 INTER_LOSSY_MAGIC = 0xB4   # inter frames, format version 1: coefficients predicted from a reference cloud
 WIDE_LOSSY_MAGIC = 0xB8    # the 0xB4 layout byte for byte with the block vectors searched over +-3 .. +-7 (the header's search byte)
 INTER_LOSSY_HEADER = struct.Struct("<BIBBBBbBBI")
+LOSSLESS_MAGIC = 0xB5      # the lossless coder (second half of this file), format version 1
+LOSSLESS_HEADER = struct.Struct("<BIBBB")
+F_COLOUR, F_PREDICT, F_STORED = 1, 2, 4
+SYMBOL_LIMIT = 1023        # the lossless decoder's clamp on a symbol; a valid one is within +-1020
+INTER_MAGIC = 0xB6         # inter frames, format version 1: the last level may be predicted from a reference cloud
+WIDE_MAGIC = 0xB7          # the 0xB6 layout byte for byte with the block vectors searched over +-3 .. +-7 (the header's search byte)
+INTER_HEADER = struct.Struct("<BIBBBBBI")
+INTER_MAX_DEPTH = 14       # (depth + 1) * 6 groups within the 90 of pcc_raht_hist
 STEP_TABLE = (256, 287, 323, 362, 406, 456)                 # Q8: 2^(k / 6), k = 0..5
 THETA = (55109, 46341, 38968, 32768)                        # Q16: 2^(-k / 4), k = 1..4
 N_TABLES, N_SLOTS, ESCAPE, MAX_ABS = 64, 128, 127, 63       # slots 0..126: the values -63..63; slot 127: the escape
@@ -176,89 +187,8 @@ def _container_span(data, at, symbols, name):
     return (at, at + nbytes), streams
 
 
-def parse_header(data, have_reference=True):
-    """{n, depth, channels, colour, qp, chroma_qp_offset, steps, dc (quantised root DC per channel), side (depth * 6 members),
-    payload=(begin, end) or None, streams, inter}.  Raises PccError on a bad magic byte, on channels, qp or depth out of range,
-    on a root DC or side byte out of range, on truncation, on trailing bytes and on a length that disagrees with the data --
-    before any GPU work.  An inter stream (0xB4, or 0xB8: the same layout searched over +-3 .. +-7) has inter=True, dc = the
-    quantised root DC residual, (depth + 1) * 6 side bytes
-    and block_log2, search, blocks, modes=(begin, end) besides; refused for it as well: a block size or search range other than
-    this build's, depth > 14, n < 2, a block count of 0 or above n, set padding bits of the mode bytes, and have_reference=False."""
-    inter = len(data) > 0 and data[0] in (INTER_LOSSY_MAGIC, WIDE_LOSSY_MAGIC)
-    name = "inter attribute stream" if inter else "attribute stream"
-    head = INTER_LOSSY_HEADER if inter else HEADER
-    if inter and not have_reference:
-        raise L.PccError(f"{name}: the stream is coded against a reference cloud and none was given")
-    if len(data) < head.size:
-        raise L.PccError(f"{name} truncated inside the header")
-    magic, n, depth, ch, flags, qp, cqo = HEADER.unpack_from(data, 0)
-    if magic not in (MAGIC, INTER_LOSSY_MAGIC, WIDE_LOSSY_MAGIC):
-        raise L.PccError(f"attribute stream: magic byte {magic:#x}, this build reads {MAGIC:#x}, {INTER_LOSSY_MAGIC:#x} and {WIDE_LOSSY_MAGIC:#x}")
-    if not 1 <= ch <= MAX_C:
-        raise L.PccError(f"attribute stream: {ch} channels outside 1..{MAX_C}")
-    if flags & ~1 or (flags & 1 and ch != 3):
-        raise L.PccError(f"attribute stream: flags {flags:#x} with {ch} channels")
-    if not QP_MIN <= qp <= QP_MAX:
-        raise L.PccError(f"attribute stream: qp {qp} outside {QP_MIN}..{QP_MAX}")
-    if n >= MAX_POINTS:
-        raise L.PccError(f"attribute stream: header claims {n} points, the limit is 2^26 - 1")
-    if (n == 0 and depth != 0) or (n > 0 and not 1 <= depth <= G.MAX_DEPTH) or n > 8 ** min(depth, 10):
-        raise L.PccError(f"attribute stream: header claims {n} points at depth {depth}")
-    hdr = {"inter": inter}
-    if inter:
-        block_log2, search, blocks = INTER_LOSSY_HEADER.unpack_from(data, 0)[7:]
-        _check_range(name, block_log2, search, magic == WIDE_LOSSY_MAGIC)
-        if n < 2:
-            raise L.PccError(f"{name}: header claims {n} points, an inter stream codes 2 .. 2^26 - 1")
-        if depth > INTER_MAX_DEPTH:
-            raise L.PccError(f"{name}: header claims depth {depth} (inter streams exist up to depth {INTER_MAX_DEPTH})")
-        if not 1 <= blocks <= n:
-            raise L.PccError(f"{name}: header claims {blocks} blocks for {n} points")
-        hdr.update(block_log2=block_log2, search=search, blocks=blocks)
-    groups = (depth + 1) * 6 if inter else depth * 6
-    steps = steps_for(qp, cqo, ch)
-    at, dc = head.size, []
-    for c in range(ch):
-        u, sh = 0, 0
-        while True:
-            if at >= len(data) or sh > 28:
-                raise L.PccError("attribute stream truncated inside the root DC")
-            b = data[at]
-            at += 1
-            u |= (b & 0x7F) << sh
-            sh += 7
-            if not b & 0x80:
-                break
-        q = (u >> 1) if not u & 1 else -((u + 1) >> 1)
-        if abs(q) * steps[c] > LIMIT:
-            raise L.PccError(f"attribute stream: root DC {q} of channel {c} is out of range")
-        dc.append(q)
-    if at + groups > len(data):
-        raise L.PccError(f"{name} truncated inside the side bytes")
-    side = list(data[at:at + groups])
-    at += groups
-    if side and max(side) >= N_TABLES:
-        raise L.PccError(f"{name}: side byte {max(side)} names no table (64 members)")
-    if inter:
-        mbytes = (hdr["blocks"] + 7) // 8
-        if at + mbytes > len(data):
-            raise L.PccError(f"{name} truncated inside the mode bytes")
-        if hdr["blocks"] % 8 and data[at + mbytes - 1] >> (hdr["blocks"] % 8):
-            raise L.PccError(f"{name}: padding bits of the mode bytes are set")
-        hdr["modes"] = (at, at + mbytes)
-        at += mbytes
-    hdr.update({"n": n, "depth": depth, "channels": ch, "colour": bool(flags & 1), "qp": qp, "chroma_qp_offset": cqo, "steps": steps,
-                "dc": dc, "side": side, "payload": None, "streams": 0})
-    if n > 1:
-        hdr["payload"], hdr["streams"] = _container_span(data, at, (n - 1) * ch, name)
-        at = hdr["payload"][1]
-    if at != len(data):
-        raise L.PccError(f"{name}: trailing bytes")
-    return hdr
-
-
 # ------------------------------------------------------------------------------------------------------------------------
-# device side
+# the stream headers, host side: one table of the six streams, one reader, one writer
 # ------------------------------------------------------------------------------------------------------------------------
 def _check_range(name, block_log2, search, wide):
     """The block size and search range of an inter header: G.SEARCH under the narrow magic bytes, G.WIDE_SEARCH under the wide ones."""
@@ -268,6 +198,170 @@ def _check_range(name, block_log2, search, wide):
         raise L.PccError(f"{name}: block_log2 {block_log2}, search {search}; this build reads {G.BLOCK_LOG2} and {reads}")
 
 
+def channel_ranges(channels, colour):
+    """[(lo, hi)] per channel of the lossless coder: 0..255, and -255..255 for Co and Cg of YCoCg-R."""
+    return [(0, 255)] + [(-255, 255) if colour else (0, 255)] * (channels - 1)
+
+
+def _dc_rule(hdr, c, q):
+    """What is wrong with the quantised root DC q of channel c (RAHT streams), or None: q * step stays within the decoder's clamp."""
+    return f"root DC {q} of channel {c} is out of range" if abs(q) * hdr["steps"][c] > LIMIT else None
+
+
+def _root_rule(hdr, c, q):
+    """What is wrong with the root value q of channel c (lossless streams), or None: inside the channel's range, 0 without a voxel."""
+    lo, hi = channel_ranges(hdr["channels"], hdr["colour"])[c]
+    return f"root value {q} of channel {c} outside {lo}..{hi}" if not lo <= q <= hi or (hdr["n"] == 0 and q) else None
+
+
+# One stream form: head (the struct of its fixed fields) and the names of those behind magic, n, depth, channels, flags; its name in
+# refusals; inter, wide; the legal flag bytes; the largest shift a root varint may reach and the rule its value obeys (`_dc_rule`
+# marks the RAHT streams: qp and steps in the header, "dc" in the result); the levels of side-byte groups beyond `depth`
+# ((depth + extra) * 6 side bytes).
+_Kind = collections.namedtuple("_Kind", "head more name inter wide flags shift rule extra")
+_QP, _BLOCKS = ("qp", "chroma_qp_offset"), ("block_log2", "search", "blocks")
+_CODED = (0, F_COLOUR, F_PREDICT, F_PREDICT | F_COLOUR)
+KINDS = {
+    MAGIC: _Kind(HEADER, _QP, "attribute stream", False, False, (0, F_COLOUR), 28, _dc_rule, 0),
+    INTER_LOSSY_MAGIC: _Kind(INTER_LOSSY_HEADER, _QP + _BLOCKS, "inter attribute stream", True, False, (0, F_COLOUR), 28, _dc_rule, 1),
+    WIDE_LOSSY_MAGIC: _Kind(INTER_LOSSY_HEADER, _QP + _BLOCKS, "inter attribute stream", True, True, (0, F_COLOUR), 28, _dc_rule, 1),
+    LOSSLESS_MAGIC: _Kind(LOSSLESS_HEADER, (), "lossless attribute stream", False, False, _CODED + (F_STORED,), 14, _root_rule, 0),
+    INTER_MAGIC: _Kind(INTER_HEADER, _BLOCKS, "inter lossless attribute stream", True, False, _CODED[2:], 14, _root_rule, 1),
+    WIDE_MAGIC: _Kind(INTER_HEADER, _BLOCKS, "inter lossless attribute stream", True, True, _CODED[2:], 14, _root_rule, 1),
+}
+
+
+def _unzigzag(data, at, max_shift):
+    """(value, the offset behind it) of the zig-zag LEB128 varint at `at`; (None, at) where the data end inside it or it runs
+    past max_shift."""
+    u, sh = 0, 0
+    while True:
+        if at >= len(data) or sh > max_shift:
+            return None, at
+        b = data[at]
+        at += 1
+        u |= (b & 0x7F) << sh
+        sh += 7
+        if not b & 0x80:
+            return ((u >> 1) if not u & 1 else -((u + 1) >> 1)), at
+
+
+def _parse(data, have_reference, family, reads):
+    """The one walk of a colour stream: fixed fields -> root varints -> side bytes -> mode bytes -> container -> trailing bytes, the
+    checks in the order the streams have always been refused in.  family: the magic bytes the calling entry point reads, its
+    intra stream first (which also names the refusal of anything else); reads: how the refusal of a foreign magic byte lists them."""
+    kind = KINDS[data[0] if len(data) and data[0] in family else family[0]]
+    name, lossy = kind.name, kind.rule is _dc_rule
+    if kind.inter and not have_reference:
+        raise L.PccError(f"{name}: the stream is coded against a reference cloud and none was given")
+    if len(data) < kind.head.size:
+        raise L.PccError(f"{name} truncated inside the header")
+    f = dict(zip(("magic", "n", "depth", "channels", "flags") + kind.more, kind.head.unpack_from(data, 0)))
+    n, depth, ch, flags = f["n"], f["depth"], f["channels"], f["flags"]
+    if f["magic"] not in family:
+        raise L.PccError(f"{name}: magic byte {f['magic']:#x}, this build reads {reads}")
+    if not 1 <= ch <= MAX_C:
+        raise L.PccError(f"{name}: {ch} channels outside 1..{MAX_C}")
+    if flags not in kind.flags or (flags & F_COLOUR and ch != 3):
+        raise L.PccError(f"{name}: flags {flags:#x} with {ch} channels")
+    if lossy and not QP_MIN <= f["qp"] <= QP_MAX:
+        raise L.PccError(f"{name}: qp {f['qp']} outside {QP_MIN}..{QP_MAX}")
+    if lossy or not kind.inter:                    # (0xB6 / 0xB7 word these two in their own way, below)
+        if n >= MAX_POINTS:
+            raise L.PccError(f"{name}: header claims {n} points, the limit is 2^26 - 1")
+        if (n == 0 and depth != 0) or (n > 0 and not 1 <= depth <= G.MAX_DEPTH) or n > 8 ** min(depth, 10):
+            raise L.PccError(f"{name}: header claims {n} points at depth {depth}")
+    hdr = {"n": n, "depth": depth, "channels": ch, "colour": bool(flags & F_COLOUR), "side": [], "payload": None, "streams": 0,
+           "inter": kind.inter}
+    if lossy:
+        hdr.update(qp=f["qp"], chroma_qp_offset=f["chroma_qp_offset"], steps=steps_for(f["qp"], f["chroma_qp_offset"], ch))
+    else:
+        hdr.update(predict=bool(flags & F_PREDICT), stored=bool(flags & F_STORED), raw=None)
+    if kind.inter:
+        _check_range(name, f["block_log2"], f["search"], kind.wide)
+        if not 2 <= n < MAX_POINTS:
+            raise L.PccError(f"{name}: header claims {n} points, an inter stream codes 2 .. 2^26 - 1")
+        if lossy and depth > INTER_MAX_DEPTH:
+            raise L.PccError(f"{name}: header claims depth {depth} (inter streams exist up to depth {INTER_MAX_DEPTH})")
+        if not lossy and (not 1 <= depth <= INTER_MAX_DEPTH or n > 8 ** min(depth, 10)):
+            raise L.PccError(f"{name}: header claims {n} points at depth {depth} (inter streams exist up to depth {INTER_MAX_DEPTH})")
+        if not 1 <= f["blocks"] <= n:
+            raise L.PccError(f"{name}: header claims {f['blocks']} blocks for {n} points")
+        hdr.update(block_log2=f["block_log2"], search=f["search"], blocks=f["blocks"])
+    at = kind.head.size
+    key, word = ("dc", "root DC") if lossy else ("root", "root values")
+    hdr[key] = []
+    if not lossy and hdr["stored"]:                # the stored form of 0xB5: the raw levels and nothing else
+        if len(data) != at + n * ch:
+            raise L.PccError(f"{name}: a stored body of {len(data) - at} bytes for {n} x {ch} levels")
+        hdr["raw"] = (at, at + n * ch)
+        return hdr
+    for c in range(ch):
+        q, at = _unzigzag(data, at, kind.shift)
+        if q is None:
+            raise L.PccError(f"{name} truncated inside the {word}")
+        why = kind.rule(hdr, c, q)
+        if why:
+            raise L.PccError(f"{name}: {why}")
+        hdr[key].append(q)
+    groups = (depth + kind.extra) * 6
+    if at + groups > len(data):
+        raise L.PccError(f"{name} truncated inside the side bytes")
+    hdr["side"] = list(data[at:at + groups])
+    at += groups
+    if hdr["side"] and max(hdr["side"]) >= N_TABLES:
+        raise L.PccError(f"{name}: side byte {max(hdr['side'])} names no table (64 members)")
+    if kind.inter:
+        mbytes = (hdr["blocks"] + 7) // 8
+        if at + mbytes > len(data):
+            raise L.PccError(f"{name} truncated inside the mode bytes")
+        if hdr["blocks"] % 8 and data[at + mbytes - 1] >> (hdr["blocks"] % 8):
+            raise L.PccError(f"{name}: padding bits of the mode bytes are set")
+        hdr["modes"] = (at, at + mbytes)
+        at += mbytes
+    if n > 1:                                           # no voxel, or one: no row, no length and no container
+        hdr["payload"], hdr["streams"] = _container_span(data, at, (n - 1) * ch, name)
+        at = hdr["payload"][1]
+    if at != len(data):
+        raise L.PccError(f"{name}: trailing bytes")
+    return hdr
+
+
+def parse_header(data, have_reference=True):
+    """{n, depth, channels, colour, qp, chroma_qp_offset, steps, dc (quantised root DC per channel), side (depth * 6 members),
+    payload=(begin, end) or None, streams, inter}.  Raises PccError on a bad magic byte, on channels, qp or depth out of range,
+    on a root DC or side byte out of range, on truncation, on trailing bytes and on a length that disagrees with the data --
+    before any GPU work.  An inter stream (0xB4, or 0xB8: the same layout searched over +-3 .. +-7) has inter=True, dc = the
+    quantised root DC residual, (depth + 1) * 6 side bytes and block_log2, search, blocks, modes=(begin, end) besides; refused
+    for it as well: a block size or search range other than this build's, depth > 14, n < 2, a block count of 0 or above n, set
+    padding bits of the mode bytes, and have_reference=False.  A 0xB5 .. 0xB7 stream is refused by its magic byte."""
+    return _parse(data, have_reference, (MAGIC, INTER_LOSSY_MAGIC, WIDE_LOSSY_MAGIC), f"{MAGIC:#x}, {INTER_LOSSY_MAGIC:#x} and {WIDE_LOSSY_MAGIC:#x}")
+
+
+def parse_lossless_header(data, have_reference=True):
+    """{n, depth, channels, colour, predict, stored, root (per channel), side (depth * 6 members), payload=(begin, end) or None,
+    streams, raw=(begin, end) or None, inter}.  Raises PccError on a bad magic byte, an unknown flag, the colour flag without
+    three channels, channels, n or depth out of range, a root outside its channel's range, a side byte that names no table,
+    truncation, trailing bytes, a container length that disagrees with the data and a stored body of the wrong size --
+    before any GPU work.  An inter stream (0xB6, or 0xB7: the same layout searched over +-3 .. +-7) has inter=True,
+    (depth + 1) * 6 side bytes and block_log2, search, blocks, modes=(begin, end) besides; refused for it as well: a block size
+    or search range other than this build's, depth > 14, n < 2, a block count of 0 or above n, set padding bits of the mode
+    bytes, and have_reference=False.  A 0xB3, 0xB4 or 0xB8 stream is refused by its magic byte."""
+    return _parse(data, have_reference, (LOSSLESS_MAGIC, INTER_MAGIC, WIDE_MAGIC), f"{LOSSLESS_MAGIC:#x}")
+
+
+def _stream(magic, fields, roots=(), side=(), modes=None, body=b""):
+    """The bytes of a stream from its parts: the fixed fields behind the magic byte, the root values (zig-zag varints), the side
+    bytes, one int per block (the mode bytes of an inter stream; None: none), and `u32 length | rANS container` or raw levels."""
+    out = KINDS[magic].head.pack(magic, *fields) + b"".join(_zigzag(int(q)) for q in roots) + bytes(side)
+    if modes is not None:
+        out += np.packbits(np.asarray(modes).astype(bool), bitorder="little").tobytes()
+    return out + body
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# device side
+# ------------------------------------------------------------------------------------------------------------------------
 def _colour_search(search, what):
     """The search range of a colour encoder: an int in 2 .. 7 (None: 2).  "auto" belongs to the geometry coder -- the colour follows
     the range the geometry stream ended with (`geometry.stream_search`)."""
@@ -289,6 +383,14 @@ def _depth_of(cs):
 def _level_args(node, child):
     """The eight leading arguments of the per-level entry points: the nodes, their children, the children's grid index."""
     return (L.ptr(node.keys), node.n, node.ts, L.ptr(child.keys), child.n, *S.grid_args(child.grid() if S.USE_GRID else None))
+
+
+def _node_level_args(node, child, root):
+    """The eleven leading arguments of the entry points that also probe the node level: the nodes with their own grid index
+    (the root's single node is searched), their children with theirs."""
+    use = S.USE_GRID and not root
+    return (L.ptr(node.keys), node.n, node.ts, *S.grid_args(node.grid() if use else None), L.ptr(child.keys), child.n,
+            *S.grid_args(child.grid() if S.USE_GRID else None))
 
 
 def _plan(sets, depth, dev):
@@ -342,6 +444,27 @@ def _attribute_rows(cloud, attrs, what):
     return cloud, attrs.contiguous()
 
 
+def _reference_rows(reference, reference_attrs, channels, predict, what):
+    """(set or None for an empty reference, its uint8 [M, C] levels, the permutation that brings them into the set's order or
+    None) of the reference cloud of an inter stream: an [M, 6] cloud, or a pitch-1 set / [M, >= 3] rows with `reference_attrs`.
+    Refused: the input forms `encode_attributes` refuses, rows that repeat a voxel (their colours would be ambiguous), another
+    channel count than the stream's, and a stream without prediction."""
+    who = f"{what} (reference)"
+    if not predict:
+        raise L.PccError(f"{what}: a reference needs the prediction (predict=True)")
+    cloud, levels = _attribute_rows(reference, reference_attrs, who)
+    if levels.shape[1] != channels:
+        raise L.PccError(f"{who}: {levels.shape[1]} channels, the cloud has {channels}")
+    if (cloud.n if isinstance(cloud, S.CoordSet) else cloud.shape[0]) == 0:
+        return None, None, None
+    rs, perm, keep = G.canonical_rows(cloud, who)
+    if keep is not None:
+        raise L.PccError(f"{who}: {levels.shape[0] - rs.n} rows repeat a voxel; merge them first (voxelize.voxel_grid)")
+    if levels.device != rs.device:
+        raise L.PccError(f"{who}: points and attrs are on different devices")
+    return rs, levels, perm
+
+
 def _encoder_input(what, cloud, attrs, reference, reference_attrs, mode, predict, chroma_qp_offset=0):
     """The opening of both encoders: (canonical set, uint8 levels, their permutation, reference rows or None, depth, whether an
     inter stream is coded).  Refusals in this order, those that need no launch first: the mode, the cloud's rows, the chroma
@@ -373,6 +496,46 @@ def _encoder_input(what, cloud, attrs, reference, reference_attrs, mode, predict
     return cs, levels, perm, ref, depth, inter
 
 
+def _inter_state(cs, sets, origin, depth, ref, channels, colour, d_flag, prepare="pcc_lift_prepare", search=G.SEARCH):
+    """What both sides of an inter stream (0xB6 and 0xB4) recompute from the geometry and the reference: (the block arguments of
+    the pcc_lift_inter_* / pcc_raht_inter_* entry points, the block count, int32 match row per voxel, int32 [M, C] prepared
+    reference values or None, M).  `geometry.motion_vectors` gives the vectors; the tensors the arguments point into live in
+    `sets` and the result.  prepare: the entry point that turns the reference's levels into the coder's values (plain or
+    YCoCg-R levels for the lossless coder, Q8 with BT.709 for the RAHT coder: "pcc_raht_prepare").  search above 2: the wide search,
+    whose vectors are packed displacements (`pcc_lift_inter_match_wide`)."""
+    rs, levels, perm = ref
+    dev = cs.device
+    blocks, bl, _, vec = G.motion_vectors(cs, rs, origin, depth, sets, search=search)
+    grid = blocks.grid() if (depth > bl and S.USE_GRID) else None         # the root's single node is searched
+    bargs = (L.ptr(blocks.keys), blocks.n, *S.grid_args(grid), bl)
+    match = torch.empty(cs.n, dtype=torch.int32, device=dev)
+    L.call("pcc_lift_inter_match_wide" if search > G.MAX_SEARCH else "pcc_lift_inter_match", L.ptr(sets[depth].keys), cs.n, *bargs, L.ptr(vec),
+           search, *G.ref_args(rs), *origin, L.ptr(match), d_flag, L.stream())
+    if rs is None:
+        return bargs, blocks.n, match, None, 0, (vec, grid)
+    if levels.device != dev:
+        raise L.PccError("the reference is on another device than the cloud")
+    tv = torch.empty((rs.n, channels), dtype=torch.int32, device=dev)
+    L.call(prepare, L.ptr(levels), L.ptr(perm), rs.n, channels, int(colour), L.ptr(tv), L.stream())
+    return bargs, blocks.n, match, tv, rs.n, (vec, grid)
+
+
+def _rans_body(coef, idx, symbols, segment_symbols, dev, what, ph=None):
+    """`u32 length | rANS container` of the symbol vector; one device->host read (size + container).  ph: `geometry.Phases`
+    that get the mark "index_rans" behind the coder's launches."""
+    plan = R.Plan(symbols, 1, 1, segments_for(symbols, segment_symbols))
+    cap = R.align8(plan.capacity)
+    blob = torch.zeros(8 + cap, dtype=torch.uint8, device=dev)
+    R.encode(_tables(dev), plan, coef, idx, blob.data_ptr() + 8, blob.data_ptr())
+    if ph is not None:
+        ph.mark("index_rans")
+    host = blob.cpu().numpy()
+    nb = int(host[:8].view(np.int64)[0])
+    if not 0 < nb <= cap:
+        raise L.PccError(f"{what}: the coder produced {nb} bytes for a capacity of {cap}")
+    return struct.pack("<I", nb) + host[8:8 + nb].tobytes()
+
+
 def _intra_tail(what, sets, masks, offs, checks, coef, v_root, depth, ch, rows, segment_symbols, dev, ph):
     """(root values as they are, side bytes, `u32 length | rANS container`) of an intra stream (0xB3, 0xB5) from the coded rows
     and the root's values: the groups, their histograms, the member choice (one read), the member index and the coder (one
@@ -395,6 +558,91 @@ def _intra_tail(what, sets, masks, offs, checks, coef, v_root, depth, ch, rows, 
         _fill_index(masks, offs, sets, depth, ch, d_side, idx, rows)
         body = _rans_body(coef, idx, rows * ch, segment_symbols, dev, what, ph)    # one read: size + container
     return root, side, body
+
+
+def _inter_index(masks, offs, sets, depth, first, ch, bargs, d_mode, d_side, idx, coef_p, coef, rows, d_flag):
+    """idx of all rows of an inter RAHT stream: the levels above the blocks as in the intra stream, the levels inside them by
+    their block's mode.  d_side None: groups; coef given (encoder): the intra symbols of mode-0 blocks are copied into coef_p."""
+    _fill_index(masks, offs, sets, first, ch, d_side, idx, rows)
+    for l in range(first, depth):
+        L.call("pcc_raht_inter_select", L.ptr(sets[l].keys), L.ptr(masks[l]), L.ptr(offs[l]), sets[l].n, l, depth, ch, *bargs, L.ptr(d_mode),
+               L.ptr(d_side), L.ptr(idx), L.ptr(coef_p), L.ptr(coef), sets[l].n - 1, rows, d_flag, L.stream())
+
+
+def _encode_inter_lossy(what, cs, levels, perm, ref, qp, cqo, colour, mode, segment_symbols, timings, search=G.SEARCH):
+    """The inter half of `encode_attributes` (n >= 2, depth <= 14): the 0xB4 stream (0xB8 when `search` is above 2) and, for
+    mode "auto", the 0xB3 stream from
+    the same forward pass; the shorter is returned, intra on a tie.  Device->host reads beyond the level sets: 2 for the inter
+    stream (modes, root DCs and histograms; the container), 2 more for the intra stream of "auto"."""
+    n, ch, dev = cs.n, levels.shape[1], cs.device
+    steps = steps_for(qp, cqo, ch)
+    h_steps = (C.c_int32 * ch)(*steps)
+    origin, depth = tuple(cs.bounds.lo), _depth_of(cs)
+    rows = n - 1
+    with torch.cuda.device(dev):
+        ph = G.Phases(timings is not None)
+        sets = G.level_sets(cs, origin, depth)
+        ph.mark("start")
+        d_flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        bargs, nb, match, tv, nr, _keep = _inter_state(cs, sets, origin, depth, ref, ch, colour, L.ptr(d_flag), "pcc_raht_prepare", search)
+        first = depth - bargs[-1]
+        ph.mark("motion_match_ms")
+        values = torch.empty((n, ch), dtype=torch.int32, device=dev)
+        L.call("pcc_raht_prepare", L.ptr(levels), L.ptr(perm), n, ch, int(colour), L.ptr(values), L.stream())
+        masks, offs, checks = _plan(sets, depth, dev)
+        fill_sums = torch.empty((nb, ch + 1), dtype=torch.int32, device=dev)
+        pred = torch.empty((n, ch), dtype=torch.int32, device=dev)
+        L.call("pcc_raht_inter_fill", L.ptr(sets[depth].keys), n, *bargs, L.ptr(match), L.ptr(tv), nr, ch, None, L.ptr(fill_sums), L.ptr(pred),
+               L.ptr(d_flag), L.stream())
+        ph.mark("prepare_plan_fill_ms")
+        coef = torch.zeros((rows, ch), dtype=torch.int32, device=dev)      # the intra symbols of every row
+        coef_p = torch.zeros((rows, ch), dtype=torch.int32, device=dev)    # the inter stream's symbols
+        sums = torch.zeros((nb, 2), dtype=torch.int32, device=dev)
+        d_mode = torch.empty(nb, dtype=torch.int32, device=dev)
+        w_child, v_child, p_child = None, values, pred
+        for l in range(depth - 1, -1, -1):                                  # the levels above the blocks come after the decision
+            w = torch.empty(sets[l].n, dtype=torch.int32, device=dev)
+            v = torch.empty((sets[l].n, ch), dtype=torch.int32, device=dev)
+            p = torch.empty((sets[l].n, ch), dtype=torch.int32, device=dev)
+            L.call("pcc_raht_inter_forward", *_level_args(sets[l], sets[l + 1]), *bargs, L.ptr(offs[l]), L.ptr(w_child), L.ptr(v_child),
+                   L.ptr(p_child), ch, h_steps, L.ptr(w), L.ptr(v), L.ptr(p), L.ptr(coef), L.ptr(coef_p), sets[l].n - 1, rows,
+                   L.ptr(sums) if l >= first else None, L.ptr(d_flag), L.stream())
+            if l == first:
+                L.call("pcc_raht_inter_modes", L.ptr(sums), L.ptr(fill_sums), nb, ch, L.ptr(d_mode), L.ptr(p), L.stream())
+            w_child, v_child, p_child = w, v, p
+        ph.mark("forward_modes_ms")
+        groups = (depth + 1) * 6
+        idx = torch.empty(rows * ch, dtype=torch.int32, device=dev)
+        hist = torch.empty(groups * N_SLOTS, dtype=torch.int32, device=dev)
+        _inter_index(masks, offs, sets, depth, first, ch, bargs, d_mode, None, idx, coef_p, coef, rows, L.ptr(d_flag))
+        L.call("pcc_raht_hist", L.ptr(coef_p), L.ptr(idx), rows * ch, groups, L.ptr(hist), L.stream())
+        back = torch.cat([v_child.reshape(-1), p_child.reshape(-1), checks.reshape(-1), d_flag, d_mode, hist]).cpu().numpy()      # one read
+        at = 2 * ch + 4 * depth
+        _check_plan(back[2 * ch:at], sets, what)
+        if back[at] != 0:
+            raise L.PccError(f"{what}: the blocks, vectors or matches of the cloud are inconsistent")
+        root = [quantise(int(back[c]) - int(back[ch + c]), steps[c]) for c in range(ch)]
+        modes = back[at + 1:at + 1 + nb]
+        side = choose_members(back[at + 1 + nb:])
+        ph.mark("select_hist_choose_ms")
+        d_side = torch.tensor(side, dtype=torch.int32, device=dev)
+        _inter_index(masks, offs, sets, depth, first, ch, bargs, d_mode, d_side, idx, None, None, rows, L.ptr(d_flag))
+        body = _rans_body(coef_p, idx, rows * ch, segment_symbols, dev, what)          # one read: size + container
+        ph.mark("index_rans_ms")
+        out = _stream(WIDE_LOSSY_MAGIC if search > G.MAX_SEARCH else INTER_LOSSY_MAGIC, (n, depth, ch, int(colour), qp, cqo, G.BLOCK_LOG2, search, nb),
+                      root, side, modes, body)
+        intra = None
+        if mode == "auto":
+            dc, side0, body0 = _intra_tail(what, sets, masks, offs, checks, coef, v_child, depth, ch, rows, segment_symbols, dev, G.Phases(False))
+            intra = _stream(MAGIC, (n, depth, ch, int(colour), qp, cqo), [quantise(q, st) for q, st in zip(dc, steps)], side0, None, body0)
+            ph.mark("intra_stream_ms")
+        if timings is not None:
+            torch.cuda.synchronize(dev)
+            timings["inter_stages_ms"] = ph.report()
+            timings["inter_bytes"], timings["intra_bytes"] = len(out), (len(intra) if intra is not None else None)
+            timings["mode1_blocks"], timings["blocks"] = int(modes.sum()), nb
+            timings["host_reads_by_construction"] = 4 if mode == "auto" else 2   # beyond those of building the level sets
+    return out if intra is None or len(out) < len(intra) else intra
 
 
 @torch.no_grad()
@@ -420,7 +668,7 @@ def encode_attributes(cloud, qp, chroma_qp_offset=-2, colour=True, attrs=None, s
     n, ch, dev = cs.n, levels.shape[1], cs.device
     colour = bool(colour) and ch == 3
     if n == 0:
-        return HEADER.pack(MAGIC, 0, 0, ch, int(colour), qp, cqo) + b"\x00" * ch
+        return _stream(MAGIC, (0, 0, ch, int(colour), qp, cqo), [0] * ch)
     if inter:
         return _encode_inter_lossy(what, cs, levels, perm, ref, qp, cqo, colour, mode, segment_symbols, timings, search)
     steps = steps_for(qp, cqo, ch)
@@ -449,11 +697,62 @@ def encode_attributes(cloud, qp, chroma_qp_offset=-2, colour=True, attrs=None, s
             timings["stages_ms"] = ph.report()
             timings["stages_ms"].setdefault("index_rans", 0.0)             # (a single voxel has no rows to code)
             timings["host_reads_by_construction"] = 2 if rows else 1       # beyond those of building the level sets
-    out = bytearray(HEADER.pack(MAGIC, n, depth, ch, int(colour), qp, cqo))
-    for q, step in zip(root, steps):
-        out += _zigzag(quantise(q, step))
-    out += bytes(side)
-    return bytes(out + body)
+    return _stream(MAGIC, (n, depth, ch, int(colour), qp, cqo), [quantise(q, st) for q, st in zip(root, steps)], side, None, body)
+
+
+def _decoder_input(what, hdr, geometry, device, reference, reference_attrs):
+    """(canonical set of the geometry on the GPU, the reference rows of an inter stream or None) of both decoders; refuses a
+    reference an inter stream cannot use, a geometry off the GPU and one whose n or depth are not the header's."""
+    ref = _reference_rows(reference, reference_attrs, hdr["channels"], True, what) if hdr["inter"] else None
+    if torch.is_tensor(geometry) and device is not None:
+        geometry = geometry.to(device)
+    cs = G.canonical_rows(geometry, what)[0]
+    if cs.device.type != "cuda" or (device is not None and torch.device(device).type != "cuda"):
+        raise L.PccError(f"{what} runs on a GPU (no CPU fallback)")
+    n, depth = hdr["n"], hdr["depth"]
+    if cs.n != n or (n and _depth_of(cs) != depth):
+        raise L.PccError(f"{what}: the stream codes {n} points at depth {depth}, the geometry has {cs.n} at depth "
+                         f"{_depth_of(cs) if cs.n else 0}")
+    return cs, ref
+
+
+def _decoder_plan(cs, depth, ch, ph):
+    """What both decoders build from the geometry alone: (level sets, masks, offsets and checks of `_plan`, int32 weights per
+    level, the status words rANS status | clamp flag, the zeroed coefficient rows)."""
+    dev = cs.device
+    ph.mark("start")
+    sets = G.level_sets(cs, tuple(cs.bounds.lo), depth)
+    ph.mark("level_sets_ms")
+    masks, offs, checks = _plan(sets, depth, dev)
+    weights = [None] * (depth + 1)                                          # the voxels weigh 1: no array
+    for l in range(depth - 1, -1, -1):
+        weights[l] = torch.empty(sets[l].n, dtype=torch.int32, device=dev)
+        L.call("pcc_raht_weights", *_level_args(sets[l], sets[l + 1]), L.ptr(weights[l + 1]), L.ptr(weights[l]), L.stream())
+    status = torch.zeros(2, dtype=torch.int32, device=dev)
+    coef = torch.zeros(max(cs.n - 1, 1) * ch, dtype=torch.int32, device=dev)
+    ph.mark("plan_weights_ms")
+    return sets, masks, offs, checks, weights, status, coef
+
+
+def _block_modes(data, hdr, blocks, dev):
+    """int32 mode per block of an inter stream, from the header's mode bytes."""
+    m0, m1 = hdr["modes"]
+    bits = np.unpackbits(np.frombuffer(data, np.uint8, m1 - m0, m0), bitorder="little")[:blocks]
+    return torch.from_numpy(bits.astype(np.int32)).to(dev)
+
+
+def _decoder_read(what, name, left, status, checks, sets, ph, timings):
+    """The decode's one device->host read and what it refuses: a geometry that does not expand level by level, a malformed
+    container, a value that `left` its range.  name: the stream's name in the refusals."""
+    back = torch.cat([status, checks.reshape(-1)]).cpu().numpy()
+    if timings is not None:
+        torch.cuda.synchronize(status.device)
+        timings["stages_ms"] = ph.report()
+    _check_plan(back[2:], sets, what)
+    if back[0] != 0:
+        raise L.PccError(f"{name}: malformed rANS container (status {int(back[0])})")
+    if back[1] != 0:
+        raise L.PccError(f"{name}: {left}")
 
 
 @torch.no_grad()
@@ -532,350 +831,9 @@ def decode_attributes(data, geometry, device=None, reference=None, reference_att
     return out
 
 
-def _decoder_input(what, hdr, geometry, device, reference, reference_attrs):
-    """(canonical set of the geometry on the GPU, the reference rows of an inter stream or None) of both decoders; refuses a
-    reference an inter stream cannot use, a geometry off the GPU and one whose n or depth are not the header's."""
-    ref = _reference_rows(reference, reference_attrs, hdr["channels"], True, what) if hdr["inter"] else None
-    if torch.is_tensor(geometry) and device is not None:
-        geometry = geometry.to(device)
-    cs = G.canonical_rows(geometry, what)[0]
-    if cs.device.type != "cuda" or (device is not None and torch.device(device).type != "cuda"):
-        raise L.PccError(f"{what} runs on a GPU (no CPU fallback)")
-    n, depth = hdr["n"], hdr["depth"]
-    if cs.n != n or (n and _depth_of(cs) != depth):
-        raise L.PccError(f"{what}: the stream codes {n} points at depth {depth}, the geometry has {cs.n} at depth "
-                         f"{_depth_of(cs) if cs.n else 0}")
-    return cs, ref
-
-
-def _decoder_plan(cs, depth, ch, ph):
-    """What both decoders build from the geometry alone: (level sets, masks, offsets and checks of `_plan`, int32 weights per
-    level, the status words rANS status | clamp flag, the zeroed coefficient rows)."""
-    dev = cs.device
-    ph.mark("start")
-    sets = G.level_sets(cs, tuple(cs.bounds.lo), depth)
-    ph.mark("level_sets_ms")
-    masks, offs, checks = _plan(sets, depth, dev)
-    weights = [None] * (depth + 1)                                          # the voxels weigh 1: no array
-    for l in range(depth - 1, -1, -1):
-        weights[l] = torch.empty(sets[l].n, dtype=torch.int32, device=dev)
-        L.call("pcc_raht_weights", *_level_args(sets[l], sets[l + 1]), L.ptr(weights[l + 1]), L.ptr(weights[l]), L.stream())
-    status = torch.zeros(2, dtype=torch.int32, device=dev)
-    coef = torch.zeros(max(cs.n - 1, 1) * ch, dtype=torch.int32, device=dev)
-    ph.mark("plan_weights_ms")
-    return sets, masks, offs, checks, weights, status, coef
-
-
-def _block_modes(data, hdr, blocks, dev):
-    """int32 mode per block of an inter stream, from the header's mode bytes."""
-    m0, m1 = hdr["modes"]
-    bits = np.unpackbits(np.frombuffer(data, np.uint8, m1 - m0, m0), bitorder="little")[:blocks]
-    return torch.from_numpy(bits.astype(np.int32)).to(dev)
-
-
-def _decoder_read(what, name, left, status, checks, sets, ph, timings):
-    """The decode's one device->host read and what it refuses: a geometry that does not expand level by level, a malformed
-    container, a value that `left` its range.  name: the stream's name in the refusals."""
-    back = torch.cat([status, checks.reshape(-1)]).cpu().numpy()
-    if timings is not None:
-        torch.cuda.synchronize(status.device)
-        timings["stages_ms"] = ph.report()
-    _check_plan(back[2:], sets, what)
-    if back[0] != 0:
-        raise L.PccError(f"{name}: malformed rANS container (status {int(back[0])})")
-    if back[1] != 0:
-        raise L.PccError(f"{name}: {left}")
-
-
 # ------------------------------------------------------------------------------------------------------------------------
 # the lossless coder (DESIGN.md section 7i): the same levels, rows, groups, family and container; a reversible arithmetic
 # ------------------------------------------------------------------------------------------------------------------------
-LOSSLESS_MAGIC = 0xB5      # format version 1
-LOSSLESS_HEADER = struct.Struct("<BIBBB")
-F_COLOUR, F_PREDICT, F_STORED = 1, 2, 4
-SYMBOL_LIMIT = 1023        # the decoder's clamp on a symbol; a valid one is within +-1020
-INTER_MAGIC = 0xB6         # inter frames, format version 1: the last level may be predicted from a reference cloud
-WIDE_MAGIC = 0xB7          # the 0xB6 layout byte for byte with the block vectors searched over +-3 .. +-7 (the header's search byte)
-INTER_HEADER = struct.Struct("<BIBBBBBI")
-INTER_MAX_DEPTH = 14       # (depth + 1) * 6 groups within the 90 of pcc_raht_hist
-
-
-def channel_ranges(channels, colour):
-    """[(lo, hi)] per channel: 0..255, and -255..255 for Co and Cg of YCoCg-R."""
-    return [(0, 255)] + [(-255, 255) if colour else (0, 255)] * (channels - 1)
-
-
-def _root_values(data, at, n, channels, colour, name):
-    """(root value per channel, the offset behind them) of the zig-zag varints at `at`, each inside its channel's range."""
-    root = []
-    for c, (lo, hi) in enumerate(channel_ranges(channels, colour)):
-        u, sh = 0, 0
-        while True:
-            if at >= len(data) or sh > 14:
-                raise L.PccError(f"{name} truncated inside the root values")
-            b = data[at]
-            at += 1
-            u |= (b & 0x7F) << sh
-            sh += 7
-            if not b & 0x80:
-                break
-        q = (u >> 1) if not u & 1 else -((u + 1) >> 1)
-        if not lo <= q <= hi or (n == 0 and q):
-            raise L.PccError(f"{name}: root value {q} of channel {c} outside {lo}..{hi}")
-        root.append(q)
-    return root, at
-
-
-def _parse_inter_header(data, have_reference):
-    """The 0xB6 / 0xB7 half of `parse_lossless_header`."""
-    name = "inter lossless attribute stream"
-    if not have_reference:
-        raise L.PccError(f"{name}: the stream is coded against a reference cloud and none was given")
-    if len(data) < INTER_HEADER.size:
-        raise L.PccError(f"{name} truncated inside the header")
-    magic, n, depth, ch, flags, block_log2, search, blocks = INTER_HEADER.unpack_from(data, 0)
-    if not 1 <= ch <= MAX_C:
-        raise L.PccError(f"{name}: {ch} channels outside 1..{MAX_C}")
-    if flags not in (F_PREDICT, F_PREDICT | F_COLOUR) or (flags & F_COLOUR and ch != 3):
-        raise L.PccError(f"{name}: flags {flags:#x} with {ch} channels")
-    _check_range(name, block_log2, search, magic == WIDE_MAGIC)
-    if not 2 <= n < MAX_POINTS:
-        raise L.PccError(f"{name}: header claims {n} points, an inter stream codes 2 .. 2^26 - 1")
-    if not 1 <= depth <= INTER_MAX_DEPTH or n > 8 ** min(depth, 10):
-        raise L.PccError(f"{name}: header claims {n} points at depth {depth} (inter streams exist up to depth {INTER_MAX_DEPTH})")
-    if not 1 <= blocks <= n:
-        raise L.PccError(f"{name}: header claims {blocks} blocks for {n} points")
-    colour = bool(flags & F_COLOUR)
-    root, at = _root_values(data, INTER_HEADER.size, n, ch, colour, name)
-    groups = (depth + 1) * 6
-    if at + groups > len(data):
-        raise L.PccError(f"{name} truncated inside the side bytes")
-    side = list(data[at:at + groups])
-    at += groups
-    if max(side) >= N_TABLES:
-        raise L.PccError(f"{name}: side byte {max(side)} names no table (64 members)")
-    mbytes = (blocks + 7) // 8
-    if at + mbytes > len(data):
-        raise L.PccError(f"{name} truncated inside the mode bytes")
-    if blocks % 8 and data[at + mbytes - 1] >> (blocks % 8):
-        raise L.PccError(f"{name}: padding bits of the mode bytes are set")
-    hdr = {"n": n, "depth": depth, "channels": ch, "colour": colour, "predict": True, "stored": False, "root": root, "side": side,
-           "payload": None, "streams": 0, "raw": None, "inter": True, "block_log2": block_log2, "search": search, "blocks": blocks,
-           "modes": (at, at + mbytes)}
-    hdr["payload"], hdr["streams"] = _container_span(data, at + mbytes, (n - 1) * ch, name)
-    if hdr["payload"][1] != len(data):
-        raise L.PccError(f"{name}: trailing bytes")
-    return hdr
-
-
-def parse_lossless_header(data, have_reference=True):
-    """{n, depth, channels, colour, predict, stored, root (per channel), side (depth * 6 members), payload=(begin, end) or None,
-    streams, raw=(begin, end) or None, inter}.  Raises PccError on a bad magic byte, an unknown flag, the colour flag without
-    three channels, channels, n or depth out of range, a root outside its channel's range, a side byte that names no table,
-    truncation, trailing bytes, a container length that disagrees with the data and a stored body of the wrong size --
-    before any GPU work.  An inter stream (0xB6, or 0xB7: the same layout searched over +-3 .. +-7) has inter=True,
-    (depth + 1) * 6 side bytes and block_log2, search, blocks,
-    modes=(begin, end) besides; refused for it as well: a block size or search range other than this build's, depth > 14,
-    n < 2, a block count of 0 or above n, set padding bits of the mode bytes, and have_reference=False."""
-    if len(data) and data[0] in (INTER_MAGIC, WIDE_MAGIC):
-        return _parse_inter_header(data, have_reference)
-    if len(data) < LOSSLESS_HEADER.size:
-        raise L.PccError("lossless attribute stream truncated inside the header")
-    magic, n, depth, ch, flags = LOSSLESS_HEADER.unpack_from(data, 0)
-    if magic != LOSSLESS_MAGIC:
-        raise L.PccError(f"lossless attribute stream: magic byte {magic:#x}, this build reads {LOSSLESS_MAGIC:#x}")
-    if not 1 <= ch <= MAX_C:
-        raise L.PccError(f"lossless attribute stream: {ch} channels outside 1..{MAX_C}")
-    if flags & ~7 or (flags & F_COLOUR and ch != 3) or (flags & F_STORED and flags != F_STORED):
-        raise L.PccError(f"lossless attribute stream: flags {flags:#x} with {ch} channels")
-    if n >= MAX_POINTS:
-        raise L.PccError(f"lossless attribute stream: header claims {n} points, the limit is 2^26 - 1")
-    if (n == 0 and depth != 0) or (n > 0 and not 1 <= depth <= G.MAX_DEPTH) or n > 8 ** min(depth, 10):
-        raise L.PccError(f"lossless attribute stream: header claims {n} points at depth {depth}")
-    colour = bool(flags & F_COLOUR)
-    hdr = {"n": n, "depth": depth, "channels": ch, "colour": colour, "predict": bool(flags & F_PREDICT), "stored": bool(flags & F_STORED),
-           "root": [], "side": [], "payload": None, "streams": 0, "raw": None, "inter": False}
-    at = LOSSLESS_HEADER.size
-    if hdr["stored"]:
-        if len(data) != at + n * ch:
-            raise L.PccError(f"lossless attribute stream: a stored body of {len(data) - at} bytes for {n} x {ch} levels")
-        hdr["raw"] = (at, at + n * ch)
-        return hdr
-    hdr["root"], at = _root_values(data, at, n, ch, colour, "lossless attribute stream")
-    if at + depth * 6 > len(data):
-        raise L.PccError("lossless attribute stream truncated inside the side bytes")
-    hdr["side"] = list(data[at:at + depth * 6])
-    at += depth * 6
-    if hdr["side"] and max(hdr["side"]) >= N_TABLES:
-        raise L.PccError(f"lossless attribute stream: side byte {max(hdr['side'])} names no table (64 members)")
-    if n > 1:
-        hdr["payload"], hdr["streams"] = _container_span(data, at, (n - 1) * ch, "lossless attribute stream")
-        at = hdr["payload"][1]
-    if at != len(data):
-        raise L.PccError("lossless attribute stream: trailing bytes")
-    return hdr
-
-
-def _node_level_args(node, child, root):
-    """The eleven leading arguments of the entry points that also probe the node level: the nodes with their own grid index
-    (the root's single node is searched), their children with theirs."""
-    use = S.USE_GRID and not root
-    return (L.ptr(node.keys), node.n, node.ts, *S.grid_args(node.grid() if use else None), L.ptr(child.keys), child.n,
-            *S.grid_args(child.grid() if S.USE_GRID else None))
-
-
-def _reference_rows(reference, reference_attrs, channels, predict, what):
-    """(set or None for an empty reference, its uint8 [M, C] levels, the permutation that brings them into the set's order or
-    None) of the reference cloud of an inter stream: an [M, 6] cloud, or a pitch-1 set / [M, >= 3] rows with `reference_attrs`.
-    Refused: the input forms `encode_attributes` refuses, rows that repeat a voxel (their colours would be ambiguous), another
-    channel count than the stream's, and a stream without prediction."""
-    who = f"{what} (reference)"
-    if not predict:
-        raise L.PccError(f"{what}: a reference needs the prediction (predict=True)")
-    cloud, levels = _attribute_rows(reference, reference_attrs, who)
-    if levels.shape[1] != channels:
-        raise L.PccError(f"{who}: {levels.shape[1]} channels, the cloud has {channels}")
-    if (cloud.n if isinstance(cloud, S.CoordSet) else cloud.shape[0]) == 0:
-        return None, None, None
-    rs, perm, keep = G.canonical_rows(cloud, who)
-    if keep is not None:
-        raise L.PccError(f"{who}: {levels.shape[0] - rs.n} rows repeat a voxel; merge them first (voxelize.voxel_grid)")
-    if levels.device != rs.device:
-        raise L.PccError(f"{who}: points and attrs are on different devices")
-    return rs, levels, perm
-
-
-def _inter_state(cs, sets, origin, depth, ref, channels, colour, d_flag, prepare="pcc_lift_prepare", search=G.SEARCH):
-    """What both sides of an inter stream (0xB6 and 0xB4) recompute from the geometry and the reference: (the block arguments of
-    the pcc_lift_inter_* / pcc_raht_inter_* entry points, the block count, int32 match row per voxel, int32 [M, C] prepared
-    reference values or None, M).  `geometry.motion_vectors` gives the vectors; the tensors the arguments point into live in
-    `sets` and the result.  prepare: the entry point that turns the reference's levels into the coder's values (plain or
-    YCoCg-R levels for the lossless coder, Q8 with BT.709 for the RAHT coder: "pcc_raht_prepare").  search above 2: the wide search,
-    whose vectors are packed displacements (`pcc_lift_inter_match_wide`)."""
-    rs, levels, perm = ref
-    dev = cs.device
-    blocks, bl, _, vec = G.motion_vectors(cs, rs, origin, depth, sets, search=search)
-    grid = blocks.grid() if (depth > bl and S.USE_GRID) else None         # the root's single node is searched
-    bargs = (L.ptr(blocks.keys), blocks.n, *S.grid_args(grid), bl)
-    match = torch.empty(cs.n, dtype=torch.int32, device=dev)
-    L.call("pcc_lift_inter_match_wide" if search > G.MAX_SEARCH else "pcc_lift_inter_match", L.ptr(sets[depth].keys), cs.n, *bargs, L.ptr(vec),
-           search, *G.ref_args(rs), *origin, L.ptr(match), d_flag, L.stream())
-    if rs is None:
-        return bargs, blocks.n, match, None, 0, (vec, grid)
-    if levels.device != dev:
-        raise L.PccError("the reference is on another device than the cloud")
-    tv = torch.empty((rs.n, channels), dtype=torch.int32, device=dev)
-    L.call(prepare, L.ptr(levels), L.ptr(perm), rs.n, channels, int(colour), L.ptr(tv), L.stream())
-    return bargs, blocks.n, match, tv, rs.n, (vec, grid)
-
-
-def _rans_body(coef, idx, symbols, segment_symbols, dev, what, ph=None):
-    """`u32 length | rANS container` of the symbol vector; one device->host read (size + container).  ph: `geometry.Phases`
-    that get the mark "index_rans" behind the coder's launches."""
-    plan = R.Plan(symbols, 1, 1, segments_for(symbols, segment_symbols))
-    cap = R.align8(plan.capacity)
-    blob = torch.zeros(8 + cap, dtype=torch.uint8, device=dev)
-    R.encode(_tables(dev), plan, coef, idx, blob.data_ptr() + 8, blob.data_ptr())
-    if ph is not None:
-        ph.mark("index_rans")
-    host = blob.cpu().numpy()
-    nb = int(host[:8].view(np.int64)[0])
-    if not 0 < nb <= cap:
-        raise L.PccError(f"{what}: the coder produced {nb} bytes for a capacity of {cap}")
-    return struct.pack("<I", nb) + host[8:8 + nb].tobytes()
-
-
-def _inter_index(masks, offs, sets, depth, first, ch, bargs, d_mode, d_side, idx, coef_p, coef, rows, d_flag):
-    """idx of all rows of an inter RAHT stream: the levels above the blocks as in the intra stream, the levels inside them by
-    their block's mode.  d_side None: groups; coef given (encoder): the intra symbols of mode-0 blocks are copied into coef_p."""
-    _fill_index(masks, offs, sets, first, ch, d_side, idx, rows)
-    for l in range(first, depth):
-        L.call("pcc_raht_inter_select", L.ptr(sets[l].keys), L.ptr(masks[l]), L.ptr(offs[l]), sets[l].n, l, depth, ch, *bargs, L.ptr(d_mode),
-               L.ptr(d_side), L.ptr(idx), L.ptr(coef_p), L.ptr(coef), sets[l].n - 1, rows, d_flag, L.stream())
-
-
-def _encode_inter_lossy(what, cs, levels, perm, ref, qp, cqo, colour, mode, segment_symbols, timings, search=G.SEARCH):
-    """The inter half of `encode_attributes` (n >= 2, depth <= 14): the 0xB4 stream (0xB8 when `search` is above 2) and, for
-    mode "auto", the 0xB3 stream from
-    the same forward pass; the shorter is returned, intra on a tie.  Device->host reads beyond the level sets: 2 for the inter
-    stream (modes, root DCs and histograms; the container), 2 more for the intra stream of "auto"."""
-    n, ch, dev = cs.n, levels.shape[1], cs.device
-    steps = steps_for(qp, cqo, ch)
-    h_steps = (C.c_int32 * ch)(*steps)
-    origin, depth = tuple(cs.bounds.lo), _depth_of(cs)
-    rows = n - 1
-    with torch.cuda.device(dev):
-        ph = G.Phases(timings is not None)
-        sets = G.level_sets(cs, origin, depth)
-        ph.mark("start")
-        d_flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        bargs, nb, match, tv, nr, _keep = _inter_state(cs, sets, origin, depth, ref, ch, colour, L.ptr(d_flag), "pcc_raht_prepare", search)
-        first = depth - bargs[-1]
-        ph.mark("motion_match_ms")
-        values = torch.empty((n, ch), dtype=torch.int32, device=dev)
-        L.call("pcc_raht_prepare", L.ptr(levels), L.ptr(perm), n, ch, int(colour), L.ptr(values), L.stream())
-        masks, offs, checks = _plan(sets, depth, dev)
-        fill_sums = torch.empty((nb, ch + 1), dtype=torch.int32, device=dev)
-        pred = torch.empty((n, ch), dtype=torch.int32, device=dev)
-        L.call("pcc_raht_inter_fill", L.ptr(sets[depth].keys), n, *bargs, L.ptr(match), L.ptr(tv), nr, ch, None, L.ptr(fill_sums), L.ptr(pred),
-               L.ptr(d_flag), L.stream())
-        ph.mark("prepare_plan_fill_ms")
-        coef = torch.zeros((rows, ch), dtype=torch.int32, device=dev)      # the intra symbols of every row
-        coef_p = torch.zeros((rows, ch), dtype=torch.int32, device=dev)    # the inter stream's symbols
-        sums = torch.zeros((nb, 2), dtype=torch.int32, device=dev)
-        d_mode = torch.empty(nb, dtype=torch.int32, device=dev)
-        w_child, v_child, p_child = None, values, pred
-        for l in range(depth - 1, -1, -1):                                  # the levels above the blocks come after the decision
-            w = torch.empty(sets[l].n, dtype=torch.int32, device=dev)
-            v = torch.empty((sets[l].n, ch), dtype=torch.int32, device=dev)
-            p = torch.empty((sets[l].n, ch), dtype=torch.int32, device=dev)
-            L.call("pcc_raht_inter_forward", *_level_args(sets[l], sets[l + 1]), *bargs, L.ptr(offs[l]), L.ptr(w_child), L.ptr(v_child),
-                   L.ptr(p_child), ch, h_steps, L.ptr(w), L.ptr(v), L.ptr(p), L.ptr(coef), L.ptr(coef_p), sets[l].n - 1, rows,
-                   L.ptr(sums) if l >= first else None, L.ptr(d_flag), L.stream())
-            if l == first:
-                L.call("pcc_raht_inter_modes", L.ptr(sums), L.ptr(fill_sums), nb, ch, L.ptr(d_mode), L.ptr(p), L.stream())
-            w_child, v_child, p_child = w, v, p
-        ph.mark("forward_modes_ms")
-        groups = (depth + 1) * 6
-        idx = torch.empty(rows * ch, dtype=torch.int32, device=dev)
-        hist = torch.empty(groups * N_SLOTS, dtype=torch.int32, device=dev)
-        _inter_index(masks, offs, sets, depth, first, ch, bargs, d_mode, None, idx, coef_p, coef, rows, L.ptr(d_flag))
-        L.call("pcc_raht_hist", L.ptr(coef_p), L.ptr(idx), rows * ch, groups, L.ptr(hist), L.stream())
-        back = torch.cat([v_child.reshape(-1), p_child.reshape(-1), checks.reshape(-1), d_flag, d_mode, hist]).cpu().numpy()      # one read
-        at = 2 * ch + 4 * depth
-        _check_plan(back[2 * ch:at], sets, what)
-        if back[at] != 0:
-            raise L.PccError(f"{what}: the blocks, vectors or matches of the cloud are inconsistent")
-        root = [quantise(int(back[c]) - int(back[ch + c]), steps[c]) for c in range(ch)]
-        modes = back[at + 1:at + 1 + nb]
-        side = choose_members(back[at + 1 + nb:])
-        ph.mark("select_hist_choose_ms")
-        d_side = torch.tensor(side, dtype=torch.int32, device=dev)
-        _inter_index(masks, offs, sets, depth, first, ch, bargs, d_mode, d_side, idx, None, None, rows, L.ptr(d_flag))
-        body = _rans_body(coef_p, idx, rows * ch, segment_symbols, dev, what)          # one read: size + container
-        ph.mark("index_rans_ms")
-        out = bytearray(INTER_LOSSY_HEADER.pack(WIDE_LOSSY_MAGIC if search > G.MAX_SEARCH else INTER_LOSSY_MAGIC, n, depth, ch, int(colour), qp, cqo,
-                                                G.BLOCK_LOG2, search, nb))
-        for q in root:
-            out += _zigzag(q)
-        out += bytes(side) + np.packbits(modes.astype(bool), bitorder="little").tobytes() + body
-        intra = None
-        if mode == "auto":
-            dc, side0, body0 = _intra_tail(what, sets, masks, offs, checks, coef, v_child, depth, ch, rows, segment_symbols, dev, G.Phases(False))
-            intra = bytearray(HEADER.pack(MAGIC, n, depth, ch, int(colour), qp, cqo))
-            for q, step in zip(dc, steps):
-                intra += _zigzag(quantise(q, step))
-            intra += bytes(side0) + body0
-            ph.mark("intra_stream_ms")
-        if timings is not None:
-            torch.cuda.synchronize(dev)
-            timings["inter_stages_ms"] = ph.report()
-            timings["inter_bytes"], timings["intra_bytes"] = len(out), (len(intra) if intra is not None else None)
-            timings["mode1_blocks"], timings["blocks"] = int(modes.sum()), nb
-            timings["host_reads_by_construction"] = 4 if mode == "auto" else 2   # beyond those of building the level sets
-    return bytes(out if intra is None or len(out) < len(intra) else intra)
-
-
 @torch.no_grad()
 def encode_attributes_lossless(cloud, colour=True, attrs=None, predict=True, segment_symbols=SEGMENT_SYMBOLS, timings=None,
                                reference=None, reference_attrs=None, mode="auto", search=None):
@@ -896,7 +854,7 @@ def encode_attributes_lossless(cloud, colour=True, attrs=None, predict=True, seg
     n, ch, dev = cs.n, levels.shape[1], cs.device
     colour, predict = bool(colour) and ch == 3, bool(predict)
     if n == 0:
-        return LOSSLESS_HEADER.pack(LOSSLESS_MAGIC, 0, 0, ch, F_STORED)
+        return _stream(LOSSLESS_MAGIC, (0, 0, ch, F_STORED))
     origin = tuple(cs.bounds.lo)
     rows = n - 1
     with torch.cuda.device(dev):
@@ -934,14 +892,11 @@ def encode_attributes_lossless(cloud, colour=True, attrs=None, predict=True, seg
         out, stored = None, False
         if not inter or mode == "auto":
             root, side, body = _intra_tail(what, sets, masks, offs, checks, coef, v[0], depth, ch, rows, segment_symbols, dev, ph)
-            out = bytearray(LOSSLESS_HEADER.pack(LOSSLESS_MAGIC, n, depth, ch, (F_COLOUR if colour else 0) | (F_PREDICT if predict else 0)))
-            for q in root:
-                out += _zigzag(q)
-            out += bytes(side) + body
+            out = _stream(LOSSLESS_MAGIC, (n, depth, ch, (F_COLOUR if colour else 0) | (F_PREDICT if predict else 0)), root, side, None, body)
             stored = len(out) > LOSSLESS_HEADER.size + n * ch
             if stored:                                                     # a third read, of the raw levels, in this case alone
                 raw = levels if perm is None else levels[perm]
-                out = LOSSLESS_HEADER.pack(LOSSLESS_MAGIC, n, depth, ch, F_STORED) + raw.cpu().numpy().tobytes()
+                out = _stream(LOSSLESS_MAGIC, (n, depth, ch, F_STORED), body=raw.cpu().numpy().tobytes())
         if inter:
             # the select pass: modes from the block sums, the temporal rows of mode-1 blocks into coef, their rows into the groups
             # of level `depth`; then the members, the member index and the container as above
@@ -961,7 +916,7 @@ def encode_attributes_lossless(cloud, colour=True, attrs=None, predict=True, seg
             at = ch + 4 * depth
             if back[at] != 0:
                 raise L.PccError(f"{what}: the blocks, vectors or matches of the cloud are inconsistent")
-            modes = np.packbits(back[at + 1:at + 1 + nb].astype(bool), bitorder="little").tobytes()
+            modes = back[at + 1:at + 1 + nb]
             side = choose_members(back[at + 1 + nb:])
             ph.mark("select_hist_choose_ms", "inter")
             d_side = torch.tensor(side, dtype=torch.int32, device=dev)
@@ -970,14 +925,11 @@ def encode_attributes_lossless(cloud, colour=True, attrs=None, predict=True, seg
                    L.stream())
             body = _rans_body(coef, idx, rows * ch, segment_symbols, dev, what)          # one read: size + container
             ph.mark("inter_index_rans_ms", "inter")
-            coded = bytearray(INTER_HEADER.pack(WIDE_MAGIC if search > G.MAX_SEARCH else INTER_MAGIC, n, depth, ch, F_PREDICT | (F_COLOUR if colour else 0),
-                                                G.BLOCK_LOG2, search, nb))
-            for c in range(ch):
-                coded += _zigzag(int(back[c]))
-            coded += bytes(side) + modes + body
+            coded = _stream(WIDE_MAGIC if search > G.MAX_SEARCH else INTER_MAGIC,
+                            (n, depth, ch, F_PREDICT | (F_COLOUR if colour else 0), G.BLOCK_LOG2, search, nb), back[:ch], side, modes, body)
             if timings is not None:
                 timings["inter_bytes"], timings["intra_bytes"] = len(coded), (len(out) if out is not None else None)
-                timings["mode1_blocks"], timings["blocks"] = int(back[at + 1:at + 1 + nb].sum()), nb
+                timings["mode1_blocks"], timings["blocks"] = int(modes.sum()), nb
             if out is None or len(coded) < len(out):
                 out = coded
         if timings is not None:
@@ -989,7 +941,7 @@ def encode_attributes_lossless(cloud, colour=True, attrs=None, predict=True, seg
                 timings["stored"] = stored
             if inter:
                 timings["inter_stages_ms"] = ph.report("inter")
-    return bytes(out)
+    return out
 
 
 @torch.no_grad()

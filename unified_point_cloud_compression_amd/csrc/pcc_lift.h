@@ -1,10 +1,10 @@
-// Lossless attribute coder, the device helpers its source files share: the reversible lifting arithmetic,
-// the existence rule of a node's seven butterflies, and the probes of a level -- a node's eight children, the 27 cells around it
-// in its own level, the children's weights, and the lifted prediction of the children from the level's own values.
+// Lossless attribute coder, the device helpers its source files share: the reversible lifting arithmetic
+// and the probes only this coder makes -- the 27 cells around a node in its own level, and the lifted prediction of the children
+// from the level's own values.  A node's eight children, their weights, the existence rule of its seven butterflies and the block
+// level of an inter frame are pcc_oct_level.h's, shared with the RAHT coder.
 // pcc_lift.hip (the intra coder) and pcc_lift_inter.hip (the last level of an inter frame) include it.
 #pragma once
-#include "pcc_common.h"
-#include "pcc_conv.h"
+#include "pcc_oct_level.h"
 
 static constexpr int LIFT_MAX_C = 8;
 static constexpr int LIFT_SYMBOL_LIMIT = 1023;        // the decoder's clamp on a symbol (a valid one is within +-1020)
@@ -24,12 +24,6 @@ __host__ __device__ inline long long lift_floor_div(long long p, long long w) {
   const long long r = p - q * w;
   if (r < 0) --q;
   else if (r >= w) ++q;
-  return q;
-}
-
-__host__ __device__ inline int lift_floor_div32(int a, int d) {      // d >= 1
-  int q = a / d;
-  if (a % d < 0) --q;
   return q;
 }
 
@@ -53,21 +47,7 @@ __host__ __device__ inline int lift_predict(const int v[8], int mask) {
 #pragma unroll
   for (int b = 0; b < 8; ++b)
     if ((mask >> b) & 1) { den += lift_cell_weight(b); num += lift_cell_weight(b) * v[b]; }
-  return lift_floor_div32(num + (den >> 1), den);
-}
-
-// which of the seven butterflies of a node exist, in row order: [0] stage 3, [1] [2] stage 2 (slot 0, 4), [3..6] stage 1
-__host__ __device__ inline void lift_emits(int mask, bool e[7]) {
-  bool p[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int two = (mask >> (2 * k)) & 3;
-    e[3 + k] = two == 3;
-    p[k] = two != 0;
-  }
-  e[1] = p[0] && p[1];
-  e[2] = p[2] && p[3];
-  e[0] = (p[0] || p[1]) && (p[2] || p[3]);
+  return oct_floor_div32(num + (den >> 1), den);
 }
 
 // the three stages over the children's weights w[8] (0: absent) and values x[8] (0 where absent): the node's value, h[7] in
@@ -94,26 +74,6 @@ __host__ __device__ inline int lift_node_fwd(const int w[8], const bool e[7], co
 }
 
 // ---- probes ----------------------------------------------------------------------------------------------------------------
-// rows of the eight children (-1: absent); returns the occupancy byte
-__device__ inline int lift_kids(const LiftLevel& L, int i, int kid[8]) {
-  const int64_t key = L.keys[i];
-  const int x = pcc_key_x(key), y = pcc_key_y(key), z = pcc_key_z(key);
-  const int cp = L.pitch >> 1;
-  int mask = 0;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int cx = x + ((j >> 2) & 1) * cp, cy = y + ((j >> 1) & 1) * cp, cz = z + (j & 1) * cp;
-    int r = -1;
-    if ((cx | cy | cz) >= 0 && cx < (int)PCC_BIAS && cy < (int)PCC_BIAS && cz < (int)PCC_BIAS) {
-      r = pcc_lookup(L.cg, L.ckeys, L.nc, pcc_key_pack(0, cx, cy, cz));
-      if (r >= L.nc) r = -1;
-    }
-    kid[j] = r;
-    if (r >= 0) mask |= 1 << j;
-  }
-  return mask;
-}
-
 // rows of the 27 cells around node i in its own level, k = 9 (dx + 1) + 3 (dy + 1) + (dz + 1) (-1: absent; k = 13 is i)
 __device__ inline void lift_neighbours(const LiftLevel& L, int i, int nb[27]) {
   const int64_t key = L.keys[i];
@@ -129,11 +89,6 @@ __device__ inline void lift_neighbours(const LiftLevel& L, int i, int nb[27]) {
     }
     nb[k] = r;
   }
-}
-
-__device__ inline void lift_child_weights(const int* __restrict__ cw, const int kid[8], int w[8]) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) w[j] = kid[j] < 0 ? 0 : (cw ? cw[kid[j]] : 1);      // cw == nullptr: the children are voxels
 }
 
 // the predictions of channel c of a node's present children from the level's values v (0 where kid[j] < 0).  Cell b of child j
@@ -184,20 +139,12 @@ __device__ inline void lift_node_hp(const int* __restrict__ v, int C, int c, con
 static bool lift_level(const char* what, const int64_t* keys, int64_t n, int32_t pitch, const uint64_t* bits, const int32_t* rank,
                        const int32_t* h_grid, const int64_t* child_keys, int64_t n_child, const uint64_t* child_bits,
                        const int32_t* child_rank, const int32_t* h_child, LiftLevel* L) {
-  if (!(keys && child_keys && n > 0 && n_child >= n && n_child < (1ll << 26))) {
-    pcc_set_error("%s: bad arguments (a level of n >= 1 nodes with n .. 2^26 - 1 children)", what);
-    return false;
-  }
-  if (!(pitch >= 2 && pitch <= (1 << 15) && pcc_is_pow2(pitch))) {
-    pcc_set_error("%s: pitch %d is not a power of two in [2, 2^15]", what, pitch);
-    return false;
-  }
+  if (!oct_level(what, keys, n, pitch, child_keys, n_child, L)) return false;
   if (pcc_grid_from_host(bits, rank, h_grid, what, &L->g) != PCC_OK) return false;                 // bits == NULL: binary search
   if (pcc_grid_from_host(child_bits, child_rank, h_child, what, &L->cg) != PCC_OK) return false;
   if ((L->g.bits && h_grid[6] != pitch) || (L->cg.bits && h_child[6] != pitch / 2)) {
     pcc_set_error("%s: a grid index has another pitch than its level", what);
     return false;
   }
-  L->keys = keys; L->n = (int)n; L->pitch = pitch; L->ckeys = child_keys; L->nc = (int)n_child;
   return true;
 }

@@ -42,8 +42,8 @@ __global__ void __launch_bounds__(256) k_lift_forward(LiftLevel L, const int* __
   if (i >= L.n) return;
   int kid[8], w[8];
   bool e[7];
-  lift_emits(lift_kids(L, i, kid), e);
-  lift_child_weights(cw, kid, w);
+  oct_emits(oct_kids(L, i, kid), e);
+  oct_child_weights(cw, kid, w);
   int s = 0;
 #pragma unroll
   for (int j = 0; j < 8; ++j) s += w[j];
@@ -69,8 +69,8 @@ __global__ void __launch_bounds__(256) k_lift_residual(LiftLevel L, const int* _
   if (i >= L.n) return;
   int kid[8], w[8], nb[27];
   bool e[7];
-  lift_emits(lift_kids(L, i, kid), e);
-  lift_child_weights(cw, kid, w);
+  oct_emits(oct_kids(L, i, kid), e);
+  oct_child_weights(cw, kid, w);
   lift_neighbours(L, i, nb);
   long long row[7], r = row_base + off[i] - i;
 #pragma unroll
@@ -92,8 +92,8 @@ __global__ void __launch_bounds__(256) k_lift_inverse(LiftLevel L, const int* __
   if (i >= L.n) return;
   int kid[8], w[8], nb[27];
   bool e[7];
-  lift_emits(lift_kids(L, i, kid), e);
-  lift_child_weights(cw, kid, w);
+  oct_emits(oct_kids(L, i, kid), e);
+  oct_child_weights(cw, kid, w);
   if (predict) lift_neighbours(L, i, nb);
   long long row[7], r = row_base + off[i] - i;
 #pragma unroll

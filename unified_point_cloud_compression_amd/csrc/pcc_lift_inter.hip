@@ -18,17 +18,6 @@
 #include "pcc_geom_inter.h"
 #include "pcc_lift.h"
 
-struct LiftBlocks { const int64_t* keys; int n; PccGrid g; int bl; };      // the nodes of the block level, origin-relative
-
-// the row of the block that holds an origin-relative cell (-1: none, which a consistent geometry never gives)
-__device__ inline int lift_block_of(const LiftBlocks& B, int64_t key) {
-  const int bm = (1 << B.bl) - 1;
-  const int x = pcc_key_x(key), y = pcc_key_y(key), z = pcc_key_z(key);
-  if ((x | y | z) < 0 || x >= (int)PCC_BIAS || y >= (int)PCC_BIAS || z >= (int)PCC_BIAS) return -1;
-  const int row = pcc_lookup(B.g, B.keys, B.n, pcc_key_pack(0, x & ~bm, y & ~bm, z & ~bm));
-  return (row >= 0 && row < B.n) ? row : -1;
-}
-
 // the matches of a node's children, validated: tm[j] in [-1, nr); returns false when one had to be dropped
 __device__ inline bool lift_kid_matches(const int* __restrict__ match, int nr, const int kid[8], int tm[8]) {
   bool ok = true;
@@ -42,13 +31,13 @@ __device__ inline bool lift_kid_matches(const int* __restrict__ match, int nr, c
 }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_lift_inter_match(const int64_t* __restrict__ vkeys, int n, LiftBlocks B, const int* __restrict__ vec,
+__global__ void __launch_bounds__(256) k_lift_inter_match(const int64_t* __restrict__ vkeys, int n, OctBlocks B, const int* __restrict__ vec,
                                                           InterCands cands, const int64_t* __restrict__ rkeys, int nr, PccGrid rg, int ox,
                                                           int oy, int oz, int* __restrict__ match, int* __restrict__ d_flag) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int64_t key = vkeys[i];
-  const int row = lift_block_of(B, key);
+  const int row = oct_block_of(B, key);
   int j = row < 0 ? -1 : vec[row];
   if (j < 0 || j >= cands.n) { atomicOr(d_flag, 1); j = 0; }
   int dx, dy, dz;
@@ -64,13 +53,13 @@ __global__ void __launch_bounds__(256) k_lift_inter_match(const int64_t* __restr
 }
 
 // k_lift_inter_match with a packed displacement per block (the wide search); one outside +-search counts as zero and sets the flag
-__global__ void __launch_bounds__(256) k_lift_inter_match_wide(const int64_t* __restrict__ vkeys, int n, LiftBlocks B, const int* __restrict__ disp,
+__global__ void __launch_bounds__(256) k_lift_inter_match_wide(const int64_t* __restrict__ vkeys, int n, OctBlocks B, const int* __restrict__ disp,
                                                                int search, const int64_t* __restrict__ rkeys, int nr, PccGrid rg, int ox,
                                                                int oy, int oz, int* __restrict__ match, int* __restrict__ d_flag) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int64_t key = vkeys[i];
-  const int row = lift_block_of(B, key);
+  const int row = oct_block_of(B, key);
   int dx, dy, dz;
   if (!wide_unpack(row < 0 ? -1 : disp[row], search, dx, dy, dz)) atomicOr(d_flag, 1);
   const int qx = ox + pcc_key_x(key) - dx, qy = oy + pcc_key_y(key) - dy, qz = oz + pcc_key_z(key) - dz;
@@ -83,7 +72,7 @@ __global__ void __launch_bounds__(256) k_lift_inter_match_wide(const int64_t* __
   match[i] = m;
 }
 
-__global__ void __launch_bounds__(256) k_lift_inter_residual(LiftLevel L, LiftBlocks B, const int* __restrict__ off,
+__global__ void __launch_bounds__(256) k_lift_inter_residual(LiftLevel L, OctBlocks B, const int* __restrict__ off,
                                                              const int* __restrict__ v, int C, const int* __restrict__ match,
                                                              const int* __restrict__ tv, int nr, int* __restrict__ coef,
                                                              int* __restrict__ coef_t, long long row_base, long long rows_total,
@@ -94,11 +83,11 @@ __global__ void __launch_bounds__(256) k_lift_inter_residual(LiftLevel L, LiftBl
   if (live) {
     int kid[8], w[8], nb[27], tm[8];
     bool e[7];
-    lift_emits(lift_kids(L, i, kid), e);
-    lift_child_weights(nullptr, kid, w);
+    oct_emits(oct_kids(L, i, kid), e);
+    oct_child_weights(nullptr, kid, w);
     lift_neighbours(L, i, nb);
     bool ok = lift_kid_matches(match, nr, kid, tm);
-    blk = lift_block_of(B, L.keys[i]);
+    blk = oct_block_of(B, L.keys[i]);
     if (blk < 0) ok = false;
     long long row[7], r = row_base + off[i] - i;
 #pragma unroll
@@ -146,15 +135,15 @@ __global__ void __launch_bounds__(256) k_lift_inter_modes(const int* __restrict_
 }
 
 __global__ void __launch_bounds__(256) k_lift_inter_select(const int64_t* __restrict__ keys, const int* __restrict__ mask,
-                                                           const int* __restrict__ off, int n, int level, int C, LiftBlocks B,
+                                                           const int* __restrict__ off, int n, int level, int C, OctBlocks B,
                                                            const int* __restrict__ mode, const int* __restrict__ side,
                                                            int* __restrict__ idx, int* __restrict__ coef, const int* __restrict__ coef_t,
                                                            long long row_base, long long rows_total, int* __restrict__ d_flag) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   bool e[7];
-  lift_emits(mask[i] & 255, e);
-  const int blk = lift_block_of(B, keys[i]);
+  oct_emits(mask[i] & 255, e);
+  const int blk = oct_block_of(B, keys[i]);
   int m = blk < 0 ? -1 : mode[blk];
   if (m != 0 && m != 1) { atomicOr(d_flag, 1); m = 0; }
   long long r = row_base + off[i] - i;
@@ -174,7 +163,7 @@ __global__ void __launch_bounds__(256) k_lift_inter_select(const int64_t* __rest
 }
 
 // The body below the prediction is k_lift_inverse's (pcc_lift.hip): the same clamps in the same places.
-__global__ void __launch_bounds__(256) k_lift_inter_inverse(LiftLevel L, LiftBlocks B, const int* __restrict__ mode,
+__global__ void __launch_bounds__(256) k_lift_inter_inverse(LiftLevel L, OctBlocks B, const int* __restrict__ mode,
                                                             const int* __restrict__ off, const int* __restrict__ v, int C, int colour,
                                                             const int* __restrict__ match, const int* __restrict__ tv, int nr,
                                                             const int* __restrict__ coef, long long row_base, long long rows_total,
@@ -183,11 +172,11 @@ __global__ void __launch_bounds__(256) k_lift_inter_inverse(LiftLevel L, LiftBlo
   if (i >= L.n) return;
   int kid[8], w[8], nb[27], tm[8];
   bool e[7];
-  lift_emits(lift_kids(L, i, kid), e);
-  lift_child_weights(nullptr, kid, w);
+  oct_emits(oct_kids(L, i, kid), e);
+  oct_child_weights(nullptr, kid, w);
   lift_neighbours(L, i, nb);
   bool clamped = !lift_kid_matches(match, nr, kid, tm);
-  const int blk = lift_block_of(B, L.keys[i]);
+  const int blk = oct_block_of(B, L.keys[i]);
   int m = blk < 0 ? -1 : mode[blk];
   if (m != 0 && m != 1) { clamped = true; m = 0; }
   long long row[7], r = row_base + off[i] - i;
@@ -245,21 +234,6 @@ __global__ void __launch_bounds__(256) k_lift_inter_inverse(LiftLevel L, LiftBlo
 }
 
 // ---- entry points --------------------------------------------------------------------------------------------------------------
-static bool lift_blocks(const char* what, const int64_t* keys, int64_t n, const uint64_t* bits, const int32_t* rank, const int32_t* h,
-                        int32_t block_log2, LiftBlocks* B) {
-  if (!(keys && n > 0 && n < (1ll << 24) && block_log2 >= 1 && block_log2 <= 4)) {
-    pcc_set_error("%s: bad block level (1 .. 2^24 - 1 blocks, block_log2 in 1..4)", what);
-    return false;
-  }
-  if (pcc_grid_from_host(bits, rank, h, what, &B->g) != PCC_OK) return false;
-  if (B->g.bits && h[6] != (1 << block_log2)) {
-    pcc_set_error("%s: the block grid has another pitch", what);
-    return false;
-  }
-  B->keys = keys; B->n = (int)n; B->bl = block_log2;
-  return true;
-}
-
 // the last level of a cloud: nodes at pitch 2 whose children are the voxels
 static bool lift_last_level(const char* what, const int64_t* keys, int64_t n, int32_t pitch, const uint64_t* bits, const int32_t* rank,
                             const int32_t* h_grid, const int64_t* child_keys, int64_t n_child, const uint64_t* child_bits,
@@ -287,8 +261,8 @@ extern "C" int pcc_lift_inter_match(const int64_t* voxel_keys, int64_t n, const 
   PCC_REQUIRE(voxel_keys && vec && match && d_flag && n > 0 && n < (1ll << 26), "pcc_lift_inter_match: bad arguments");
   PCC_REQUIRE(n_ref >= 0 && n_ref < (1ll << 26) && (n_ref == 0 || ref_keys), "pcc_lift_inter_match: bad reference set");
   PCC_REQUIRE(inter_origin_ok(ox, oy, oz), "pcc_lift_inter_match: origin outside the 16-bit key range");
-  LiftBlocks B;
-  if (!lift_blocks("pcc_lift_inter_match", block_keys, n_blocks, block_bits, block_rank, h_block, block_log2, &B)) return PCC_EINVAL;
+  OctBlocks B;
+  if (!oct_blocks("pcc_lift_inter_match", block_keys, n_blocks, block_bits, block_rank, h_block, block_log2, &B)) return PCC_EINVAL;
   InterCands c;
   PCC_TRY(inter_cands(search, "pcc_lift_inter_match", &c));
   PccGrid g;
@@ -309,8 +283,8 @@ extern "C" int pcc_lift_inter_match_wide(const int64_t* voxel_keys, int64_t n, c
   PCC_REQUIRE(n_ref >= 0 && n_ref < (1ll << 26) && (n_ref == 0 || ref_keys), "pcc_lift_inter_match_wide: bad reference set");
   PCC_REQUIRE(inter_origin_ok(ox, oy, oz), "pcc_lift_inter_match_wide: origin outside the 16-bit key range");
   PCC_REQUIRE(search >= 1 && search <= 7, "pcc_lift_inter_match_wide: search range %d outside 1..7", search);
-  LiftBlocks B;
-  if (!lift_blocks("pcc_lift_inter_match_wide", block_keys, n_blocks, block_bits, block_rank, h_block, block_log2, &B)) return PCC_EINVAL;
+  OctBlocks B;
+  if (!oct_blocks("pcc_lift_inter_match_wide", block_keys, n_blocks, block_bits, block_rank, h_block, block_log2, &B)) return PCC_EINVAL;
   PccGrid g;
   PCC_TRY(pcc_grid_from_host(n_ref ? ref_bits : nullptr, ref_rank, h_ref, "pcc_lift_inter_match_wide", &g));
   PCC_REQUIRE(!g.bits || h_ref[6] == 1, "pcc_lift_inter_match_wide: the reference grid must have pitch 1");
@@ -329,9 +303,9 @@ extern "C" int pcc_lift_inter_residual(const int64_t* keys, int64_t n, int32_t p
                                        int64_t rows_total, int32_t* sums, int32_t* d_flag, void* stream) {
   const char* what = "pcc_lift_inter_residual";
   LiftLevel L;
-  LiftBlocks B;
+  OctBlocks B;
   if (!lift_last_level(what, keys, n, pitch, bits, rank, h_grid, child_keys, n_child, child_bits, child_rank, h_child, &L)) return PCC_EINVAL;
-  if (!lift_blocks(what, block_keys, n_blocks, block_bits, block_rank, h_block, block_log2, &B)) return PCC_EINVAL;
+  if (!oct_blocks(what, block_keys, n_blocks, block_bits, block_rank, h_block, block_log2, &B)) return PCC_EINVAL;
   if (!lift_reference(what, match, ref_values, n_ref)) return PCC_EINVAL;
   // rows_total == row_base: no node of the level has two children -- no row is touched, coef_t may be NULL, the sums stay 0
   PCC_REQUIRE(channels >= 1 && channels <= LIFT_MAX_C && off && v && coef && sums && d_flag && row_base >= 0 && rows_total > 0 &&
@@ -351,8 +325,8 @@ extern "C" int pcc_lift_inter_select(const int64_t* keys, const int32_t* mask, c
                                      int32_t* mode, const int32_t* side, int32_t* idx, int32_t* coef, const int32_t* coef_t,
                                      int64_t row_base, int64_t rows_total, int32_t* d_flag, void* stream) {
   const char* what = "pcc_lift_inter_select";
-  LiftBlocks B;
-  if (!lift_blocks(what, block_keys, n_blocks, block_bits, block_rank, h_block, block_log2, &B)) return PCC_EINVAL;
+  OctBlocks B;
+  if (!oct_blocks(what, block_keys, n_blocks, block_bits, block_rank, h_block, block_log2, &B)) return PCC_EINVAL;
   PCC_REQUIRE(keys && mask && off && mode && idx && d_flag && n > 0 && n < (1ll << 26) && level >= 0 && level < 14 && channels >= 1 &&
               channels <= LIFT_MAX_C && row_base >= 0 && rows_total > 0 && rows_total >= row_base && rows_total < (1ll << 26),
               "pcc_lift_inter_select: bad arguments (the last level of a cloud of depth <= 14)");
@@ -379,9 +353,9 @@ extern "C" int pcc_lift_inter_inverse(const int64_t* keys, int64_t n, int32_t pi
                                       int64_t row_base, int64_t rows_total, int32_t* child_v, int32_t* d_flag, void* stream) {
   const char* what = "pcc_lift_inter_inverse";
   LiftLevel L;
-  LiftBlocks B;
+  OctBlocks B;
   if (!lift_last_level(what, keys, n, pitch, bits, rank, h_grid, child_keys, n_child, child_bits, child_rank, h_child, &L)) return PCC_EINVAL;
-  if (!lift_blocks(what, block_keys, n_blocks, block_bits, block_rank, h_block, block_log2, &B)) return PCC_EINVAL;
+  if (!oct_blocks(what, block_keys, n_blocks, block_bits, block_rank, h_block, block_log2, &B)) return PCC_EINVAL;
   if (!lift_reference(what, match, ref_values, n_ref)) return PCC_EINVAL;
   PCC_REQUIRE(channels >= 1 && channels <= LIFT_MAX_C && (!colour || channels == 3) && mode && off && v && coef && child_v && d_flag &&
               row_base >= 0 && rows_total > 0 && rows_total < (1ll << 26), "pcc_lift_inter_inverse: bad arguments");

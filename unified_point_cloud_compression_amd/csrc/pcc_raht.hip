@@ -42,15 +42,15 @@ __global__ void __launch_bounds__(256) k_raht_mask(RahtLevel L, int* __restrict_
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= L.n) return;
   int kid[8];
-  mask[i] = raht_kids(L, i, kid);
+  mask[i] = oct_kids(L, i, kid);
 }
 
 __global__ void __launch_bounds__(256) k_raht_weights(RahtLevel L, const int* __restrict__ cw, int* __restrict__ wout) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= L.n) return;
   int kid[8], w[8], s = 0;
-  raht_kids(L, i, kid);
-  raht_child_weights(cw, kid, w);
+  oct_kids(L, i, kid);
+  oct_child_weights(cw, kid, w);
 #pragma unroll
   for (int j = 0; j < 8; ++j) s += w[j];
   wout[i] = s;
@@ -63,8 +63,8 @@ __global__ void __launch_bounds__(256) k_raht_forward(RahtLevel L, const int* __
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= L.n) return;
   int kid[8], w[8];
-  raht_kids(L, i, kid);
-  raht_child_weights(cw, kid, w);
+  oct_kids(L, i, kid);
+  oct_child_weights(cw, kid, w);
   RahtNode nd;
   raht_node(w, nd);
   wout[i] = nd.weight;
@@ -110,8 +110,8 @@ __global__ void __launch_bounds__(256) k_raht_inverse(RahtLevel L, const int* __
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= L.n) return;
   int kid[8], w[8];
-  raht_kids(L, i, kid);
-  raht_child_weights(cw, kid, w);
+  oct_kids(L, i, kid);
+  oct_child_weights(cw, kid, w);
   RahtNode nd;
   raht_node(w, nd);
   long long row[7], r = row_base + off[i] - i;
@@ -164,7 +164,7 @@ __global__ void __launch_bounds__(256) k_raht_index(const int* __restrict__ mask
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   bool e[7];
-  raht_emits(mask[i] & 255, e);
+  oct_emits(mask[i] & 255, e);
   long long r = row_base + off[i] - i;
 #pragma unroll
   for (int t = 0; t < 7; ++t) {

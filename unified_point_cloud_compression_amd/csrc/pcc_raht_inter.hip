@@ -19,23 +19,6 @@
 // bounded by caller-given counts; a block row, a mode or a match outside its range counts as mode 0 / unmatched and sets the flag.
 #include "pcc_raht.h"
 
-struct RahtBlocks { const int64_t* keys; int n; PccGrid g; int bl; };      // the nodes of the block level, origin-relative
-
-// the row of the block that holds an origin-relative cell (-1: none, which a consistent geometry never gives)
-__device__ inline int raht_block_of(const RahtBlocks& B, int64_t key) {
-  const int bm = (1 << B.bl) - 1;
-  const int x = pcc_key_x(key), y = pcc_key_y(key), z = pcc_key_z(key);
-  if ((x | y | z) < 0 || x >= (int)PCC_BIAS || y >= (int)PCC_BIAS || z >= (int)PCC_BIAS) return -1;
-  const int row = pcc_lookup(B.g, B.keys, B.n, pcc_key_pack(0, x & ~bm, y & ~bm, z & ~bm));
-  return (row >= 0 && row < B.n) ? row : -1;
-}
-
-__device__ inline int raht_floor_div(int a, int d) {                       // d >= 1
-  int q = a / d;
-  if (a % d < 0) --q;
-  return q;
-}
-
 // Rows are in key order, so runs of lanes share a block.  A run starts where the block differs from the lane below; `end` is the
 // lane after this lane's run.  Every lane of the wave must call these.
 __device__ inline bool raht_run_head(int blk, int& end) {
@@ -88,13 +71,13 @@ __device__ inline int raht_quantise(long long h, long long step) {
 // ---- kernels ---------------------------------------------------------------------------------------------------------------
 // sums [blocks, C + 1]: per channel the sum of the matched voxels' reference rows (|value| < 2^17, at most 4096 voxels: int32),
 // then their count
-__global__ void __launch_bounds__(256) k_raht_inter_sums(const int64_t* __restrict__ vkeys, int n, RahtBlocks B, const int* __restrict__ match,
+__global__ void __launch_bounds__(256) k_raht_inter_sums(const int64_t* __restrict__ vkeys, int n, OctBlocks B, const int* __restrict__ match,
                                                          const int* __restrict__ tv, int nr, int C, int* __restrict__ sums,
                                                          int* __restrict__ d_flag) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   int blk = -1, m = -1;
   if (i < n) {
-    blk = raht_block_of(B, vkeys[i]);
+    blk = oct_block_of(B, vkeys[i]);
     m = match[i];
     if (m < -1 || m >= nr || blk < 0) { atomicOr(d_flag, 1); m = -1; }
   }
@@ -107,12 +90,12 @@ __global__ void __launch_bounds__(256) k_raht_inter_sums(const int64_t* __restri
   }
 }
 
-__global__ void __launch_bounds__(256) k_raht_inter_fill(const int64_t* __restrict__ vkeys, int n, RahtBlocks B, const int* __restrict__ match,
+__global__ void __launch_bounds__(256) k_raht_inter_fill(const int64_t* __restrict__ vkeys, int n, OctBlocks B, const int* __restrict__ match,
                                                          const int* __restrict__ tv, int nr, int C, const int* __restrict__ sums,
                                                          const int* __restrict__ mode, int* __restrict__ pred, int* __restrict__ d_flag) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const int blk = raht_block_of(B, vkeys[i]);
+  const int blk = oct_block_of(B, vkeys[i]);
   int m = match[i];
   if (m < -1 || m >= nr) m = -1;                      // k_raht_inter_sums has set the flag
   int keep = blk < 0 ? 0 : (mode ? mode[blk] : 1);
@@ -121,12 +104,12 @@ __global__ void __launch_bounds__(256) k_raht_inter_fill(const int64_t* __restri
   if (cnt <= 0) keep = 0;                             // a block without any match is mode 0 by rule
   for (int c = 0; c < C; ++c) {
     int p = 0;
-    if (keep) p = m >= 0 ? tv[(size_t)m * C + c] : raht_floor_div(sums[(size_t)blk * (C + 1) + c], cnt);
+    if (keep) p = m >= 0 ? tv[(size_t)m * C + c] : oct_floor_div32(sums[(size_t)blk * (C + 1) + c], cnt);
     pred[(size_t)i * C + c] = p;
   }
 }
 
-__global__ void __launch_bounds__(256) k_raht_inter_forward(RahtLevel L, RahtBlocks B, const int* __restrict__ off, const int* __restrict__ cw,
+__global__ void __launch_bounds__(256) k_raht_inter_forward(RahtLevel L, OctBlocks B, const int* __restrict__ off, const int* __restrict__ cw,
                                                             const int* __restrict__ cv, const int* __restrict__ cp, int C, RahtSteps steps,
                                                             int* __restrict__ wout, int* __restrict__ vout, int* __restrict__ pout,
                                                             int* __restrict__ coef, int* __restrict__ coef_p, long long row_base,
@@ -136,13 +119,13 @@ __global__ void __launch_bounds__(256) k_raht_inter_forward(RahtLevel L, RahtBlo
   int blk = -1, s_intra = 0, s_inter = 0;
   if (live) {
     int kid[8], w[8];
-    raht_kids(L, i, kid);
-    raht_child_weights(cw, kid, w);
+    oct_kids(L, i, kid);
+    oct_child_weights(cw, kid, w);
     RahtNode nd;
     raht_node(w, nd);
     wout[i] = nd.weight;
     if (sums) {
-      blk = raht_block_of(B, L.keys[i]);
+      blk = oct_block_of(B, L.keys[i]);
       if (blk < 0) atomicOr(d_flag, 1);
     }
     long long row[7], r = row_base + off[i] - i;
@@ -191,15 +174,15 @@ __global__ void __launch_bounds__(256) k_raht_inter_modes(const int* __restrict_
 }
 
 __global__ void __launch_bounds__(256) k_raht_inter_select(const int64_t* __restrict__ keys, const int* __restrict__ mask,
-                                                           const int* __restrict__ off, int n, int level, int depth, int C, RahtBlocks B,
+                                                           const int* __restrict__ off, int n, int level, int depth, int C, OctBlocks B,
                                                            const int* __restrict__ mode, const int* __restrict__ side,
                                                            int* __restrict__ idx, int* __restrict__ coef_p, const int* __restrict__ coef,
                                                            long long row_base, long long rows_total, int* __restrict__ d_flag) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   bool e[7];
-  raht_emits(mask[i] & 255, e);
-  const int blk = raht_block_of(B, keys[i]);
+  oct_emits(mask[i] & 255, e);
+  const int blk = oct_block_of(B, keys[i]);
   int m = blk < 0 ? -1 : mode[blk];
   if (m != 0 && m != 1) { atomicOr(d_flag, 1); m = 0; }
   long long r = row_base + off[i] - i;
@@ -224,8 +207,8 @@ __global__ void __launch_bounds__(256) k_raht_inter_predict(RahtLevel L, const i
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= L.n) return;
   int kid[8], w[8];
-  raht_kids(L, i, kid);
-  raht_child_weights(cw, kid, w);
+  oct_kids(L, i, kid);
+  oct_child_weights(cw, kid, w);
   RahtNode nd;
   raht_node(w, nd);
   long long row[7], r = row_base + off[i] - i;
@@ -251,8 +234,8 @@ __global__ void __launch_bounds__(256) k_raht_inter_inverse(RahtLevel L, const i
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= L.n) return;
   int kid[8], w[8];
-  raht_kids(L, i, kid);
-  raht_child_weights(cw, kid, w);
+  oct_kids(L, i, kid);
+  oct_child_weights(cw, kid, w);
   RahtNode nd;
   raht_node(w, nd);
   long long row[7], r = row_base + off[i] - i;
@@ -301,28 +284,13 @@ __global__ void __launch_bounds__(256) k_raht_inter_inverse(RahtLevel L, const i
 }
 
 // ---- entry points --------------------------------------------------------------------------------------------------------------
-static bool raht_blocks(const char* what, const int64_t* keys, int64_t n, const uint64_t* bits, const int32_t* rank, const int32_t* h,
-                        int32_t block_log2, RahtBlocks* B) {
-  if (!(keys && n > 0 && n < (1ll << 24) && block_log2 >= 1 && block_log2 <= 4)) {
-    pcc_set_error("%s: bad block level (1 .. 2^24 - 1 blocks, block_log2 in 1..4)", what);
-    return false;
-  }
-  if (pcc_grid_from_host(bits, rank, h, what, &B->g) != PCC_OK) return false;
-  if (B->g.bits && h[6] != (1 << block_log2)) {
-    pcc_set_error("%s: the block grid has another pitch", what);
-    return false;
-  }
-  B->keys = keys; B->n = (int)n; B->bl = block_log2;
-  return true;
-}
-
 extern "C" int pcc_raht_inter_fill(const int64_t* voxel_keys, int64_t n, const int64_t* block_keys, int64_t n_blocks,
                                    const uint64_t* block_bits, const int32_t* block_rank, const int32_t* h_block, int32_t block_log2,
                                    const int32_t* match, const int32_t* ref_values, int64_t n_ref, int32_t channels, const int32_t* mode,
                                    int32_t* sums, int32_t* pred, int32_t* d_flag, void* stream) {
   const char* what = "pcc_raht_inter_fill";
-  RahtBlocks B;
-  if (!raht_blocks(what, block_keys, n_blocks, block_bits, block_rank, h_block, block_log2, &B)) return PCC_EINVAL;
+  OctBlocks B;
+  if (!oct_blocks(what, block_keys, n_blocks, block_bits, block_rank, h_block, block_log2, &B)) return PCC_EINVAL;
   PCC_REQUIRE(voxel_keys && match && sums && pred && d_flag && n > 0 && n < (1ll << 26) && channels >= 1 && channels <= RAHT_MAX_C &&
               n_ref >= 0 && n_ref < (1ll << 26) && (n_ref == 0 || ref_values), "pcc_raht_inter_fill: bad arguments");
   hipStream_t s = (hipStream_t)stream;
@@ -345,11 +313,11 @@ extern "C" int pcc_raht_inter_forward(const int64_t* keys, int64_t n, int32_t pi
   const char* what = "pcc_raht_inter_forward";
   RahtLevel L;
   RahtSteps st;
-  RahtBlocks B = {};
+  OctBlocks B = {};
   if (!raht_level(what, keys, n, pitch, child_keys, n_child, child_bits, child_rank, h_child, &L)) return PCC_EINVAL;
   if (!raht_steps(what, channels, h_steps, &st)) return PCC_EINVAL;
   if (sums) {                                         // a level at or below the blocks: its nodes' sums go to their blocks
-    if (!raht_blocks(what, block_keys, n_blocks, block_bits, block_rank, h_block, block_log2, &B)) return PCC_EINVAL;
+    if (!oct_blocks(what, block_keys, n_blocks, block_bits, block_rank, h_block, block_log2, &B)) return PCC_EINVAL;
     PCC_REQUIRE(pitch <= (1 << block_log2) && d_flag, "pcc_raht_inter_forward: sums belong to the levels inside the blocks");
   }
   PCC_REQUIRE(off && child_v && child_p && w && v && p && coef && coef_p && row_base >= 0 && rows_total > 0,
@@ -376,8 +344,8 @@ extern "C" int pcc_raht_inter_select(const int64_t* keys, const int32_t* mask, c
                                      const int32_t* side, int32_t* idx, int32_t* coef_p, const int32_t* coef, int64_t row_base,
                                      int64_t rows_total, int32_t* d_flag, void* stream) {
   const char* what = "pcc_raht_inter_select";
-  RahtBlocks B;
-  if (!raht_blocks(what, block_keys, n_blocks, block_bits, block_rank, h_block, block_log2, &B)) return PCC_EINVAL;
+  OctBlocks B;
+  if (!oct_blocks(what, block_keys, n_blocks, block_bits, block_rank, h_block, block_log2, &B)) return PCC_EINVAL;
   PCC_REQUIRE(keys && mask && off && mode && idx && d_flag && n > 0 && n < (1ll << 26) && depth >= 1 && depth < 15 &&
               level >= depth - block_log2 && level >= 0 && level < depth && channels >= 1 && channels <= RAHT_MAX_C && row_base >= 0 &&
               rows_total > 0 && rows_total < (1ll << 26) && (!coef || coef_p),
