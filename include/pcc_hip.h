@@ -878,6 +878,47 @@ int pcc_raht_inter_inverse(const int64_t* keys, int64_t n, int32_t pitch, const 
                            int64_t rows_total, int32_t* child_v, int32_t* d_flag, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 8f-3c" prediction from the parent level in the RAHT colour coder (DESIGN.md section 7f "Prediction from the parent level",
+ *       stream 0xB9): the rows, steps and groups of 8f-3c, every row coded as quantise(H - Hp).  Per node of a level with
+ *       reconstructed DC D and weight w: its mean m = (a D + 2^29) >> 30, a = isqrt(((1 << 32) / w) << 28), clamped to +-2^24;
+ *       child (dx, dy, dz) is predicted from the means of the present cells node + d * b of the node's own level by the 27 / 9 /
+ *       3 / 1 rule of 8f-3d; P = (pred * isqrt(w_child << 32) + 2^15) >> 16, clamped to +-2^30; Hp = the node's three butterfly
+ *       stages over the present children's P with the children's weights; the decoder takes H = Hp + q * step (both terms and
+ *       the sum clamped to +-2^30) and the inverse butterflies of pcc_raht_inverse with L = D.  Closed loop: the encoder runs
+ *       pcc_raht_forward with every step 1 (h_true = the unquantised H rows), then pcc_raht_pred_root and pcc_raht_pred_encode
+ *       level by level from the root.  A level is given as in 8f-3d: bits / rank / h_grid are the NODE level's own grid index
+ *       (pitch h_grid[6] == pitch) or three NULLs: binary search over keys.  Same bits either way.  v, m: the level's
+ *       reconstructed DCs and means, int32 [n, channels]; child_v, child_m: those of the children, written here (child_m NULL
+ *       exactly where child_w is NULL: the children are voxels, whose means nothing reads).  d_flag: device int32 zeroed by the
+ *       caller; a clamp sets bit 0 (a valid stream never clamps).
+ * pcc_raht_pred_mean / pcc_raht_pred_scale / pcc_raht_pred_predict  HOST: the kernels' own arithmetic for the CPU tests.  mean:
+ *                         *h_out = m before its clamp (|dc| <= 2^30, 1 <= w < 2^26).  scale: *h_out = P before its clamp (|pred|
+ *                         <= 2^24, 1 <= w < 2^26).  predict: *h_out = the prediction from h_means[8] (cell b = bx<<2 | by<<1 | bz,
+ *                         |mean| <= 2^24) and the presence mask 1..255.
+ * pcc_raht_pred_root      v_out[c] = quantise(v[c]) * step (clamped) and m_out[c] = its mean for the root of weight `weight`:
+ *                         the encoder hands in the true root DC, the decoder the header's q * step (which comes back unchanged).
+ * pcc_raht_pred_encode    coef rows of the level = quantise(h_true - Hp); child_v, child_m as the decoder will reconstruct them.
+ * pcc_raht_pred_inverse   child_v, child_m from v, m and the rows' symbols.
+ * ---------------------------------------------------------------------------------------- */
+int pcc_raht_pred_mean(int64_t dc, uint32_t w, int64_t* h_out);
+int pcc_raht_pred_scale(int64_t pred, uint32_t w, int64_t* h_out);
+int pcc_raht_pred_predict(const int32_t* h_means /*[8]*/, int32_t mask, int32_t* h_out);
+int pcc_raht_pred_root(const int32_t* v, int64_t weight, int32_t channels, const int32_t* h_steps, int32_t* v_out, int32_t* m_out,
+                       int32_t* d_flag, void* stream);
+int pcc_raht_pred_encode(const int64_t* keys, int64_t n, int32_t pitch, const uint64_t* bits, const int32_t* rank,
+                         const int32_t* h_grid, const int64_t* child_keys, int64_t n_child, const uint64_t* child_bits,
+                         const int32_t* child_rank, const int32_t* h_child, const int32_t* off, const int32_t* child_w /*nullable*/,
+                         const int32_t* v, const int32_t* m, int32_t channels, const int32_t* h_steps, const int32_t* h_true,
+                         int32_t* coef, int64_t row_base, int64_t rows_total, int32_t* child_v, int32_t* child_m /*nullable*/,
+                         int32_t* d_flag, void* stream);
+int pcc_raht_pred_inverse(const int64_t* keys, int64_t n, int32_t pitch, const uint64_t* bits, const int32_t* rank,
+                          const int32_t* h_grid, const int64_t* child_keys, int64_t n_child, const uint64_t* child_bits,
+                          const int32_t* child_rank, const int32_t* h_child, const int32_t* off, const int32_t* child_w /*nullable*/,
+                          const int32_t* v, const int32_t* m, int32_t channels, const int32_t* h_steps, const int32_t* coef,
+                          int64_t row_base, int64_t rows_total, int32_t* child_v, int32_t* child_m /*nullable*/, int32_t* d_flag,
+                          void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * 8f-3d lossless attribute coder over the same level sets: the levels, stages, slot pairs, rows and
  *       groups of 8f-3c (pcc_raht_mask / pcc_raht_weights / pcc_raht_index / pcc_raht_hist and pcc_geom_child_offsets serve both)
  *       with a reversible arithmetic.  Values are plain int32 levels [rows, channels], 1 <= channels <= 8: 0..255, and with

@@ -68,7 +68,7 @@ def scaled_voxels(cloud, position_scale):
 
 
 @torch.no_grad()
-def compress_anchor(cloud, qp, position_scale=1.0, chroma_qp_offset=-2, reference=None, attributes="intra", search=None):
+def compress_anchor(cloud, qp, position_scale=1.0, chroma_qp_offset=-2, reference=None, attributes="intra", search=None, predict=None):
     """[N, 6] GPU cloud (xyz, rgb in [0, 1]) -> bytes.  position_scale in (0, 1]: below 1 the points are scaled first; points
     that then share a cell are merged with their mean colour.  qp, chroma_qp_offset: `attributes.encode_attributes`.
     reference: voxels IN THE SCALED DOMAIN that `decompress_anchor` will be given too (the previous frame's decoded geometry,
@@ -76,7 +76,10 @@ def compress_anchor(cloud, qp, position_scale=1.0, chroma_qp_offset=-2, referenc
     colour ignores the reference; "auto" / "inter" -- the mode of `attributes.encode_attributes`, which then needs an [M, 6]
     reference of distinct scaled-domain integer voxels with rgb in [0, 1]: the previous frame AS DECODED
     (`compress_anchor_sequence` keeps that loop closed).  search: the block vectors' range, as in `geometry.encode_geometry`
-    (None, 2 .. 7 or "auto"); the colour coder uses the range the geometry stream ended with, 2 where it fell back to intra."""
+    (None, 2 .. 7 or "auto"); the colour coder uses the range the geometry stream ended with, 2 where it fell back to intra.
+    predict: the form of the intra colour stream, as in `attributes.encode_attributes` (None / False: 0xB3; True: 0xB9, coefficients
+    predicted from the parent level -- what `tmc3 --transformType=0` does with its intra prediction on; "auto": the shorter);
+    `decompress_anchor` reads either."""
     what = "compress_anchor"
     if attributes not in ("auto", "inter", "intra"):
         raise L.PccError(f"{what}: attributes {attributes!r} is not one of auto, inter, intra")
@@ -95,10 +98,10 @@ def compress_anchor(cloud, qp, position_scale=1.0, chroma_qp_offset=-2, referenc
     levels = torch.round(g.attrs.to(torch.float64) * 255.0).clamp_(0, 255).to(torch.uint8)
     geometry = encode_geometry(cs, reference=reference, search=search)
     if attributes == "intra":
-        colours = encode_attributes(cs, qp, chroma_qp_offset, attrs=levels)
+        colours = encode_attributes(cs, qp, chroma_qp_offset, attrs=levels, predict=predict)
     else:
         colours = encode_attributes(cs, qp, chroma_qp_offset, attrs=levels, reference=reference, mode=attributes,
-                                    search=stream_search(geometry))
+                                    search=stream_search(geometry), predict=predict)
     return HEADER.pack(MAGIC, scale, len(geometry)) + geometry + colours
 
 
@@ -131,20 +134,22 @@ def decompress_anchor(data, device, reference=None):
 
 
 @torch.no_grad()
-def compress_anchor_sequence(frames, qp, position_scale=1.0, chroma_qp_offset=-2, intra_period=32, search=None):
+def compress_anchor_sequence(frames, qp, position_scale=1.0, chroma_qp_offset=-2, intra_period=32, search=None, predict=None):
     """Frames ([N, 6] clouds as for `compress_anchor`) -> one stream per frame, closed loop: frame i is coded on its own when
     i % intra_period == 0, else against frame i - 1 AS DECODED -- its voxels in the scaled domain and its decoded colours --
     with geometry and colour both "auto".  The encoder decodes every stream it wrote to hold what the decoder will hold.
-    `decompress_anchor_sequence` returns the frames."""
+    predict: the form of every intra colour stream (the intra frames and the intra candidates of the others), as in
+    `compress_anchor`.  `decompress_anchor_sequence` returns the frames."""
     if int(intra_period) < 1:
         raise L.PccError(f"compress_anchor_sequence: intra_period {intra_period} is not positive")
     out, prev = [], None
     for i, frame in enumerate(frames):
         if i % int(intra_period) == 0:
-            out.append(compress_anchor(frame, qp, position_scale, chroma_qp_offset))
+            out.append(compress_anchor(frame, qp, position_scale, chroma_qp_offset, predict=predict))
             prev = None
         else:
-            out.append(compress_anchor(frame, qp, position_scale, chroma_qp_offset, reference=prev, attributes="auto", search=search))
+            out.append(compress_anchor(frame, qp, position_scale, chroma_qp_offset, reference=prev, attributes="auto", search=search,
+                                       predict=predict))
         _, cs, levels = _decode_anchor(out[-1], frame.device, prev)
         prev = _decoded_cloud(1.0, cs, levels)
     return out

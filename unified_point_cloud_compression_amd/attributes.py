@@ -12,6 +12,9 @@ this project's own stream: no G-PCC syntax and no bit-compatibility claim, the s
              (coded against a reference cloud the decoder holds, in the coefficient domain; no vector travels; "Inter frames" in 7f)
     wide:    u8 0xB8 | the 0xB4 layout byte for byte, search in 3 .. 7: the matches come from block vectors searched over
              [-search, search]^3 (`encode_attributes(..., search=)`; the decoder re-runs that search; 0xB4 itself reads 2 only)
+    predicted: u8 0xB9 | the 0xB3 layout byte for byte, n >= 2: every coefficient travels as quantise(H - Hp), Hp the transform of
+             a prediction of the node's children from the parent level as the decoder has reconstructed it
+             (`encode_attributes(..., predict=)`; "Prediction from the parent level" in 7f)
 
 The geometry is not in the stream: the decoder is handed it and refuses a stream whose n or depth differ from the set's.
 Level l of the transform is level l of the octree (`geometry.level_sets`); inside a node three stages of weighted Haar
@@ -25,7 +28,7 @@ parallel.  Everything on this side -- the steps, the family, the member choice, 
 There is no CPU fallback.  Device->host reads: encode 2 beyond building the level sets (the histograms with the root DC, the
 container); decode ONE at the end (the rANS status and the clamp flag; either raises PccError).  `parse_header` rejects a
 damaged stream on the host before any GPU work, and every buffer and launch is sized by the geometry set, never by the
-payload.  All six headers of this file are one layout with optional parts: the table `KINDS` says per magic byte which parts a
+payload.  All seven headers of this file are one layout with optional parts: the table `KINDS` says per magic byte which parts a
 stream has and what its fields may hold, `_parse` (behind `parse_header` and `parse_lossless_header`) reads it and `_stream`
 writes it.
 
@@ -62,6 +65,7 @@ QP_MIN, QP_MAX = 4, 51
 HEADER = struct.Struct("<BIBBBBb")
 INTER_LOSSY_MAGIC = 0xB4   # inter frames, format version 1: coefficients predicted from a reference cloud
 WIDE_LOSSY_MAGIC = 0xB8    # the 0xB4 layout byte for byte with the block vectors searched over +-3 .. +-7 (the header's search byte)
+PRED_MAGIC = 0xB9          # intra, the 0xB3 layout byte for byte: coefficients predicted from the parent level (closed loop)
 INTER_LOSSY_HEADER = struct.Struct("<BIBBBBbBBI")
 LOSSLESS_MAGIC = 0xB5      # the lossless coder (second half of this file), format version 1
 LOSSLESS_HEADER = struct.Struct("<BIBBB")
@@ -188,7 +192,7 @@ def _container_span(data, at, symbols, name):
 
 
 # ------------------------------------------------------------------------------------------------------------------------
-# the stream headers, host side: one table of the six streams, one reader, one writer
+# the stream headers, host side: one table of the seven streams, one reader, one writer
 # ------------------------------------------------------------------------------------------------------------------------
 def _check_range(name, block_log2, search, wide):
     """The block size and search range of an inter header: G.SEARCH under the narrow magic bytes, G.WIDE_SEARCH under the wide ones."""
@@ -223,6 +227,7 @@ _QP, _BLOCKS = ("qp", "chroma_qp_offset"), ("block_log2", "search", "blocks")
 _CODED = (0, F_COLOUR, F_PREDICT, F_PREDICT | F_COLOUR)
 KINDS = {
     MAGIC: _Kind(HEADER, _QP, "attribute stream", False, False, (0, F_COLOUR), 28, _dc_rule, 0),
+    PRED_MAGIC: _Kind(HEADER, _QP, "predicted attribute stream", False, False, (0, F_COLOUR), 28, _dc_rule, 0),
     INTER_LOSSY_MAGIC: _Kind(INTER_LOSSY_HEADER, _QP + _BLOCKS, "inter attribute stream", True, False, (0, F_COLOUR), 28, _dc_rule, 1),
     WIDE_LOSSY_MAGIC: _Kind(INTER_LOSSY_HEADER, _QP + _BLOCKS, "inter attribute stream", True, True, (0, F_COLOUR), 28, _dc_rule, 1),
     LOSSLESS_MAGIC: _Kind(LOSSLESS_HEADER, (), "lossless attribute stream", False, False, _CODED + (F_STORED,), 14, _root_rule, 0),
@@ -275,6 +280,10 @@ def _parse(data, have_reference, family, reads):
            "inter": kind.inter}
     if lossy:
         hdr.update(qp=f["qp"], chroma_qp_offset=f["chroma_qp_offset"], steps=steps_for(f["qp"], f["chroma_qp_offset"], ch))
+        if f["magic"] == PRED_MAGIC:                   # the only RAHT stream with this key: the others' results stay as they were
+            if n < 2:
+                raise L.PccError(f"{name}: header claims {n} points, a predicted stream codes 2 .. 2^26 - 1")
+            hdr["predict"] = True
     else:
         hdr.update(predict=bool(flags & F_PREDICT), stored=bool(flags & F_STORED), raw=None)
     if kind.inter:
@@ -331,11 +340,13 @@ def parse_header(data, have_reference=True):
     """{n, depth, channels, colour, qp, chroma_qp_offset, steps, dc (quantised root DC per channel), side (depth * 6 members),
     payload=(begin, end) or None, streams, inter}.  Raises PccError on a bad magic byte, on channels, qp or depth out of range,
     on a root DC or side byte out of range, on truncation, on trailing bytes and on a length that disagrees with the data --
-    before any GPU work.  An inter stream (0xB4, or 0xB8: the same layout searched over +-3 .. +-7) has inter=True, dc = the
-    quantised root DC residual, (depth + 1) * 6 side bytes and block_log2, search, blocks, modes=(begin, end) besides; refused
+    before any GPU work.  A predicted stream (0xB9: the 0xB3 layout) has predict=True besides, the only one with that key, and is
+    refused with fewer than two points.  An inter stream (0xB4, or 0xB8: the same layout searched over +-3 .. +-7) has
+    inter=True, dc = the quantised root DC residual, (depth + 1) * 6 side bytes and block_log2, search, blocks, modes=(begin, end) besides; refused
     for it as well: a block size or search range other than this build's, depth > 14, n < 2, a block count of 0 or above n, set
     padding bits of the mode bytes, and have_reference=False.  A 0xB5 .. 0xB7 stream is refused by its magic byte."""
-    return _parse(data, have_reference, (MAGIC, INTER_LOSSY_MAGIC, WIDE_LOSSY_MAGIC), f"{MAGIC:#x}, {INTER_LOSSY_MAGIC:#x} and {WIDE_LOSSY_MAGIC:#x}")
+    return _parse(data, have_reference, (MAGIC, INTER_LOSSY_MAGIC, WIDE_LOSSY_MAGIC, PRED_MAGIC),
+                  f"{MAGIC:#x}, {INTER_LOSSY_MAGIC:#x} and {WIDE_LOSSY_MAGIC:#x}")
 
 
 def parse_lossless_header(data, have_reference=True):
@@ -346,7 +357,7 @@ def parse_lossless_header(data, have_reference=True):
     before any GPU work.  An inter stream (0xB6, or 0xB7: the same layout searched over +-3 .. +-7) has inter=True,
     (depth + 1) * 6 side bytes and block_log2, search, blocks, modes=(begin, end) besides; refused for it as well: a block size
     or search range other than this build's, depth > 14, n < 2, a block count of 0 or above n, set padding bits of the mode
-    bytes, and have_reference=False.  A 0xB3, 0xB4 or 0xB8 stream is refused by its magic byte."""
+    bytes, and have_reference=False.  A 0xB3, 0xB4, 0xB8 or 0xB9 stream is refused by its magic byte."""
     return _parse(data, have_reference, (LOSSLESS_MAGIC, INTER_MAGIC, WIDE_MAGIC), f"{LOSSLESS_MAGIC:#x}")
 
 
@@ -536,6 +547,49 @@ def _rans_body(coef, idx, symbols, segment_symbols, dev, what, ph=None):
     return struct.pack("<I", nb) + host[8:8 + nb].tobytes()
 
 
+def _forward_pass(sets, offs, values, depth, ch, h_steps, coef, rows):
+    """The bottom-up pass of an intra stream, one launch per level: the rows of `coef` become quantise(H) under h_steps (every step
+    1: H itself).  Returns (the root's DC [1, C], int32 weights per level, None for the voxels)."""
+    dev = values.device
+    weights, v_child = [None] * (depth + 1), values
+    for l in range(depth - 1, -1, -1):
+        weights[l] = torch.empty(sets[l].n, dtype=torch.int32, device=dev)
+        v = torch.empty((sets[l].n, ch), dtype=torch.int32, device=dev)
+        L.call("pcc_raht_forward", *_level_args(sets[l], sets[l + 1]), L.ptr(offs[l]), L.ptr(weights[l + 1]), L.ptr(v_child), ch, h_steps,
+               L.ptr(weights[l]), L.ptr(v), L.ptr(coef), sets[l].n - 1, rows, L.stream())
+        v_child = v
+    return v_child, weights
+
+
+def _check_predict(what, predict):
+    if predict is not None and predict is not False and predict is not True and predict != "auto":
+        raise L.PccError(f"{what}: predict {predict!r} is not one of None, False, True, \"auto\"")
+    return predict or False
+
+
+def _predicted_rows(sets, offs, values, depth, ch, h_steps, rows):
+    """(symbol rows [rows, C] of a 0xB9 stream, the root's true DC [1, C]), rows >= 1.  Closed loop: the bottom-up pass with every
+    step 1 leaves the true H at the rows; then from the root down, one launch per level, `pcc_raht_pred_encode` forms Hp from the
+    level's DCs and means AS THE DECODER RECONSTRUCTS THEM, writes quantise(H - Hp) and rebuilds the children's DCs and means with
+    the decoder's own device function.  The clamp flag is not read: the encoder's values are within the quantisation error of the
+    source (DESIGN.md 7f bounds), and the decoder reads its own."""
+    dev, n = values.device, sets[depth].n
+    h_true = torch.zeros((rows, ch), dtype=torch.int32, device=dev)
+    v_root, weights = _forward_pass(sets, offs, values, depth, ch, (C.c_int32 * ch)(*([1] * ch)), h_true, rows)
+    coef = torch.zeros((rows, ch), dtype=torch.int32, device=dev)
+    d_flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    v = torch.empty((1, ch), dtype=torch.int32, device=dev)
+    m = torch.empty((1, ch), dtype=torch.int32, device=dev)
+    L.call("pcc_raht_pred_root", L.ptr(v_root), n, ch, h_steps, L.ptr(v), L.ptr(m), L.ptr(d_flag), L.stream())
+    for l in range(depth):
+        cv = torch.zeros((sets[l + 1].n, ch), dtype=torch.int32, device=dev)
+        cm = torch.empty((sets[l + 1].n, ch), dtype=torch.int32, device=dev) if l + 1 < depth else None    # nothing reads the voxels' means
+        L.call("pcc_raht_pred_encode", *_node_level_args(sets[l], sets[l + 1], l == 0), L.ptr(offs[l]), L.ptr(weights[l + 1]), L.ptr(v),
+               L.ptr(m), ch, h_steps, L.ptr(h_true), L.ptr(coef), sets[l].n - 1, rows, L.ptr(cv), L.ptr(cm), L.ptr(d_flag), L.stream())
+        v, m = cv, cm
+    return coef, v_root
+
+
 def _intra_tail(what, sets, masks, offs, checks, coef, v_root, depth, ch, rows, segment_symbols, dev, ph):
     """(root values as they are, side bytes, `u32 length | rANS container`) of an intra stream (0xB3, 0xB5) from the coded rows
     and the root's values: the groups, their histograms, the member choice (one read), the member index and the coder (one
@@ -569,11 +623,12 @@ def _inter_index(masks, offs, sets, depth, first, ch, bargs, d_mode, d_side, idx
                L.ptr(d_side), L.ptr(idx), L.ptr(coef_p), L.ptr(coef), sets[l].n - 1, rows, d_flag, L.stream())
 
 
-def _encode_inter_lossy(what, cs, levels, perm, ref, qp, cqo, colour, mode, segment_symbols, timings, search=G.SEARCH):
+def _encode_inter_lossy(what, cs, levels, perm, ref, qp, cqo, colour, mode, segment_symbols, timings, search=G.SEARCH, predict=False):
     """The inter half of `encode_attributes` (n >= 2, depth <= 14): the 0xB4 stream (0xB8 when `search` is above 2) and, for
     mode "auto", the 0xB3 stream from
-    the same forward pass; the shorter is returned, intra on a tie.  Device->host reads beyond the level sets: 2 for the inter
-    stream (modes, root DCs and histograms; the container), 2 more for the intra stream of "auto"."""
+    the same forward pass (predict True: the 0xB9 stream in its place, "auto": the shorter of those two, 0xB3 on a tie); the
+    shorter is returned, intra on a tie.  Device->host reads beyond the level sets: 2 for the inter stream (modes, root DCs and
+    histograms; the container), 2 more for every intra stream of "auto"."""
     n, ch, dev = cs.n, levels.shape[1], cs.device
     steps = steps_for(qp, cqo, ch)
     h_steps = (C.c_int32 * ch)(*steps)
@@ -633,21 +688,24 @@ def _encode_inter_lossy(what, cs, levels, perm, ref, qp, cqo, colour, mode, segm
                       root, side, modes, body)
         intra = None
         if mode == "auto":
-            dc, side0, body0 = _intra_tail(what, sets, masks, offs, checks, coef, v_child, depth, ch, rows, segment_symbols, dev, G.Phases(False))
-            intra = _stream(MAGIC, (n, depth, ch, int(colour), qp, cqo), [quantise(q, st) for q, st in zip(dc, steps)], side0, None, body0)
+            for magic in ([MAGIC] if not predict else [PRED_MAGIC] if predict is True else [MAGIC, PRED_MAGIC]):
+                sym, v_root = (coef, v_child) if magic == MAGIC else _predicted_rows(sets, offs, values, depth, ch, h_steps, rows)
+                dc, side0, body0 = _intra_tail(what, sets, masks, offs, checks, sym, v_root, depth, ch, rows, segment_symbols, dev, G.Phases(False))
+                data = _stream(magic, (n, depth, ch, int(colour), qp, cqo), [quantise(q, st) for q, st in zip(dc, steps)], side0, None, body0)
+                intra = data if intra is None or len(data) < len(intra) else intra
             ph.mark("intra_stream_ms")
         if timings is not None:
             torch.cuda.synchronize(dev)
             timings["inter_stages_ms"] = ph.report()
             timings["inter_bytes"], timings["intra_bytes"] = len(out), (len(intra) if intra is not None else None)
             timings["mode1_blocks"], timings["blocks"] = int(modes.sum()), nb
-            timings["host_reads_by_construction"] = 4 if mode == "auto" else 2   # beyond those of building the level sets
+            timings["host_reads_by_construction"] = (6 if predict == "auto" else 4) if mode == "auto" else 2   # beyond those of building the level sets
     return out if intra is None or len(out) < len(intra) else intra
 
 
 @torch.no_grad()
 def encode_attributes(cloud, qp, chroma_qp_offset=-2, colour=True, attrs=None, segment_symbols=SEGMENT_SYMBOLS, timings=None,
-                      reference=None, reference_attrs=None, mode="auto", search=None):
+                      reference=None, reference_attrs=None, mode="auto", search=None, predict=None):
     """[N, 6] GPU tensor (xyz, then rgb in [0, 1]: colours become round(255 c)), or a pitch-1 CoordSet / [N, >= 3] rows with
     `attrs` uint8 [N, C], 1 <= C <= 8 -> bytes.  Any row order (attributes follow their rows into canonical order; a set's
     attributes are in the set's order).  Duplicate voxels, CPU tensors and batched input raise PccError.  colour: the integer
@@ -660,8 +718,13 @@ def encode_attributes(cloud, qp, chroma_qp_offset=-2, colour=True, attrs=None, s
     (DESIGN.md 7f); "inter": the inter stream (fewer than two voxels still travel as intra; depth 15 raises); "intra", or no
     reference: today's stream byte for byte.  search: the range of the block vectors the inter stream's matches come from --
     None or 2: 0xB4 as ever; 3 .. 7: the stream 0xB8, the 0xB4 layout with that range in its header (no vector travels: the
-    decoder re-runs the wide search)."""
+    decoder re-runs the wide search).
+    predict: the form of the INTRA stream wherever one is produced (no reference, mode "intra", the intra candidate of mode
+    "auto"; the inter streams are untouched).  None / False: 0xB3, today's bytes; True: 0xB9, every coefficient predicted from
+    the parent level in a closed loop (fewer than two voxels still travel as 0xB3); "auto": the shorter of the two, 0xB3 on a
+    tie -- by stream length alone.  The closed loop costs a second pass over the levels; the decoder needs no argument."""
     what = "encode_attributes"
+    predict = _check_predict(what, predict)
     search = _colour_search(search, what)
     cs, levels, perm, ref, depth, inter = _encoder_input(what, cloud, attrs, reference, reference_attrs, mode, True, chroma_qp_offset)
     qp, cqo = min(max(int(qp), QP_MIN), QP_MAX), int(chroma_qp_offset)
@@ -670,7 +733,7 @@ def encode_attributes(cloud, qp, chroma_qp_offset=-2, colour=True, attrs=None, s
     if n == 0:
         return _stream(MAGIC, (0, 0, ch, int(colour), qp, cqo), [0] * ch)
     if inter:
-        return _encode_inter_lossy(what, cs, levels, perm, ref, qp, cqo, colour, mode, segment_symbols, timings, search)
+        return _encode_inter_lossy(what, cs, levels, perm, ref, qp, cqo, colour, mode, segment_symbols, timings, search, predict)
     steps = steps_for(qp, cqo, ch)
     h_steps = (C.c_int32 * ch)(*steps)
     rows = n - 1
@@ -682,22 +745,24 @@ def encode_attributes(cloud, qp, chroma_qp_offset=-2, colour=True, attrs=None, s
         L.call("pcc_raht_prepare", L.ptr(levels), L.ptr(perm), n, ch, int(colour), L.ptr(values), L.stream())
         masks, offs, checks = _plan(sets, depth, dev)
         ph.mark("prepare_plan")
-        coef = torch.zeros((max(rows, 1), ch), dtype=torch.int32, device=dev)
-        w_child, v_child = None, values
-        for l in range(depth - 1, -1, -1):
-            w = torch.empty(sets[l].n, dtype=torch.int32, device=dev)
-            v = torch.empty((sets[l].n, ch), dtype=torch.int32, device=dev)
-            L.call("pcc_raht_forward", *_level_args(sets[l], sets[l + 1]), L.ptr(offs[l]), L.ptr(w_child), L.ptr(v_child), ch, h_steps,
-                   L.ptr(w), L.ptr(v), L.ptr(coef), sets[l].n - 1, rows, L.stream())
-            w_child, v_child = w, v
-        ph.mark("forward")
-        root, side, body = _intra_tail(what, sets, masks, offs, checks, coef, v_child, depth, ch, rows, segment_symbols, dev, ph)
+        out = None
+        for magic in ([MAGIC] if not predict or not rows else [PRED_MAGIC] if predict is True else [MAGIC, PRED_MAGIC]):
+            if magic == MAGIC:
+                coef = torch.zeros((max(rows, 1), ch), dtype=torch.int32, device=dev)
+                v_root = _forward_pass(sets, offs, values, depth, ch, h_steps, coef, rows)[0]
+                ph.mark("forward")
+            else:
+                coef, v_root = _predicted_rows(sets, offs, values, depth, ch, h_steps, rows)
+                ph.mark("forward_predict")
+            root, side, body = _intra_tail(what, sets, masks, offs, checks, coef, v_root, depth, ch, rows, segment_symbols, dev, ph)
+            data = _stream(magic, (n, depth, ch, int(colour), qp, cqo), [quantise(q, st) for q, st in zip(root, steps)], side, None, body)
+            out = data if out is None or len(data) < len(out) else out
         if timings is not None:
             torch.cuda.synchronize(dev)
             timings["stages_ms"] = ph.report()
             timings["stages_ms"].setdefault("index_rans", 0.0)             # (a single voxel has no rows to code)
-            timings["host_reads_by_construction"] = 2 if rows else 1       # beyond those of building the level sets
-    return _stream(MAGIC, (n, depth, ch, int(colour), qp, cqo), [quantise(q, st) for q, st in zip(root, steps)], side, None, body)
+            timings["host_reads_by_construction"] = (4 if predict == "auto" else 2) if rows else 1   # beyond those of building the level sets
+    return out
 
 
 def _decoder_input(what, hdr, geometry, device, reference, reference_attrs):
@@ -759,9 +824,10 @@ def _decoder_read(what, name, left, status, checks, sets, ph, timings):
 def decode_attributes(data, geometry, device=None, reference=None, reference_attrs=None, timings=None):
     """bytes + the block's geometry (the pitch-1 CoordSet `decode_geometry(..., as_set=True)` returns, or [n, >= 3] rows) ->
     uint8 [n, C] in the canonical order `decode_geometry` returns.  device=None: the geometry's.  reference, reference_attrs:
-    the reference cloud `encode_attributes` was given; an inter stream (0xB4) needs it with its levels, an intra stream ignores
-    it.  The decoder re-runs the motion search and the matching, forms the prediction's transform from the reference it was
-    handed, compares the header's block count with the geometry's and sizes every buffer from the geometry.  Raises PccError on
+    the reference cloud `encode_attributes` was given; an inter stream (0xB4) needs it with its levels, an intra stream (0xB3, or
+    0xB9: coefficients predicted from the parent level, rebuilt level by level from the root) ignores it.  For an inter stream
+    the decoder re-runs the motion search and the matching, forms the prediction's transform from the reference it was handed,
+    compares the header's block count with the geometry's and sizes every buffer from the geometry.  Raises PccError on
     a malformed stream, on a stream whose n, depth or block count differ from the geometry's, and on a payload that does not
     decode; never returns anything but exactly [n, C].  timings: a dict that receives per-stage device events
     (tools/anchor_inter_timing.py); asking for them adds a synchronisation at the end."""
@@ -813,9 +879,19 @@ def decode_attributes(data, geometry, device=None, reference=None, reference_att
             R.decode(_tables(dev), d_buf, b1 - b0, idx, rows * ch, 1, 1, hdr["streams"], coef, status.data_ptr())
         ph.mark("index_rans_ms")
         v = torch.tensor([[q * s for q, s in zip(hdr["dc"], steps)]], dtype=torch.int32, device=dev)
+        predicted, m = bool(hdr.get("predict")), None
+        if predicted:                                       # 0xB9: the root's DC as it stands (q * step again) and its mean
+            root, m = v, torch.empty((1, ch), dtype=torch.int32, device=dev)
+            v = torch.empty((1, ch), dtype=torch.int32, device=dev)
+            L.call("pcc_raht_pred_root", L.ptr(root), n, ch, h_steps, L.ptr(v), L.ptr(m), status.data_ptr() + 4, L.stream())
         for l in range(depth):
             cv = torch.zeros((sets[l + 1].n, ch), dtype=torch.int32, device=dev)
-            if inter:
+            if predicted:
+                cm = torch.empty((sets[l + 1].n, ch), dtype=torch.int32, device=dev) if l + 1 < depth else None
+                L.call("pcc_raht_pred_inverse", *_node_level_args(sets[l], sets[l + 1], l == 0), L.ptr(offs[l]), L.ptr(weights[l + 1]), L.ptr(v),
+                       L.ptr(m), ch, h_steps, L.ptr(coef), sets[l].n - 1, rows, L.ptr(cv), L.ptr(cm), status.data_ptr() + 4, L.stream())
+                m = cm
+            elif inter:
                 L.call("pcc_raht_inter_inverse", *_level_args(sets[l], sets[l + 1]), L.ptr(offs[l]), L.ptr(weights[l + 1]), L.ptr(v),
                        L.ptr(p_root) if l == 0 else None, ch, h_steps, L.ptr(coef), L.ptr(hp), sets[l].n - 1, rows, L.ptr(cv),
                        status.data_ptr() + 4, L.stream())

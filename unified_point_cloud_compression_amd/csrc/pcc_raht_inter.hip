@@ -40,34 +40,6 @@ __device__ inline int raht_run_sum(int v, int end) {
   return v;
 }
 
-// the three stages of a node over one channel's child values x[8] (0 where absent): h[7] in row order (0 where the butterfly
-// does not exist); returns the node's DC.  The arithmetic of k_raht_forward.
-__device__ inline long long raht_node_fwd(const RahtNode& nd, const long long x[8], long long h[7]) {
-  long long y[4], u[2], dc;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {                       // absent values are 0: a lone sibling is the sum
-    h[3 + k] = 0;
-    if (nd.e[3 + k]) raht_fwd(nd.a[3 + k], nd.b[3 + k], x[2 * k], x[2 * k + 1], y[k], h[3 + k]);
-    else y[k] = x[2 * k] + x[2 * k + 1];
-  }
-#pragma unroll
-  for (int m = 0; m < 2; ++m) {
-    h[1 + m] = 0;
-    if (nd.e[1 + m]) raht_fwd(nd.a[1 + m], nd.b[1 + m], y[2 * m], y[2 * m + 1], u[m], h[1 + m]);
-    else u[m] = y[2 * m] + y[2 * m + 1];
-  }
-  h[0] = 0;
-  if (nd.e[0]) raht_fwd(nd.a[0], nd.b[0], u[0], u[1], dc, h[0]);
-  else dc = u[0] + u[1];
-  return dc;
-}
-
-__device__ inline int raht_quantise(long long h, long long step) {
-  const long long m = h < 0 ? -h : h;
-  const long long q = (m + (step >> 1)) / step;
-  return (int)(h < 0 ? -q : q);
-}
-
 // ---- kernels ---------------------------------------------------------------------------------------------------------------
 // sums [blocks, C + 1]: per channel the sum of the matched voxels' reference rows (|value| < 2^17, at most 4096 voxels: int32),
 // then their count

@@ -196,6 +196,14 @@ SIGNATURES = {
     "pcc_raht_inter_predict": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _i64, _i64, _p]),
     "pcc_raht_inter_inverse": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _i32, C.POINTER(_i32), _p, _p, _i64, _i64,
                                          _p, _p, _p]),
+    "pcc_raht_pred_mean": (C.c_int, [_i64, C.c_uint32, C.POINTER(_i64)]),
+    "pcc_raht_pred_scale": (C.c_int, [_i64, C.c_uint32, C.POINTER(_i64)]),
+    "pcc_raht_pred_predict": (C.c_int, [C.POINTER(_i32), _i32, C.POINTER(_i32)]),
+    "pcc_raht_pred_root": (C.c_int, [_p, _i64, _i32, C.POINTER(_i32), _p, _p, _p, _p]),
+    "pcc_raht_pred_encode": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _i32, C.POINTER(_i32), _p, _p, _i64,
+                                       _i64, _p, _p, _p, _p]),
+    "pcc_raht_pred_inverse": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _i32, C.POINTER(_i32), _p, _i64, _i64,
+                                        _p, _p, _p, _p]),
     "pcc_lift_pair": (C.c_int, [C.c_uint32, C.c_uint32, _i32, _i32, C.POINTER(_i64)]),
     "pcc_lift_predict": (C.c_int, [C.POINTER(_i32), _i32, C.POINTER(_i32)]),
     "pcc_lift_prepare": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p]),
