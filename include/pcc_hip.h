@@ -729,6 +729,27 @@ int pcc_geom_wide_pack(const int32_t* comps, int64_t n, int32_t search, int32_t*
 int pcc_geom_wide_unpack(const int32_t* disp, int64_t n, int32_t search, int32_t* comps, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 8f-3b** several references per frame (DESIGN.md section 7e "Several references", stream format 0xAB): every block takes its
+ *       prediction from one of n_slots (1..4) reference slots.  A slot is a reference set of 8f-3b': ref_keys[s], n_ref[s] (0: an
+ *       empty slot), and its pitch-1 grid index ref_bits[s] / ref_rank[s] / h_ref[s] (NULLs: binary search); the five arrays are
+ *       HOST arrays of n_slots entries.  Blocks, pyramids and the origin as in 8f-3b', vectors as packed displacements of 8f-3b*
+ *       with 1 <= search <= 7.  One wave per block; no atomics, integers only.
+ * pcc_geom_multi_block_bits
+ *   encoder form (cur_pyramid given): vecs[n_slots, n_blocks] holds every slot's own vector for every block.  For each slot in
+ *       order the slot's pyramid under its vector is built and its match count c = |finest tier AND cur_pyramid's| taken; the
+ *       block keeps the slot with the largest count, the LOWER slot on a tie.  Writes sel[b], disp[b] (the chosen slot's vector),
+ *       pyramid[b] (its pyramid) and, with counts non-NULL, counts[n_blocks, n_slots].
+ *   decoder form (cur_pyramid NULL): sel[n_blocks] is an INPUT and vecs[n_blocks] the one vector per block the stream carries;
+ *       pyramid[b] is the pyramid of slot sel[b] under vecs[b].  disp and counts are not used (counts must be NULL).
+ *   A selector outside 0 .. n_slots - 1 counts as slot 0, a displacement outside +-search as zero; either sets *d_bad.
+ * ---------------------------------------------------------------------------------------- */
+int pcc_geom_multi_block_bits(const int64_t* block_keys, int64_t n_blocks, int32_t block_log2, int32_t n_slots,
+                              const int64_t* const* ref_keys, const int64_t* n_ref, const uint64_t* const* ref_bits,
+                              const int32_t* const* ref_rank, const int32_t* const* h_ref, int32_t ox, int32_t oy, int32_t oz,
+                              const int32_t* vecs, int32_t search, const uint64_t* cur_pyramid /*nullable*/, int32_t* sel,
+                              int32_t* disp /*nullable*/, uint64_t* pyramid, int32_t* counts /*nullable*/, int32_t* d_bad, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * 8f-3b'' global motion of the inter coders (DESIGN.md section 7e "Global motion"; motion.py): one rigid transform per frame,
  *       applied to the reference before the block motion of 8f-3b'.
  *       The transform is 12 int32 on the HOST: M[3][3] row-major in Q24, then t[3] in Q8 voxels; |M_ij| <= PCC_MOTION_MAX_M,

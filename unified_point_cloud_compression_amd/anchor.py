@@ -32,7 +32,7 @@ from . import lib as L
 from . import sparse as S
 from .attributes import (INTER_LOSSY_MAGIC, INTER_MAGIC, WIDE_LOSSY_MAGIC, WIDE_MAGIC, decode_attributes, decode_attributes_lossless,
                          encode_attributes, encode_attributes_lossless)
-from .geometry import canonical_rows, decode_geometry, encode_geometry, stream_search, stream_transform
+from .geometry import canonical_rows, decode_geometry, encode_geometry, reference_slots, stream_search, stream_transform
 from .motion import warp_cloud
 from .voxelize import voxel_grid
 
@@ -183,6 +183,11 @@ def parse_lossless_container(data):
     return bytes(data[LOSSLESS_HEADER.size:LOSSLESS_HEADER.size + len_g]), bytes(data[LOSSLESS_HEADER.size + len_g:])
 
 
+def _first_cloud(reference, what):
+    """The cloud the colour coder sees of a `reference=` argument: the argument itself, or the first entry's cloud of a list."""
+    return reference_slots(reference, what)[0][0] if isinstance(reference, (list, tuple)) else reference
+
+
 def _has_colours(reference):
     return torch.is_tensor(reference) and reference.dim() == 2 and reference.shape[1] == 6
 
@@ -212,10 +217,14 @@ def compress_lossless(cloud, reference=None, attributes="intra", global_motion=N
     reference of distinct voxels and codes the colours against its colours.  global_motion: as in
     `geometry.encode_geometry` (None, "auto" or a RigidTransform); when the geometry comes out wrapped, the colours are coded
     against the warped reference.  search: the block vectors' range, as in `geometry.encode_geometry` (None, 2 .. 7 or "auto");
-    the colour coder uses the range the geometry stream ended with, 2 where it fell back to intra."""
+    the colour coder uses the range the geometry stream ended with, 2 where it fell back to intra.
+    reference may also be a list of 1..4 clouds or pairs (cloud, RigidTransform), as `geometry.encode_geometry` takes them
+    (global_motion must then be None): the geometry chooses among them per block, the colours see the first entry's cloud,
+    plain, exactly as if it were the only reference."""
     what = "compress_lossless"
     if attributes not in ("auto", "inter", "intra"):
         raise L.PccError(f"{what}: attributes {attributes!r} is not one of auto, inter, intra")
+    references, reference = reference, _first_cloud(reference, what)
     if attributes != "intra" and not _has_colours(reference):
         raise L.PccError(f"{what}: attributes={attributes!r} needs an [M, 6] reference cloud (xyz, rgb in [0, 1])")
     if not torch.is_tensor(cloud) or cloud.dim() != 2 or cloud.shape[1] != 6 or cloud.shape[0] == 0:
@@ -231,7 +240,7 @@ def compress_lossless(cloud, reference=None, attributes="intra", global_motion=N
         raise L.PccError(f"{what}: {cloud.shape[0] - cs.n} rows repeat a voxel; merge them first (voxelize.voxel_grid)")
     levels = torch.round(cloud[:, 3:6].to(torch.float64) * 255.0).clamp_(0, 255).to(torch.uint8)
     levels = (levels if perm is None else levels[perm]).contiguous()
-    geometry = encode_geometry(cs, reference=reference, global_motion=global_motion, search=search)
+    geometry = encode_geometry(cs, reference=references, global_motion=global_motion, search=search)
     if attributes == "intra":
         colours = encode_attributes_lossless(cs, attrs=levels)
     else:
@@ -244,40 +253,48 @@ def compress_lossless(cloud, reference=None, attributes="intra", global_motion=N
 def decompress_lossless(data, device, reference=None):
     """bytes -> [n, 6] float32 on `device` in canonical order: the exact coordinates, colours level / 255 (round(255 c) of
     them gives the levels back).  reference: the cloud `compress_lossless` was given; a stream whose colours are coded against
-    it (magic byte 0xB6 of the attribute part) raises PccError when the reference has no colours."""
+    it (magic byte 0xB6 of the attribute part) raises PccError when the reference has no colours.  A list, as
+    `compress_lossless` took it, goes to the geometry decoder; the colours see its first entry's cloud."""
     geometry, attributes = parse_lossless_container(data)
+    references, reference = reference, _first_cloud(reference, "decompress_lossless")
     inter = len(attributes) > 0 and attributes[0] in (INTER_MAGIC, WIDE_MAGIC)
     if inter and not _has_colours(reference):
         raise L.PccError("decompress_lossless: the colours are coded against a reference; an [M, 6] reference cloud is required")
-    cs = decode_geometry(geometry, device, as_set=True, reference=reference)
+    cs = decode_geometry(geometry, device, as_set=True, reference=references)
     levels = decode_attributes_lossless(attributes, cs, reference=_colour_reference(reference, geometry) if inter else None)
     rgb = levels.to(torch.float64) / torch.tensor(255.0, dtype=torch.float64, device=cs.device)
     return torch.cat([cs.coords()[:cs.n, 1:].to(torch.float64), rgb], dim=1).to(torch.float32)
 
 
 @torch.no_grad()
-def compress_lossless_sequence(frames, intra_period=32, global_motion=None, search=None):
+def compress_lossless_sequence(frames, intra_period=32, global_motion=None, search=None, references=1):
     """Frames ([N, 6] clouds as for `compress_lossless`) -> one stream per frame: frame i is coded on its own when
     i % intra_period == 0, else against frame i - 1 with geometry and colour both "auto" (lossless: the decoder holds the same
     frame) and `global_motion` as given.  Every stream decodes with `decompress_lossless(stream, device, reference=previous
-    frame)`."""
+    frame)`.  references=2: a frame whose two predecessors both lie inside its intra period codes its geometry against
+    [frame i - 1, frame i - 2] (global_motion must then be None) and decodes with that list; its colours see frame i - 1."""
     if int(intra_period) < 1:
         raise L.PccError(f"compress_lossless_sequence: intra_period {intra_period} is not positive")
-    out, prev = [], None
+    if references not in (1, 2) or (references == 2 and global_motion is not None):
+        raise L.PccError("compress_lossless_sequence: references is 1 or 2, and 2 goes with global_motion=None")
+    out, prev, prev2 = [], None, None
     for i, frame in enumerate(frames):
-        if i % int(intra_period) == 0:
+        at = i % int(intra_period)
+        if at == 0:
             out.append(compress_lossless(frame))
+        elif references == 2 and at >= 2:
+            out.append(compress_lossless(frame, reference=[prev, prev2], attributes="auto", search=search))
         else:
             out.append(compress_lossless(frame, reference=prev, attributes="auto", global_motion=global_motion, search=search))
-        prev = frame
+        prev, prev2 = frame, prev
     return out
 
 
 @torch.no_grad()
 def decompress_lossless_sequence(streams, device):
     """The streams of `compress_lossless_sequence` -> the frames, each [n, 6] float32 in canonical order."""
-    out, prev = [], None
+    out, prev, prev2 = [], None, None
     for data in streams:
-        prev = decompress_lossless(data, device, reference=prev)
+        prev, prev2 = decompress_lossless(data, device, reference=[prev, prev2] if prev2 is not None else prev), prev
         out.append(prev)
     return out

@@ -20,6 +20,24 @@ __device__ inline bool inter_has(const PccGrid& g, const int64_t* __restrict__ k
   return pcc_lookup(g, keys, n, pcc_key_pack(0, x, y, z)) >= 0;
 }
 
+// The finest tier of a block's pyramid, probed by one wave: word `lane` of tier bl in the LDS pyramid w gets bit `bit` = cell
+// c = 64 lane + bit = (lx << 2 bl | ly << bl | lz) of the block whose corner, already displaced, is (x0, y0, z0), set when the
+// source (sg, skeys, ns) holds that voxel.  Shared by the block-bits kernels of pcc_geom_inter.hip, pcc_geom_wide.hip and
+// pcc_geom_multi.hip -- as a statement macro, not a function: through a function (by reference, by value, returning the word) the
+// two older kernels came out with other scalar registers (tools/kernel_identity.py), and their instruction text is a record.
+// Declares cells, side, words and per in the caller's scope.
+#define INTER_PROBE_FINEST(w, lane, bl, sg, skeys, ns, x0, y0, z0)                                                                  \
+  const int cells = 1 << (3 * (bl)), side = (1 << (bl)) - 1;                                                                        \
+  const int words = cells > 64 ? cells >> 6 : 1, per = cells < 64 ? cells : 64;                                                     \
+  if ((lane) < words) {                                                                                                             \
+    unsigned long long m = 0;                                                                                                       \
+    for (int bit = 0; bit < per; ++bit) {                                                                                           \
+      const int c = (lane) * 64 + bit;                                                                                              \
+      if (inter_has(sg, skeys, ns, (x0) + (c >> (2 * (bl))), (y0) + ((c >> (bl)) & side), (z0) + (c & side))) m |= 1ull << bit;      \
+    }                                                                                                                               \
+    (w)[inter_tier(bl) + (lane)] = m;                                                                                               \
+  }
+
 // its row in the set (-1: absent, or a row the set does not have)
 __device__ inline int inter_row(const PccGrid& g, const int64_t* __restrict__ keys, int n, int x, int y, int z) {
   const int B = (int)PCC_BIAS;

@@ -125,16 +125,7 @@ __global__ void __launch_bounds__(64) k_wide_block_bits(const int64_t* __restric
   int dx, dy, dz;
   if (!wide_unpack(disp[b], search, dx, dy, dz) && lane == 0) atomicOr(d_bad, 1);
   const int x0 = ox + pcc_key_x(key) - dx, y0 = oy + pcc_key_y(key) - dy, z0 = oz + pcc_key_z(key) - dz;
-  const int cells = 1 << (3 * bl), side = (1 << bl) - 1;
-  const int words = cells > 64 ? cells >> 6 : 1, per = cells < 64 ? cells : 64;
-  if (lane < words) {
-    unsigned long long m = 0;
-    for (int bit = 0; bit < per; ++bit) {
-      const int c = lane * 64 + bit;
-      if (inter_has(sg, skeys, ns, x0 + (c >> (2 * bl)), y0 + ((c >> bl) & side), z0 + (c & side))) m |= 1ull << bit;
-    }
-    w[inter_tier(bl) + lane] = m;
-  }
+  INTER_PROBE_FINEST(w, lane, bl, sg, skeys, ns, x0, y0, z0)
   __syncthreads();
   for (int e = bl - 1; e >= 0; --e) {
     const int ce = 1 << (3 * e), se = (1 << e) - 1;

@@ -63,6 +63,21 @@ The stream behind the transform is coded against `motion.warp_cloud(reference, T
 (`pcc_motion_warp`).  `parse_header` checks the transform's ranges on the host; the decoder warps the reference rows as they
 come (no canonicalisation first: the set of warped cells does not depend on their order), which costs the one read the
 canonicalisation of the reference would have cost, and decodes the inner stream as before.
+
+Several references (`encode_geometry(x, reference=[r0, (r1, T), ...])`, DESIGN.md section 7e "Several references"): up to four
+reference slots, every block predicted from the slot that matches it best.
+
+    stream  = u8 0xAB | u8 K (2..4) | K x slot | inner
+    slot    = u8 source (an index into the clouds the decoder is handed) | u8 warped (0 / 1) | if warped: 12 x i32 transform
+    inner   = a complete 0xA8 or 0xAA stream, magic byte included, with the selector list immediately before the vector list
+    selectors = one slot number per block, in canonical order:
+              raw:    one byte each                                            (fewer than RAW_NODES blocks)
+              coded:  u8 m | m x (u8 slot, u32 count) ascending | u32 length | rANS container over `vector_table(hist)` of the K slots
+
+Every slot is searched as a single reference would be (a warped slot as `motion.warp_set(cloud, T)`); a block takes the slot
+with the most matches under that slot's vector, the lower slot on a tie, and lists that slot's vector.  The kernel is
+`pcc_geom_multi_block_bits` (csrc/pcc_geom_multi.hip); the selectors ride in the encoder's read of the raw levels' bytes, and the
+decoder's one read carries the selector list's rANS status and range flag.
 """
 import ctypes as C
 import itertools
@@ -142,6 +157,8 @@ SEARCH = 2                # vectors in [-2, 2]^3: 125 candidates, an index fits 
 MAX_SEARCH = 2
 MAGIC_WIDE = 0xAA         # the 0xA8 layout with search in WIDE_SEARCH and the vectors listed as displacements, per component
 WIDE_SEARCH = (3, 7)      # dx + 8 fits the 4 bits of a packed displacement, a window column of 16 + 2 * 7 z cells fits a word
+MAGIC_MULTI = 0xAB        # wrapper: u8 0xAB | u8 K | K slots | an 0xA8 or 0xAA stream with a selector list before its vector list
+MAX_SLOTS = 4
 HEADER_INTER = struct.Struct("<BIB3iBB")
 SIDE_INTER = struct.Struct("<8I9III")      # popcount classes of the absent nodes | distance classes of the present | children | length
 N_ROWS = 2 * N_CTX        # table rows: context + 64 * present
@@ -277,7 +294,70 @@ def _parse_vectors_wide(data, at, blocks, search):
     return {"raw": False, "payload": (at, at + nbytes), "hist": hists, "streams": streams}, at + nbytes
 
 
-def parse_header(data, have_reference=True):
+def _parse_selectors(data, at, blocks, k):
+    """The selector list of an 0xAB stream's inner stream, the layout of `_parse_vectors` over the k slots."""
+    if blocks < RAW_NODES:
+        if at + blocks > len(data):
+            raise L.PccError("geometry stream truncated inside the selector list")
+        if max(data[at:at + blocks]) >= k:
+            raise L.PccError(f"geometry stream: a selector outside the {k} reference slots")
+        return {"raw": True, "payload": (at, at + blocks), "hist": None, "streams": 0}, at + blocks
+    if at + 1 > len(data) or at + 1 + 5 * data[at] + 4 > len(data):
+        raise L.PccError("geometry stream truncated inside the selector histogram")
+    hist, last = [0] * k, -1
+    for j in range(data[at]):
+        i, c = struct.unpack_from("<BI", data, at + 1 + 5 * j)
+        if not last < i < k or c == 0:
+            raise L.PccError(f"geometry stream: the selector histogram lists the slots 0..{k - 1} in ascending order, each with a count")
+        hist[i], last = c, i
+    if sum(hist) != blocks:
+        raise L.PccError(f"geometry stream: the selector histogram counts {sum(hist)} of {blocks} blocks")
+    at += 1 + 5 * data[at]
+    nbytes = int.from_bytes(data[at:at + 4], "little")
+    at += 4
+    streams = _container_streams(data, at, nbytes, blocks, "the selector list")
+    return {"raw": False, "payload": (at, at + nbytes), "hist": hist, "streams": streams}, at + nbytes
+
+
+def _parse_multi(data, have_reference, clouds):
+    """The dictionary of an 0xAB stream: that of its inner stream with `slots` = [(source, RigidTransform or None)], `selectors`
+    and `inner`, the byte the payload spans count from."""
+    clouds = (1 if have_reference else 0) if clouds is None else int(clouds)
+    if not have_reference or clouds < 1:
+        raise L.PccError("geometry stream: a stream with several references (0xab) decodes against reference clouds, none was given")
+    if len(data) < 2:
+        raise L.PccError("geometry stream truncated inside the slot table")
+    k = data[1]
+    if not 2 <= k <= MAX_SLOTS:
+        raise L.PccError(f"geometry stream (0xab): {k} reference slots, this build reads 2..{MAX_SLOTS}")
+    at, slots = 2, []
+    for s in range(k):
+        if at + 2 > len(data):
+            raise L.PccError("geometry stream truncated inside the slot table")
+        source, warped = data[at], data[at + 1]
+        at += 2
+        if source >= clouds:
+            raise L.PccError(f"geometry stream (0xab): slot {s} names reference cloud {source}, {clouds} {'was' if clouds == 1 else 'were'} given")
+        if warped > 1:
+            raise L.PccError(f"geometry stream (0xab): slot {s} has the warped byte {warped}, this build reads 0 and 1")
+        T = None
+        if warped:
+            if at + M.PACKED.size > len(data):
+                raise L.PccError("geometry stream truncated inside the transform of a reference slot")
+            T = M.RigidTransform.unpack(data[at:at + M.PACKED.size])        # (refuses entries outside the ranges)
+            at += M.PACKED.size
+        slots.append((source, T))
+    if at >= len(data):
+        raise L.PccError("geometry stream truncated behind the slot table")
+    if data[at] not in (MAGIC_INTER, MAGIC_WIDE):
+        raise L.PccError(f"geometry stream (0xab): the stream behind the slot table has the magic byte {data[at]:#x}, not {MAGIC_INTER:#x} or "
+                         f"{MAGIC_WIDE:#x}")
+    hdr = parse_header(bytes(data[at:]), True, _selectors=k)
+    hdr.update(slots=slots, inner=at)
+    return hdr
+
+
+def parse_header(data, have_reference=True, clouds=None, _selectors=0):
     """Walk the stream on the host: {n, depth, origin, levels}; levels[l] = dict(nodes, children, raw, payload=(begin, end),
     pop).  An inter stream (0xA8, or 0xAA: the wide search, whose `vectors["hist"]` are three component histograms) adds
     inter=True, block_log2, search, first (the level of the blocks) and vectors = dict(raw,
@@ -285,7 +365,13 @@ def parse_header(data, have_reference=True):
     range, on an inter stream when the caller has no reference, on truncated or inconsistent side information and on trailing
     bytes -- before any GPU work.  A global-motion wrapper (0xA9) is refused without a reference too; its transform's ranges are
     checked here, the stream behind it is parsed as above (and must not be a wrapper again) and its dictionary is returned with
-    `transform` (a RigidTransform) and `inner` = 49, the byte the payload spans count from."""
+    `transform` (a RigidTransform) and `inner` = 49, the byte the payload spans count from.  A stream with several references
+    (0xAB) is refused without a reference, with a slot count outside 2..4, a slot whose `source` is not below `clouds` (the number
+    of reference clouds the caller holds; None: one when there is a reference), a warped byte above 1, a transform 0xA9 would
+    refuse or another magic byte than 0xA8 / 0xAA behind the slot table; its dictionary is that of the stream behind the table
+    with `slots` = [(source, RigidTransform or None)], `selectors` = dict(raw, payload, hist, streams) and `inner`."""
+    if len(data) >= 1 and data[0] == MAGIC_MULTI and not _selectors:
+        return _parse_multi(data, have_reference, clouds)
     if len(data) >= 1 and data[0] == MAGIC_GLOBAL:
         if not have_reference:
             raise L.PccError("geometry stream: a global-motion stream (0xa9) decodes against a reference cloud, none was given")
@@ -301,8 +387,8 @@ def parse_header(data, have_reference=True):
         raise L.PccError("geometry stream truncated inside the header")
     magic, n, depth, ox, oy, oz = HEADER.unpack_from(data, 0)
     if magic not in (MAGIC, MAGIC_INTER, MAGIC_WIDE):
-        raise L.PccError(f"geometry stream: magic byte {magic:#x}, this build reads {MAGIC:#x}, {MAGIC_INTER:#x}, {MAGIC_GLOBAL:#x} and "
-                         f"{MAGIC_WIDE:#x}")
+        raise L.PccError(f"geometry stream: magic byte {magic:#x}, this build reads {MAGIC:#x}, {MAGIC_INTER:#x}, {MAGIC_GLOBAL:#x}, "
+                         f"{MAGIC_WIDE:#x} and {MAGIC_MULTI:#x}")
     inter, wide = magic != MAGIC, magic == MAGIC_WIDE
     at, first, k, block_log2, search = HEADER.size, depth, 1, 0, 0
     if inter:
@@ -329,9 +415,11 @@ def parse_header(data, have_reference=True):
     reach = (1 << (depth - 1)) if depth > 1 else 0            # the largest cell has bit depth - 1 set (depth is minimal)
     if min(ox, oy, oz) < -S.BIAS + 64 or max(ox, oy, oz) + reach >= S.BIAS - 64:
         raise L.PccError(f"geometry stream: origin {(ox, oy, oz)} at depth {depth} leaves the 16-bit key range")
-    nodes, levels, vectors = 1, [], None
+    nodes, levels, vectors, selectors = 1, [], None, None
     for lvl in range(depth):
         if inter and lvl == first:
+            if _selectors:
+                selectors, at = _parse_selectors(data, at, nodes, _selectors)
             vectors, at = _parse_vectors_wide(data, at, nodes, search) if wide else _parse_vectors(data, at, nodes, k)
         if nodes < RAW_NODES:
             if at + nodes > len(data):
@@ -379,6 +467,8 @@ def parse_header(data, have_reference=True):
     hdr = {"n": n, "depth": depth, "origin": (ox, oy, oz), "levels": levels}
     if inter:                                  # (an intra stream's dictionary is what it always was)
         hdr.update(inter=True, block_log2=block_log2, search=search, first=first, vectors=vectors)
+    if _selectors:
+        hdr["selectors"] = selectors
     return hdr
 
 
@@ -474,13 +564,36 @@ def encode_geometry(x, segment_nodes=SEGMENT_NODES, timings=None, reference=None
     search (DESIGN.md section 7e "Wide search"): the range of the block vectors of an inter stream.  None or 2 -- [-2, 2]^3, the
     0xA8 stream, today's bytes.  3 .. 7 -- [-search, search]^3, the 0xAA stream.  "auto" -- coded at 2 and at 7, the shorter stream
     is kept, 2 on a tie; with mode "auto" that stream is then compared with the intra one as before, so a wider search never
-    costs bytes, only encode time.  0 and 1 are refused: the encoder has never written them."""
+    costs bytes, only encode time.  0 and 1 are refused: the encoder has never written them.
+    Several references (DESIGN.md section 7e "Several references"): reference may be a list or tuple of 1 .. 4 entries, each a
+    cloud or a pair (cloud, RigidTransform) -- that cloud warped; the transform travels in the stream.  A one-entry list is that
+    entry, a lone pair is the 0xA9 call; with a list global_motion must be None.  Two or more entries: every block takes the
+    entry that matches it best (stream 0xAB).  mode "inter" forces that stream; "auto" returns the shorter of it and of the same
+    call with the first entry alone, that one on a tie -- more references never cost bytes.  search "auto" codes the 0xAB stream
+    at 2 and at 7.  global_motion="both" with a single reference: shorthand for [reference, (reference, estimate_rigid(x,
+    reference))], the plain call when there is no estimate or it is the identity."""
     if mode not in ("auto", "inter", "intra"):
         raise L.PccError(f"encode_geometry: mode {mode!r} is not one of auto, inter, intra")
     search = check_search(search, "encode_geometry")
-    if not (global_motion is None or isinstance(global_motion, M.RigidTransform) or (isinstance(global_motion, str) and global_motion == "auto")):
-        raise L.PccError(f"encode_geometry: global_motion {global_motion!r} is not None, \"auto\" or a RigidTransform")
+    if not (global_motion is None or isinstance(global_motion, M.RigidTransform) or (isinstance(global_motion, str) and global_motion in ("auto", "both"))):
+        raise L.PccError(f"encode_geometry: global_motion {global_motion!r} is not None, \"auto\", \"both\" or a RigidTransform")
     cs = _input_set(x)
+    if isinstance(reference, (list, tuple)):
+        slots = reference_slots(reference, "encode_geometry")
+        if global_motion is not None:
+            raise L.PccError("encode_geometry: with a list of references global_motion must be None (a transform travels with its entry: "
+                             "(cloud, RigidTransform))")
+        if len(slots) == 1:                            # a one-entry list is that entry; a lone pair is the 0xA9 call
+            return encode_geometry(cs, segment_nodes, timings, slots[0][0], mode, slots[0][1], search)
+        return _encode_multi(cs, slots, mode, segment_nodes, timings, search)
+    if isinstance(global_motion, str) and global_motion == "both":
+        if reference is None or mode == "intra" or cs.n == 0:
+            return _encode(cs, INTRA, segment_nodes, timings)
+        rs = reference_set(reference)
+        T = M.estimate_rigid(cs, rs) if rs is not None else None
+        if T is None or T.is_identity():
+            return _encode_against(cs, rs, mode, segment_nodes, timings, search)
+        return _encode_multi(cs, [(rs, None), (rs, T)], mode, segment_nodes, timings, search)
     if isinstance(global_motion, M.RigidTransform):
         if reference is None:
             raise L.PccError("encode_geometry: a global motion transform needs the reference it moves")
@@ -514,6 +627,144 @@ def _encode_global(cs, rs, T, mode, segment_nodes, timings, search=SEARCH):
     return bytes([MAGIC_GLOBAL]) + T.pack() + inner
 
 
+def _is_pair(entry):
+    return isinstance(entry, tuple) and len(entry) == 2 and isinstance(entry[1], M.RigidTransform)
+
+
+def reference_slots(reference, what):
+    """[(cloud, RigidTransform or None)] of a `reference=` argument: a cloud, a pair (cloud, RigidTransform) -- that cloud warped --
+    or a list / tuple of 1..MAX_SLOTS of either."""
+    if _is_pair(reference):
+        return [(reference[0], reference[1])]
+    if not isinstance(reference, (list, tuple)):
+        return [(reference, None)]
+    if not 1 <= len(reference) <= MAX_SLOTS:
+        raise L.PccError(f"{what}: a list of references holds 1..{MAX_SLOTS} entries, got {len(reference)}")
+    slots = []
+    for e in reference:
+        if _is_pair(e):
+            slots.append((e[0], e[1]))
+        elif e is None or isinstance(e, (list, tuple)):
+            raise L.PccError(f"{what}: an entry of a list of references is a cloud or a pair (cloud, RigidTransform)")
+        else:
+            slots.append((e, None))
+    return slots
+
+
+def slot_sources(slots):
+    """(the distinct clouds of the slots in order of first appearance, the index of each slot's cloud among them): entries that
+    are the same object share a source, so `[r, (r, T)]` decodes against `r` alone and against the same list alike."""
+    clouds, sources = [], []
+    for cloud, _ in slots:
+        at = next((i for i, c in enumerate(clouds) if c is cloud), len(clouds))
+        if at == len(clouds):
+            clouds.append(cloud)
+        sources.append(at)
+    return clouds, sources
+
+
+def _slot_sets(slots, what):
+    """(the reference set of every slot -- None: empty --, its source): each distinct cloud canonicalised once, a warped slot
+    through `motion.warp_set` of that set."""
+    clouds, sources = slot_sources(slots)
+    plain = [reference_set(c, what) for c in clouds]
+    sets = []
+    for (_, T), src in zip(slots, sources):
+        rs = plain[src]
+        if T is not None and rs is not None:
+            rs = M.warp_set(rs, T)
+            rs = rs if rs.n else None
+        sets.append(rs)
+    return sets, sources
+
+
+def _encode_multi(cs, slots, mode, segment_nodes, timings, search):
+    """`encode_geometry` with two or more reference slots [(cloud, RigidTransform or None)]: the 0xAB stream under mode "inter",
+    the shorter of it and of the same call with the first entry alone under "auto" (that entry on a tie)."""
+    if mode == "intra" or cs.n == 0:
+        return _encode(cs, INTRA, segment_nodes, timings)
+    sets, sources = _slot_sets(slots, "encode_geometry")
+    head = bytearray([MAGIC_MULTI, len(slots)])
+    for (_, T), src in zip(slots, sources):
+        head += bytes([src, 0 if T is None else 1]) + (b"" if T is None else T.pack())
+    if search == "auto":
+        multi = _encode(cs, sets, segment_nodes, timings)
+        tw = {} if timings is not None else None
+        widest = _encode(cs, sets, segment_nodes, tw, WIDE_SEARCH[1])
+        if len(widest) < len(multi):
+            multi = widest
+            if timings is not None:
+                timings.clear()
+                timings.update(tw)
+    else:
+        multi = _encode(cs, sets, segment_nodes, timings, search)
+    multi = bytes(head) + multi
+    if mode == "inter":
+        return multi
+    cloud, T = slots[0]
+    single = encode_geometry(cs, segment_nodes, None, cloud, mode, T, search)
+    if timings is not None:
+        timings["multi_bytes"], timings["single_bytes"] = len(multi), len(single)
+    return multi if len(multi) < len(single) else single
+
+
+def multi_prediction(cs, sets, origin, depth, level_sets_=None, search=SEARCH, counts=False):
+    """(blocks set, block_log2 of this cloud, int32 slot per block, int32 packed displacement per block, the predicted pyramids,
+    int32 match counts [blocks, slots] or None) of the canonical set `cs` against the reference sets `sets` (None: an empty slot):
+    every slot searched by `pcc_geom_wide_motion` -- for search <= 2 the vector `pcc_geom_inter_motion` picks --, the slot chosen
+    per block by `pcc_geom_multi_block_bits`."""
+    lib = L.load()
+    dev = cs.device
+    lv = level_sets(cs, origin, depth) if level_sets_ is None else level_sets_
+    first = max(0, depth - BLOCK_LOG2)
+    bl = depth - first
+    blocks, voxels = lv[first], lv[depth]
+    nb, k = blocks.n, len(sets)
+    pw = lib.pcc_geom_inter_pyramid_words()
+    cur = torch.empty(nb * pw, dtype=torch.int64, device=dev)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    L.call("pcc_geom_inter_block_bits", L.ptr(blocks.keys), nb, bl, L.ptr(voxels.keys), voxels.n,
+           *S.grid_args(voxels.grid() if S.USE_GRID else None), 0, 0, 0, None, SEARCH, L.ptr(cur), L.ptr(bad), L.stream())
+    vecs = torch.empty((k, nb), dtype=torch.int32, device=dev)
+    for s, rs in enumerate(sets):
+        L.call("pcc_geom_wide_motion", L.ptr(blocks.keys), nb, bl, L.ptr(cur), *ref_args(rs), *origin, search, None,
+               vecs.data_ptr() + 4 * s * nb, L.stream())
+    sel = torch.empty(nb, dtype=torch.int32, device=dev)
+    disp = torch.empty(nb, dtype=torch.int32, device=dev)
+    pred = torch.empty(nb * pw, dtype=torch.int64, device=dev)
+    cnt = torch.empty((nb, k), dtype=torch.int32, device=dev) if counts else None
+    multi_block_bits(blocks.keys, nb, bl, sets, origin, vecs, search, cur, sel, disp, pred, cnt, L.ptr(bad))
+    return blocks, bl, sel, disp, pred, cnt
+
+
+def multi_block_bits(bkeys, nb, bl, sets, origin, vecs, search, cur, sel, disp, pred, counts, bad_ptr):
+    """One launch of `pcc_geom_multi_block_bits` over the reference sets `sets` (None: an empty slot); cur None: the decoder form."""
+    k = len(sets)
+    args = [ref_args(rs) for rs in sets]
+    hs = [a[4] for a in args]                                         # (the host headers stay alive until the call returns)
+    L.call("pcc_geom_multi_block_bits", L.ptr(bkeys), nb, bl, k,
+           (C.c_void_p * k)(*[a[0] for a in args]), (C.c_int64 * k)(*[a[1] for a in args]), (C.c_void_p * k)(*[a[2] for a in args]),
+           (C.c_void_p * k)(*[a[3] for a in args]), (C.c_void_p * k)(*[None if h is None else C.addressof(h) for h in hs]),
+           *origin, L.ptr(vecs), search, L.ptr(cur), L.ptr(sel), L.ptr(disp), L.ptr(pred), L.ptr(counts), bad_ptr, L.stream())
+
+
+_DISP_LUT = {}
+
+
+def _disp_luts(dev):
+    """(int32 [4096] packed displacement -> index into candidates(SEARCH), int32 [256] index -> packed displacement) on `dev`.
+    An index the table does not hold maps to a word no range accepts, which `pcc_geom_multi_block_bits` flags."""
+    key = str(dev)
+    if key not in _DISP_LUT:
+        packed = [(dx + 8) | ((dy + 8) << 4) | ((dz + 8) << 8) for dx, dy, dz in candidates(SEARCH)]
+        to_index = np.zeros(4096, dtype=np.int32)
+        to_index[packed] = np.arange(len(packed), dtype=np.int32)
+        to_disp = np.full(256, 1 << 12, dtype=np.int32)
+        to_disp[:len(packed)] = packed
+        _DISP_LUT[key] = (torch.from_numpy(to_index).to(dev), torch.from_numpy(to_disp).to(dev))
+    return _DISP_LUT[key]
+
+
 def check_search(search, what):
     """The search range an encoder was asked for: SEARCH for None, an int in 2 .. 7, or "auto" (shared with attributes.py)."""
     if search is None:
@@ -526,10 +777,20 @@ def check_search(search, what):
     return search
 
 
+def _multi_inner(data):
+    """The byte an 0xAB stream's inner stream begins at (0 for any other stream); nothing is validated here."""
+    if len(data) < 2 or data[0] != MAGIC_MULTI:
+        return 0
+    at = 2
+    for _ in range(data[1]):
+        at += 2 + (M.PACKED.size if at + 1 < len(data) and data[at + 1] == 1 else 0)
+    return at
+
+
 def stream_search(data):
     """The search range a geometry stream ended with: its header's byte for an inter stream (0xA8 / 0xAA, also behind a global-motion
-    wrapper), SEARCH for an intra one -- the range a colour coder that follows the geometry uses."""
-    at = GLOBAL_HEADER if len(data) >= 1 and data[0] == MAGIC_GLOBAL else 0
+    wrapper or the slot table of 0xAB), SEARCH for an intra one -- the range a colour coder that follows the geometry uses."""
+    at = GLOBAL_HEADER if len(data) >= 1 and data[0] == MAGIC_GLOBAL else _multi_inner(data)
     if len(data) >= at + HEADER_INTER.size and data[at] in (MAGIC_INTER, MAGIC_WIDE):
         return data[at + HEADER_INTER.size - 1]
     return SEARCH
@@ -617,13 +878,15 @@ INTRA = object()          # `_encode(cs, INTRA, ...)`: no reference at all (None
 
 def _encode(cs, rs, segment_nodes, timings, search=SEARCH):
     """The stream of the canonical set `cs`: intra (0xA7) when `rs` is INTRA, else inter (0xA8; 0xAA when `search` is above 2)
-    against the reference set `rs` (None: empty).  One walk over the levels: those above `first` (= depth for an intra stream) take the intra kernels, the
+    against the reference set `rs` (None: empty).  A LIST of reference sets: the inner stream of 0xAB, every block predicted from
+    the set `pcc_geom_multi_block_bits` chose for it, the selector list in front of the vector list.  One walk over the levels: those above `first` (= depth for an intra stream) take the intra kernels, the
     others the inter ones.  Device->host reads: bounds, level sizes, every level's histograms, the raw levels' bytes (an inter
     stream's vectors ride in that read), the payload."""
     n = cs.n
     if n == 0:
         return HEADER.pack(MAGIC, 0, 0, 0, 0, 0)
     inter = rs is not INTRA
+    multi = isinstance(rs, list)                                         # the inner stream of 0xAB: one reference set per slot
     origin = tuple(cs.bounds.lo)
     depth = max(1, max(cs.bounds.hi[i] - origin[i] for i in range(3)).bit_length())
     first = max(0, depth - BLOCK_LOG2) if inter else depth
@@ -646,13 +909,20 @@ def _encode(cs, rs, segment_nodes, timings, search=SEARCH):
         words = [lib.pcc_geom_hist_words()] * first
         nb = 0
         if inter:
-            blocks, bl, _, vec = motion_vectors(cs, rs, origin, depth, sets, search=search)
-            ph.mark("motion_search_ms")
-            nb = blocks.n
+            if multi:                                                   # per slot a search, per block the best slot and its pyramid
+                blocks, bl, sel, vec, pred, _ = multi_prediction(cs, rs, origin, depth, sets, search)
+                ph.mark("motion_search_ms")
+                nb = blocks.n
+                if not wide:                                            # what an 0xA8 vector list codes: indices
+                    vec = _disp_luts(dev)[0][vec.long()]
+            else:
+                blocks, bl, _, vec = motion_vectors(cs, rs, origin, depth, sets, search=search)
+                ph.mark("motion_search_ms")
+                nb = blocks.n
+                pred = torch.empty(nb * lib.pcc_geom_inter_pyramid_words(), dtype=torch.int64, device=dev)
+                L.call("pcc_geom_wide_block_bits" if wide else "pcc_geom_inter_block_bits", L.ptr(blocks.keys), nb, bl, *ref_args(rs), *origin,
+                       L.ptr(vec), search, L.ptr(pred), L.ptr(bad), L.stream())
             bgrid = blocks.grid() if (first and S.USE_GRID) else None
-            pred = torch.empty(nb * lib.pcc_geom_inter_pyramid_words(), dtype=torch.int64, device=dev)
-            L.call("pcc_geom_wide_block_bits" if wide else "pcc_geom_inter_block_bits", L.ptr(blocks.keys), nb, bl, *ref_args(rs), *origin,
-                   L.ptr(vec), search, L.ptr(pred), L.ptr(bad), L.stream())
             if wide:                                                    # what the vector list codes: [blocks, 3] components
                 disp, vec = vec, torch.empty(3 * nb, dtype=torch.int32, device=dev)
                 L.call("pcc_geom_wide_unpack", L.ptr(disp), nb, search, L.ptr(vec), L.stream())
@@ -679,8 +949,8 @@ def _encode(cs, rs, segment_nodes, timings, search=SEARCH):
         ph.mark("symbols_hist_ms")
         h_hist = hist.cpu().numpy().astype(np.int64)                       # one read: every level's histograms
         raw_lv = [l for l in range(depth) if nodes[l] < RAW_NODES]
-        parts = [(sym if l < first else byte)[at[l]:at[l + 1]] for l in raw_lv] + ([vec] if inter else [])
-        raw_bytes, h_vec = {}, None
+        parts = [(sym if l < first else byte)[at[l]:at[l + 1]] for l in raw_lv] + ([vec] if inter else []) + ([sel] if multi else [])
+        raw_bytes, h_vec, h_sel = {}, None, None
         if parts:
             got = torch.cat(parts).to(torch.uint8).cpu().numpy()           # one read: the raw levels' bytes and the vectors
             p = 0
@@ -688,12 +958,16 @@ def _encode(cs, rs, segment_nodes, timings, search=SEARCH):
                 raw_bytes[l] = got[p:p + nodes[l]].tobytes()
                 p += nodes[l]
             h_vec = got[p:p + per * nb]
+            h_sel = got[p + per * nb:p + per * nb + nb] if multi else None
         # containers: the vector list (when it is coded) and the coded levels, tables from the levels before, one rANS launch each
         # into a shared blob [sizes | containers]
         code_vec = inter and k_vec > 1 and nb >= RAW_NODES
         symbols = {l: nodes[l] for l in range(depth) if nodes[l] >= RAW_NODES}
         if code_vec:
             symbols = {"vec": per * nb, **symbols}
+        code_sel = multi and nb >= RAW_NODES
+        if code_sel:
+            symbols = {"sel": nb, **symbols}
         jobs = list(symbols)
         plans = {j: R.Plan(symbols[j], 1, 1, segments_for(symbols[j], segment_nodes)) for j in jobs}
         caps = {j: R.align8(plans[j].capacity) for j in jobs}
@@ -710,6 +984,12 @@ def _encode(cs, rs, segment_nodes, timings, search=SEARCH):
             where[job] = (begin, caps[job])
             begin += caps[job]
 
+        if code_sel:
+            s_hist = np.bincount(h_sel, minlength=len(rs))
+            s_idx = torch.zeros(nb, dtype=torch.int32, device=dev)
+            keep.append(s_idx)
+            run("sel", R.fresh_cdf_tables(f"geometry_selectors{len(rs)}", dev, vector_table(s_hist), np.full(1, len(rs) + 2, dtype=np.int32),
+                                          np.zeros(1, dtype=np.int32)), L.ptr(sel), L.ptr(s_idx))
         if code_vec:
             v_hist = [np.bincount(h_vec[c::per], minlength=k_vec) for c in range(per)]
             v_idx = torch.arange(per * nb, dtype=torch.int32, device=dev) % per        # table row = component (one row: an index)
@@ -746,6 +1026,13 @@ def _encode(cs, rs, segment_nodes, timings, search=SEARCH):
     out = bytearray(HEADER_INTER.pack(MAGIC_WIDE if wide else MAGIC_INTER, n, depth, *origin, BLOCK_LOG2, search) if inter
                     else HEADER.pack(MAGIC, n, depth, *origin))
     for l in range(depth):
+        if l == first and code_sel:
+            body = container("sel")
+            occ = np.flatnonzero(s_hist)
+            out += struct.pack("<B", len(occ)) + b"".join(struct.pack("<BI", int(i), int(s_hist[i])) for i in occ)
+            out += struct.pack("<I", len(body)) + body
+        elif l == first and multi:
+            out += h_sel.tobytes()
         if l == first and k_vec > 1:
             if code_vec:
                 body = container("vec")
@@ -801,10 +1088,10 @@ def _canonical_children(keys, n, pitch, depth_level, dev, counts_ptr):
     return out, None
 
 
-def _payloads(data, levels, vectors=None, blocks=0):
+def _payloads(data, levels, vectors=None, blocks=0, selectors=None):
     """Host buffers for ONE upload each: the coded levels' rANS containers (`rans.stage`) and the raw levels' bytes as int32
     symbols.  An inter stream's vector list rides as the job "vec": its container when it is coded, else one index per block
-    behind the raw levels' bytes (zeros when the stream carries none)."""
+    behind the raw levels' bytes (zeros when the stream carries none); an 0xAB stream's selector list likewise as "sel"."""
     jobs = [l for l, lv in enumerate(levels) if not lv["raw"]]
     spans = [levels[l]["payload"] for l in jobs]
     raw_at, raw = {}, []
@@ -818,6 +1105,11 @@ def _payloads(data, levels, vectors=None, blocks=0):
         raw.extend(data[b0:b1] if b1 > b0 else [0] * blocks)               # (one index, or three components, per block)
     elif vectors is not None:
         jobs, spans = jobs + ["vec"], spans + [vectors["payload"]]
+    if selectors is not None and selectors["raw"]:                         # (an 0xAB stream's selector list rides the same way: "sel")
+        raw_at["sel"] = len(raw)
+        raw.extend(data[selectors["payload"][0]:selectors["payload"][1]])
+    elif selectors is not None:
+        jobs, spans = jobs + ["sel"], spans + [selectors["payload"]]
     buf, offsets = R.stage(data, spans)
     return buf, dict(zip(jobs, offsets)), np.asarray(raw, dtype=np.int32), raw_at          # (level 0 is one node: always raw)
 
@@ -839,7 +1131,9 @@ def _decode(hdr, data, dev, rs, as_set, timings):
     with torch.cuda.device(dev):
         ph.mark()
         vh, nb = (hdr["vectors"], levels[first]["nodes"]) if inter else (None, 0)
-        h_buf, where, h_raw, raw_at = _payloads(data, levels, vh, nb)
+        sh = hdr.get("selectors")                                          # an 0xAB stream: `rs` is the list of its slots' reference sets
+        multi = sh is not None
+        h_buf, where, h_raw, raw_at = _payloads(data, levels, vh, nb, sh)
         d_buf, d_raw = torch.from_numpy(h_buf).to(dev), torch.from_numpy(h_raw).to(dev)
         const = R.fixed_tables("geometry", dev, None, TABLE_SIZES, TABLE_OFFSETS)
         # the level's cdf and decoder blob are derived on the device (`pcc_geom_tables`), in place, before each coded level
@@ -859,8 +1153,8 @@ def _decode(hdr, data, dev, rs, as_set, timings):
         h_at = [0, *itertools.accumulate(words)]
         hist = torch.zeros(h_at[-1], dtype=torch.int32, device=dev)
         # per level: status | bad byte | child total (i64) | distinct, off-lattice (i64 x 2); an inter stream's row `depth`: the
-        # vector list's status | bad index
-        flags = torch.zeros((depth + inter, 8), dtype=torch.int32, device=dev)
+        # vector list's status | bad index; an 0xAB stream's row `depth + 1`: the selector list's status | selector or vector out of range
+        flags = torch.zeros((depth + inter + multi, 8), dtype=torch.int32, device=dev)
         keys = torch.tensor([_key_of(0, 0, 0)], dtype=torch.int64, device=dev)
         grid, by_grid = None, []
         for l, lv in enumerate(levels):
@@ -886,8 +1180,24 @@ def _decode(hdr, data, dev, rs, as_set, timings):
                     L.call("pcc_geom_wide_pack", L.ptr(comps), nb, search, L.ptr(vec), vp + 4, L.stream())
                 bkeys, bgrid = keys, grid
                 pred = torch.empty(nb * lib.pcc_geom_inter_pyramid_words(), dtype=torch.int64, device=dev)
-                L.call("pcc_geom_wide_block_bits" if wide else "pcc_geom_inter_block_bits", L.ptr(bkeys), nb, bl, *ref_args(rs), *origin,
-                       L.ptr(vec), search, L.ptr(pred), vp + 4, L.stream())
+                if multi:
+                    mp = flags.data_ptr() + 32 * (depth + 1)
+                    if sh["raw"]:
+                        sel = d_raw[raw_at["sel"]:raw_at["sel"] + nb].contiguous()
+                    else:
+                        s_cdf, s_sizes = vector_table(sh["hist"]), np.full(1, len(rs) + 2, dtype=np.int32)
+                        s_const = R.fixed_tables(f"geometry_selectors{len(rs)}", dev, None, s_sizes, np.zeros(1, dtype=np.int32))
+                        st = R.Tables(torch.from_numpy(s_cdf).to(dev), s_const.sizes, s_const.offsets,
+                                      dec=torch.from_numpy(R._dec_blob(s_cdf, s_sizes)).to(dev))
+                        sel = torch.empty(nb, dtype=torch.int32, device=dev)
+                        R.decode(st, d_buf.data_ptr() + where["sel"], sh["payload"][1] - sh["payload"][0],
+                                 torch.zeros(nb, dtype=torch.int32, device=dev), nb, 1, 1, sh["streams"], sel, mp)
+                    if not wide:                                        # indices -> displacements; one outside the table: a word the kernel flags
+                        vec = _disp_luts(dev)[1][vec.clamp(0, 255).long()]
+                    multi_block_bits(bkeys, nb, bl, rs, origin, vec.contiguous(), search, None, sel, None, pred, None, mp + 4)
+                else:
+                    L.call("pcc_geom_wide_block_bits" if wide else "pcc_geom_inter_block_bits", L.ptr(bkeys), nb, bl, *ref_args(rs), *origin,
+                           L.ptr(vec), search, L.ptr(pred), vp + 4, L.stream())
                 ph.mark("vectors_compensation_ms")
             if l < first:
                 ctx = torch.empty(m, dtype=torch.int32, device=dev)
@@ -950,6 +1260,9 @@ def _decode(hdr, data, dev, rs, as_set, timings):
         fl = back[:p].reshape(-1, 8)
         if inter and (fl[depth, 0] != 0 or fl[depth, 1] != 0):
             raise L.PccError(f"geometry stream: malformed vector list (status {int(fl[depth, 0])}, index out of range {int(fl[depth, 1])})")
+        if multi and (fl[depth + 1, 0] != 0 or fl[depth + 1, 1] != 0):
+            raise L.PccError(f"geometry stream: malformed selector list (status {int(fl[depth + 1, 0])}, selector or vector out of range "
+                             f"{int(fl[depth + 1, 1])})")
         for l, lv in enumerate(levels):
             width = words[l] - (N_CTX if l < first else N_ROWS) * 256
             got, p = [int(v) for v in back[p:p + width]], p + width
@@ -980,25 +1293,33 @@ def decode_geometry(data, device, as_set=False, reference=None, timings=None):
     """bytes -> int32 [n, 3] rows (x, y, z) in canonical order on `device`; as_set=True: the canonical pitch-1 CoordSet
     instead (no caller re-sorts).  Raises PccError on a malformed stream; never returns anything but exactly the header's n
     rows.  reference: the cloud an inter stream (0xA8, 0xAA) was coded against (same kinds of input as `encode_geometry` takes);
-    an intra stream ignores it, an inter stream without one is refused.
+    an intra stream ignores it, an inter stream without one is refused.  A stream with several references (0xAB) takes the list
+    `encode_geometry` took (or the clouds its slots name, in that order: entries that are the same object count once, a pair's
+    transform is read from the stream); any other stream decodes against the first entry of a list.
 
     Every buffer and launch is sized by what `parse_header` derived on the host (each level's nodes <= children <= n); the
     tables are derived on the device from the histograms the kernels leave there (`pcc_geom_tables`), so no level waits for
     the host.  What the payload decodes to -- rANS status, bytes outside 1..255, every level's child total and popcount
     histogram, the canonicalisation's row count -- is compared with the header's figures in ONE read at the end; until then
     a damaged payload can only produce wrong keys inside the level's cube, never a write past a buffer."""
-    hdr = parse_header(data, have_reference=reference is not None)
+    slots_in = reference_slots(reference, "decode_geometry") if isinstance(reference, (list, tuple)) else None
+    clouds = slot_sources(slots_in)[0] if slots_in is not None else ([] if reference is None else [reference])
+    hdr = parse_header(data, have_reference=reference is not None, clouds=len(clouds))
     dev = torch.device(device)
     if dev.type != "cuda":
         raise L.PccError("decode_geometry runs on a GPU (no CPU fallback)")
     transform = hdr.get("transform")
-    if transform is not None:
+    if transform is not None or "slots" in hdr:
         data = bytes(data[hdr["inner"]:])              # (the payload spans of the dictionary count from here)
     if hdr["n"] == 0:
         empty = torch.empty((0, 3), dtype=torch.int32, device=dev)
         return S.CoordSet(torch.empty(1, dtype=torch.int64, device=dev), 0, 1, S.Bounds(0, (0, 0, 0), (0, 0, 0))) if as_set else empty
     rs = None
-    if hdr.get("inter") and transform is None:
+    if slots_in is not None:                           # any other stream against a list: its first entry's cloud, as the encoder's "auto"
+        reference = slots_in[0][0]
+    if "slots" in hdr:
+        rs = _slot_sets([(clouds[src], T) for src, T in hdr["slots"]], "decode_geometry")[0]
+    elif hdr.get("inter") and transform is None:
         rs = reference_set(reference, "decode_geometry")
     elif hdr.get("inter"):
         # the warp takes the reference rows as they are -- the set of warped cells does not depend on their order -- and
@@ -1022,27 +1343,60 @@ def stream_transform(data):
     return M.RigidTransform.unpack(data[1:GLOBAL_HEADER])
 
 
-def encode_sequence(frames, intra_period=32, mode="auto", segment_nodes=SEGMENT_NODES, global_motion=None, search=None):
+def stream_slots(data):
+    """The slots of a stream with several references (0xAB) as [(source, RigidTransform or None)] -- None for a plain slot --,
+    None for any other stream.  PccError when the slot table is cut short or malformed."""
+    if len(data) < 1 or data[0] != MAGIC_MULTI:
+        return None
+    if len(data) < 2 or not 2 <= data[1] <= MAX_SLOTS:
+        raise L.PccError("geometry stream (0xab): the slot table is cut short or names a slot count outside 2..4")
+    at, out = 2, []
+    for _ in range(data[1]):
+        if at + 2 > len(data) or data[at + 1] > 1 or at + 2 + data[at + 1] * M.PACKED.size > len(data):
+            raise L.PccError("geometry stream (0xab): the slot table is cut short or holds a warped byte above 1")
+        T = M.RigidTransform.unpack(data[at + 2:at + 2 + M.PACKED.size]) if data[at + 1] else None
+        out.append((data[at], T))
+        at += 2 + data[at + 1] * M.PACKED.size
+    return out
+
+
+def encode_sequence(frames, intra_period=32, mode="auto", segment_nodes=SEGMENT_NODES, global_motion=None, search=None, references=1):
     """One stream per frame: frame i is coded against frame i - 1, every `intra_period`-th frame (0, intra_period, ...) without a
     reference.  The coder is lossless, so the decoder's previous frame is the encoder's.  mode and global_motion as in
     `encode_geometry` (global_motion applies to the frames that have a reference; `decode_sequence` reads it from the streams);
-    search as in `encode_geometry`, for the frames that have a reference."""
+    search as in `encode_geometry`, for the frames that have a reference.  references=2: a frame whose two predecessors both lie
+    inside its intra period is coded against [frame i - 1, frame i - 2] (0xAB where that is shorter under "auto"), and
+    global_motion="both" adds frame i - 1 warped by its estimate as a third slot; references=1: today's list byte for byte."""
     if int(intra_period) < 1:
         raise L.PccError(f"encode_sequence: intra_period {intra_period} must be at least 1")
-    out, prev = [], None
+    if references not in (1, 2):
+        raise L.PccError(f"encode_sequence: references {references!r} is not 1 or 2")
+    out, prev, prev2 = [], None, None
     for i, frame in enumerate(frames):
         cs = _input_set(frame)
-        ref = None if i % int(intra_period) == 0 else prev
-        out.append(encode_geometry(cs, segment_nodes=segment_nodes, reference=ref, mode=mode,
-                                   global_motion=global_motion if ref is not None else None, search=search))
-        prev = cs
+        at = i % int(intra_period)
+        ref = None if at == 0 else prev
+        if references == 2 and at >= 2 and cs.n:
+            slots = [prev, prev2]
+            if isinstance(global_motion, str) and global_motion == "both" and prev.n:
+                T = M.estimate_rigid(cs, prev)
+                if T is not None and not T.is_identity():
+                    slots.append((prev, T))
+            elif global_motion is not None:
+                raise L.PccError("encode_sequence: with references=2 global_motion is None or \"both\"")
+            out.append(encode_geometry(cs, segment_nodes=segment_nodes, reference=slots, mode=mode, search=search))
+        else:
+            out.append(encode_geometry(cs, segment_nodes=segment_nodes, reference=ref, mode=mode,
+                                       global_motion=global_motion if ref is not None else None, search=search))
+        prev, prev2 = cs, prev
     return out
 
 
 def decode_sequence(streams, device, as_set=False):
     """The frames of `encode_sequence`, in order: int32 [n, 3] tensors, or canonical CoordSets with as_set=True."""
-    out, prev = [], None
+    out, prev, prev2 = [], None, None
     for data in streams:
-        prev = decode_geometry(data, device, as_set=True, reference=prev)
+        held = [prev, prev2] if prev2 is not None else prev          # (the last two frames: what an 0xAB stream's slots name)
+        prev, prev2 = decode_geometry(data, device, as_set=True, reference=held), prev
         out.append(prev if as_set else prev.coords()[:, 1:].contiguous())
     return out

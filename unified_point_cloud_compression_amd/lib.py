@@ -172,6 +172,8 @@ SIGNATURES = {
     "pcc_geom_wide_block_bits": (C.c_int, [_p, _i64, _i32, _p, _i64, _p, _p, _p, _i32, _i32, _i32, _p, _i32, _p, _p, _p]),
     "pcc_geom_wide_pack": (C.c_int, [_p, _i64, _i32, _p, _p, _p]),
     "pcc_geom_wide_unpack": (C.c_int, [_p, _i64, _i32, _p, _p]),
+    "pcc_geom_multi_block_bits": (C.c_int, [_p, _i64, _i32, _i32, C.POINTER(_p), C.POINTER(_i64), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p),
+                                            _i32, _i32, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p]),
     "pcc_motion_warp":(C.c_int, [_p, _i64, C.POINTER(_i32), _p, _p, _p]),
     "pcc_motion_gather": (C.c_int, [_p, _i32, _i64, _p, _p, _i64, _p, _p]),
     "pcc_motion_icp_ws_bytes": (_sz, [_i64]),
